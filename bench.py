@@ -9,9 +9,15 @@ A "step" is one reference iteration: one SGD update for every user with at least
 the hot item chains solved block-wise (cu2rec_amd/csrc/blocksolve.hip), within 1e-4 test RMSE of the sequential result
 (`rmse_gap_vs_sequential` in the line, taken at equal iterations against the exact ordered mode) -- and the racy
 Hogwild modes (the reference GPU kernel's own semantics: resident launches, streaming launches) are reported beside it
-with THEIR gap.  Inputs (CSR, P, Q, biases) are resident in HBM before the timed region.  The timed region is exactly
-K steps between barrier + device synchronisation; a short region (< 0.25 s) is repeated and the MEAN region reported (all
-timed steps over all timed seconds; the median region beside it).
+with THEIR gap.  Inputs (CSR, P, Q, biases) are resident in HBM before the timed region, and the same arguments give the
+same inputs (a seeded synthetic set, the seed-42 initialisation).  The timed region is exactly K steps between barrier +
+device synchronisation, and `ms_per_step` is its wall time over K.  N > 1: a short region (< 0.25 s, or less than one
+exchange period) is repeated and the MEAN region reported (all timed steps over all timed seconds, `timed_steps`; the
+median region beside it).
+
+--dump-outputs DIR (one GPU): after the timed region, the model it leaves -- P, Q and the biases, float32 -- goes to
+DIR/<name>.npy, at most 64 MB in all (the factor matrices as fixed seeded samples of their rows when they do not fit), so
+that two builds can be compared output for output.
 
 N > 1: one process per GPU, ONE dataset whose users are sharded across the ranks (strong scaling, BASELINE.json
 configs[3]; --scaling weak gives every rank its own full-size population), trained by the C++ driver
@@ -40,7 +46,8 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 GATHER_PEAK_GBS = 8600.0     # same guide, "Indexed rows": random rows of a table that lives in the Infinity Cache
-MIN_TIMED_S = 0.25           # every reported rate rests on at least this much timed work (regions repeated: the mean; side-mode calls: the median)
+MIN_TIMED_S = 0.25           # every side-mode rate rests on at least this much timed work (the median call); N > 1: regions repeated, the mean
+DUMP_BUDGET_BYTES = 64 * 10**6  # --dump-outputs: all arrays together
 
 
 def load_dataset(name, seed, rank, barrier):
@@ -250,6 +257,27 @@ def profile_kernels(workload, factors, mode):
     return {"from": [stats, pmc], "kernels": out} if out else None
 
 
+def dump_outputs(out_dir, arrays, seed):
+    """What the timed path leaves a caller (Model.download(): P, Q, user_bias, item_bias, float32), as out_dir/<name>.npy, within
+    DUMP_BUDGET_BYTES in all.  The biases are written whole; the factor matrices whole when they fit, and otherwise the same share of
+    the rows of each, a sorted sample drawn with numpy's default_rng(seed) -- the same rows for the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    P, Q, ub, ib = arrays
+    room = DUMP_BUDGET_BYTES - ub.nbytes - ib.nbytes - 4 * 128  # (128: the .npy header)
+    share = min(1.0, room / float(P.nbytes + Q.nbytes))
+    rng = np.random.default_rng(seed)
+    out, rows = {}, {}
+    for name, a in (("user_factors", P), ("item_factors", Q)):
+        keep = int(a.shape[0] * share)
+        rows[name] = "all" if keep == a.shape[0] else "%d of %d" % (keep, a.shape[0])
+        out[name] = a if keep == a.shape[0] else a[np.sort(rng.choice(a.shape[0], keep, replace=False))]
+    out.update(user_bias=ub, item_bias=ib)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+    return {"dir": out_dir, "dtype": "float32", "shapes": {name: list(a.shape) for name, a in out.items()}, "factor_rows": rows,
+            "row_sample": "sorted, numpy default_rng(%d): user_factors first, then item_factors" % seed}
+
+
 def log(msg):
     sys.stderr.write("[bench %7.1fs] %s\n" % (time.perf_counter() - T_START, msg))
     sys.stderr.flush()
@@ -305,7 +333,12 @@ def main():
     ap.add_argument("--seed", type=int, default=20240917)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-side-modes", action="store_true", help="skip the untimed legs (Hogwild, ordered, loss kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the model after the last timed step to DIR/<name>.npy (one GPU only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and max(args.gpus, int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        ap.error("--dump-outputs writes one model: run it with --gpus 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` with no launcher: start the N ranks as FRESH child processes (torch.distributed.run, one
@@ -457,21 +490,26 @@ def main():
 
     regions = [timed_region(job, mode, it)]
     it += args.steps
-    # A short region is mostly launch + synchronisation noise: every region is EXACTLY K steps, and regions are repeated until
-    # a quarter of a second has been timed in all (at least 5 when one region is shorter than that, at most 400).  Reported: ALL
-    # timed steps over ALL timed seconds, i.e. the MEAN region -- calls of K steps run out of schedule windows of 64 iterations
-    # (ordered.hip), so one region in three carries the next window's schedule kernels and the others none, and with several ranks
-    # one region in sync_every / K carries an exchange: the median region (on the line as timed_region_s_median) would pick the
-    # cheap ones.
-    first_all = reduce_max([regions[0][0]])[0]  # every rank must take the same decision: the regions are bracketed by barriers
-    n_regions = 1 if first_all >= MIN_TIMED_S else int(min(400, max(5, np.ceil(MIN_TIMED_S / max(first_all, 1e-6)))))
-    if world > 1:  # (whole exchange periods: the mean region then carries the exchanges' true share)
-        per_period = int(np.ceil(info["sync_every"] / max(args.steps, 1)))
+    # N = 1: the timed region is the K steps asked for, no more -- the caller sizes K (a region of a fraction of a second is mostly
+    # launch + synchronisation noise; ms_per_step on the line tells how many steps a given length needs).
+    # N > 1: every region is EXACTLY K steps, and regions are repeated until a quarter of a second has been timed in all (at least 5
+    # when one region is shorter than that, at most 400) and a whole exchange period is covered.  Reported: ALL timed steps over ALL
+    # timed seconds, i.e. the MEAN region -- calls of K steps run out of schedule windows of 64 iterations (ordered.hip), so one
+    # region in three carries the next window's schedule kernels and the others none, and one region in sync_every / K carries an
+    # exchange: the median region (on the line as timed_region_s_median) would pick the cheap ones.
+    n_regions = 1
+    if world > 1:
+        first_all = reduce_max([regions[0][0]])[0]  # every rank must take the same decision: the regions are bracketed by barriers
+        n_regions = 1 if first_all >= MIN_TIMED_S else int(min(400, max(5, np.ceil(MIN_TIMED_S / max(first_all, 1e-6)))))
+        per_period = int(np.ceil(info["sync_every"] / max(args.steps, 1)))  # (the mean region then carries the exchanges' true share)
         n_regions = int(min(400, max(n_regions, per_period) if per_period <= 400 else n_regions))
     for _ in range(n_regions - 1):
         regions.append(timed_region(job, mode, it))
         it += args.steps
     check(L.cu2rec_check_faults())
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, model.download(), args.seed)
+        log("outputs of the last timed step written to %s" % args.dump_outputs)
     wall_all = reduce_max([r[0] for r in regions])  # per region: the slowest rank's wall time
     elapsed = float(np.mean(wall_all))
     elapsed_dev = float(np.mean([r[1] for r in regions]))
@@ -687,7 +725,7 @@ def main():
                    "hogwild": "sgd_resident_kernel / sgd_hogwild_kernel", "ordered": "sgd_ordered_kernel", "serial": "sgd_serial_kernel"}
         line = {
             "metric": "ratings/sec (SGD updates/sec)", "value": value, "unit": "updates/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "timed_steps": len(regions) * args.steps,
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%s-shape synthetic ratings (users %d, items %d, train nnz %d, test nnz %d%s), f=%d, lr .01, reg .02, "
                                    "mode %s" % (args.workload, full_train.rows, full_train.cols, full_train.nnz, full_test.nnz,
@@ -724,6 +762,8 @@ def main():
                                  "the launch stream; the mode's sequential chains are latency bound, not bandwidth bound: DESIGN.md section 4"},
         }
         line.update(side)
+        if args.dump_outputs:
+            line["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(train, test, f, hyper)
         print(json.dumps(line), flush=True)

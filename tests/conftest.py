@@ -8,8 +8,40 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-# the reference's bundled MovieLens latest-small file; exists only in the build container
-ML_SMALL = "/root/reference/ratings_mapped.csv"
+# the reference's bundled ratings_mapped.csv: MovieLens latest-small (GroupLens, https://grouplens.org/datasets/movielens/; 610 users,
+# 9724 items, 100836 ratings) with user and item ids mapped to 1..n, the file the golden vectors were generated from.  Stored as its
+# columns (ratings per user, item ids, ratings in half stars; an xz-compressed .npz) and written back out byte for byte on first use.
+ML_SMALL_COLUMNS = os.path.join(GOLDEN, "ml_small_ratings.npz.xz")
+ML_SMALL_SHA256 = "efffb1473e9c25f0ee21fa712fd3b6fa38fc87d371bc177d6b887a7a5a33ab11"
+
+
+_ML_SMALL_PATH = []
+
+
+def ml_small():
+    """Path of the ML_SMALL csv, written from ML_SMALL_COLUMNS once per process into a temporary directory removed at exit."""
+    if _ML_SMALL_PATH:
+        return _ML_SMALL_PATH[0]
+    import atexit
+    import hashlib
+    import io
+    import lzma
+    import shutil
+    import tempfile
+    import numpy as np
+    with open(ML_SMALL_COLUMNS, "rb") as fh:
+        z = np.load(io.BytesIO(lzma.decompress(fh.read())))
+    users = np.repeat(np.arange(1, len(z["ratings_per_user"]) + 1), z["ratings_per_user"])
+    raw = ("userId,itemId,rating\n" + "".join("%d,%d,%.1f\n" % (u, i, h / 2) for u, i, h in zip(users, z["items"].tolist(),
+                                                                                                z["half_stars"].tolist()))).encode()
+    assert hashlib.sha256(raw).hexdigest() == ML_SMALL_SHA256, "tests/golden/ml_small_ratings.npz.xz does not decode to ML_SMALL"
+    tmp = tempfile.mkdtemp(prefix="cu2rec_ml_small_")
+    atexit.register(shutil.rmtree, tmp, True)
+    path = os.path.join(tmp, "ratings_mapped.csv")
+    with open(path, "wb") as fh:
+        fh.write(raw)
+    _ML_SMALL_PATH.append(path)
+    return path
 
 
 def pytest_configure(config):
@@ -17,7 +49,7 @@ def pytest_configure(config):
 
 
 def golden_path(name):
-    return ML_SMALL if name == "ML_SMALL" else os.path.join(GOLDEN, name)
+    return ml_small() if name == "ML_SMALL" else os.path.join(GOLDEN, name)
 
 
 @pytest.fixture(scope="session")

@@ -257,6 +257,35 @@ def test_blocksolve_full_shape_ml1m_f50_is_the_oracle_bit_for_bit():
         np.testing.assert_array_equal(g, w)
 
 
+def test_bench_times_exactly_k_steps_and_dumps_the_model_they_leave(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` on the ML-1M shape, where the timed mode IS the ordered walk: the line
+    counts exactly K timed steps and W + K iterations, and DIR holds the model after the last of them -- the oracle's, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    warmup, steps, f = 2, 3, 50
+    out = tmp_path / "dump"
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--workload", "ml-1m", "--factors", str(f), "--no-cpu-baseline", "--no-side-modes", "--dump-outputs", str(out)],
+                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == steps and line["timed_steps"] == steps and line["timed_regions"] == 1
+    assert line["iterations_run"] == warmup + steps and line["ms_per_step"] > 0
+    assert line["dumped_outputs"]["factor_rows"] == {"user_factors": "all", "item_factors": "all"}
+    tr, _ = bench.load_dataset("ml-1m", 20240917, 0, lambda: None)
+    state = orc.init_model(tr.rows, tr.cols, f)
+    orc.sgd_iterations(_as_orc(tr), *state, tr.global_bias, HYPER, 42, 0, warmup + steps, dot_order=orc.DOT_TREE16)
+    for name, want in zip(("user_factors", "item_factors", "user_bias", "item_bias"), state):
+        got = np.load(out / (name + ".npy"))
+        assert got.dtype == np.float32, name
+        np.testing.assert_array_equal(got, want, err_msg=name)
+
+
 @pytest.mark.parametrize("policy,name", [(2, "resident"), (0, "streaming")])
 def test_hogwild_mid_trajectory_gap_to_sequential_stays_bounded_at_full_shape(policy, name):
     """A regression bound on the racy modes while the model is still moving (popular items lose most of their updates to the

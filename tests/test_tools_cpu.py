@@ -93,3 +93,34 @@ def test_forced_segments_and_decay_replay_follow_the_reference_rule():
     assert [s[0] for s in seg] == [c[0] for c in checks]
     lrs = [s[1] for s in seg]
     assert lrs[:5] == [float(np.float32(0.01))] * 5 and abs(lrs[5] - 0.002) < 1e-9 and abs(lrs[6] - 0.002) < 1e-9
+
+
+def test_bench_dump_outputs_keeps_the_budget_with_a_fixed_row_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the biases whole, the factor matrices whole when they fit and otherwise the same share of the rows of
+    each -- the same rows for the same seed, another sample for another -- float32 files within the budget in all."""
+    import bench
+    rng = np.random.RandomState(3)
+    P, Q = rng.rand(1000, 16).astype(np.float32), rng.rand(300, 16).astype(np.float32)
+    ub, ib = rng.rand(1000).astype(np.float32), rng.rand(300).astype(np.float32)
+    names = ("user_factors", "item_factors", "user_bias", "item_bias")
+
+    def dump(d, seed):
+        info = bench.dump_outputs(str(tmp_path / d), (P, Q, ub, ib), seed)
+        return info, {n: np.load(tmp_path / d / (n + ".npy")) for n in names}
+
+    info, whole = dump("whole", 1)
+    assert info["factor_rows"] == {"user_factors": "all", "item_factors": "all"}
+    for n, want in zip(names, (P, Q, ub, ib)):
+        assert whole[n].dtype == np.float32 and np.array_equal(whole[n], want), n
+    budget = (P.nbytes + Q.nbytes) // 2 + ub.nbytes + ib.nbytes + 4 * 128
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    info, a = dump("a", 7)
+    _, b = dump("b", 7)
+    _, c = dump("c", 8)
+    assert sum(os.path.getsize(tmp_path / "a" / (n + ".npy")) for n in names) <= budget
+    assert a["user_factors"].shape == (500, 16) and a["item_factors"].shape == (150, 16), info
+    assert np.array_equal(a["user_bias"], ub) and np.array_equal(a["item_bias"], ib)
+    for n, full in (("user_factors", P), ("item_factors", Q)):
+        assert np.array_equal(a[n], b[n]) and not np.array_equal(a[n], c[n]), n
+        rows = [int(np.flatnonzero((full == r).all(axis=1))[0]) for r in a[n]]
+        assert rows == sorted(set(rows)), n  # rows of the full matrix, each once, in order
