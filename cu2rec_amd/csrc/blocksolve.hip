@@ -1737,7 +1737,7 @@ void bs_launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream
     else if (sw <= 8) launch_solve<8>(a, it, stream);
     else if (sw <= 12) launch_solve<12>(a, it, stream);
     else if (sw <= 16) launch_solve<16>(a, it, stream);
-    else fail(CU2REC_EUNSUPPORTED, "block-solve mode is compiled for n_factors <= 256");
+    else fail(CU2REC_EUNSUPPORTED, "block-solve mode is compiled for n_factors <= 252");
 }
 
 void bs_launch_update(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {

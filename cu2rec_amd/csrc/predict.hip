@@ -7,7 +7,10 @@
 // the 32 user rows are staged once in LDS and shared by four wavefronts, each of which stages 32 item rows of its own
 // (coalesced 128-byte pieces, odd row stride so that the operand reads -- one row per lane -- are conflict free) and
 // accumulates one 32x32 tile.  Lane (r = l & 31, h = l >> 5) feeds half h of row r as A (users) and as B (items); the
-// contraction index pairs column c of half 0 with column c of half 1, which only reorders the sum.
+// contraction index pairs column c of half 0 with column c of half 1, which only reorders the sum.  Up to 63 float4 slots
+// (n_factors <= 252) the whole row is staged at once; wider rows would need more than the 160 KiB of LDS a workgroup can
+// have (5 tiles x 32 rows x 65 slots x 16 B = 166,400 B at 64 slots), so they are staged and contracted in chunks of 32
+// slots, one barrier between chunks, all accumulating into the same tile (another association of the same sum).
 //
 // Ranking = every item a user has NOT rated, best predicted rating first: rated items are masked with -inf, then one
 // segmented radix sort (descending) over all users of a batch; the first k per user are the recommendations.
@@ -28,64 +31,42 @@ namespace cu2rec {
 namespace {
 
 constexpr int kTile = 32;
+constexpr size_t kMaxLds = 160 * 1024;  // LDS of one workgroup on gfx950
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
-// 32 rows of `nslots` float4 from a row-major matrix into an LDS tile [32][RS], by one wavefront: 8 lanes x 16 bytes per
-// row piece, 8 rows per pass; rows beyond n_rows are zero.  Loads are unconditional at clamped addresses.
+// 32 rows x slots [slot0, slot0 + n) of a row-major matrix into an LDS tile [32][RS], by one wavefront: 8 lanes x 16 bytes
+// per row piece, 8 rows per pass; rows beyond n_rows are zero.  Loads are unconditional at clamped addresses.
 __device__ __forceinline__ void stage_rows(float4 *tile, const float *__restrict__ base, int ld, int first_row, int n_rows,
-                                           int nslots, int RS, int lane) {
+                                           int slot0, int n, int RS, int lane) {
     const int rsub = lane >> 3, cs = lane & 7;
-    const int nch = (nslots + 7) >> 3;
+    const int nch = (n + 7) >> 3;
     for (int c = 0; c < nch; ++c) {
         float4 v[4];
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int row = min(first_row + 8 * p + rsub, n_rows - 1);
-            v[p] = reinterpret_cast<const float4 *>(base + static_cast<size_t>(row) * ld)[min(8 * c + cs, nslots - 1)];
+            v[p] = reinterpret_cast<const float4 *>(base + static_cast<size_t>(row) * ld)[slot0 + min(8 * c + cs, n - 1)];
         }
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             const int slot = 8 * c + cs;
-            if (slot < nslots) tile[(8 * p + rsub) * RS + slot] = first_row + 8 * p + rsub < n_rows ? v[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (slot < n) tile[(8 * p + rsub) * RS + slot] = first_row + 8 * p + rsub < n_rows ? v[p] : make_float4(0.f, 0.f, 0.f, 0.f);
         }
     }
 }
 
-__global__ __launch_bounds__(256) void scores_kernel(const float *__restrict__ P, int ldp, const float *__restrict__ user_bias,
-                                                     int n_users, const float *__restrict__ Q, int ldq,
-                                                     const float *__restrict__ item_bias, int n_items, float global_bias,
-                                                     int nslots, float *__restrict__ scores) {
-    extern __shared__ float4 smem[];
-    const int RS = nslots | 1;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int user0 = blockIdx.y * kTile, item0 = (blockIdx.x * 4 + wave) * kTile;
-    float4 *utile = smem, *itile = smem + (1 + wave) * kTile * RS;
-    // wave w stages rows 8 w .. 8 w + 7 of the user tile (all four together: 32 rows) and its own 32 item rows
-    {
-        const int rsub = lane >> 3, cs = lane & 7;
-        for (int c = 0; c < (nslots + 7) >> 3; ++c) {
-            const int row = min(user0 + 8 * wave + rsub, n_users - 1), slot = 8 * c + cs;
-            const float4 v = reinterpret_cast<const float4 *>(P + static_cast<size_t>(row) * ldp)[min(slot, nslots - 1)];
-            if (slot < nslots) utile[(8 * wave + rsub) * RS + slot] = user0 + 8 * wave + rsub < n_users ? v : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    }
-    if (item0 < n_items) stage_rows(itile, Q, ldq, item0, n_items, nslots, RS, lane);
-    __syncthreads();
-    if (item0 >= n_items) return;
-    const int r = lane & 31, h = lane >> 5;
-    const int S0 = (nslots + 1) >> 1;
-    f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+// acc += U[32 x 4n] * I[32 x 4n]^T over the n slots staged in utile / itile
+__device__ __forceinline__ void contract(f32x16 &acc, const float4 *utile, const float4 *itile, int RS, int n, int r, int h) {
+    const int S0 = (n + 1) >> 1;
     for (int c = 0; c < S0; c += 2) {
         float4 a4[2], b4[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int slot = h * S0 + c + i;
-            const bool ok = c + i < S0 && slot < nslots;
-            const float4 ua = utile[r * RS + min(slot, nslots - 1)], ib = itile[r * RS + min(slot, nslots - 1)];
+            const bool ok = c + i < S0 && slot < n;
+            const float4 ua = utile[r * RS + min(slot, n - 1)], ib = itile[r * RS + min(slot, n - 1)];
             a4[i] = ok ? ua : make_float4(0.f, 0.f, 0.f, 0.f);
             b4[i] = ok ? ib : make_float4(0.f, 0.f, 0.f, 0.f);
         }
@@ -97,6 +78,41 @@ __global__ __launch_bounds__(256) void scores_kernel(const float *__restrict__ P
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[i].w, b4[i].w, acc, 0, 0, 0);
         }
     }
+}
+
+// chunk: slots staged at once (nslots itself up to 63, else 32); every wave reaches every barrier, a wave without items only
+// stages its part of the user tile
+__global__ __launch_bounds__(256) void scores_kernel(const float *__restrict__ P, int ldp, const float *__restrict__ user_bias,
+                                                     int n_users, const float *__restrict__ Q, int ldq,
+                                                     const float *__restrict__ item_bias, int n_items, float global_bias,
+                                                     int nslots, int chunk, float *__restrict__ scores) {
+    extern __shared__ float4 smem[];
+    const int RS = chunk | 1;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int user0 = blockIdx.y * kTile, item0 = (blockIdx.x * 4 + wave) * kTile;
+    const bool active = item0 < n_items;
+    float4 *utile = smem, *itile = smem + (1 + wave) * kTile * RS;
+    const int r = lane & 31, h = lane >> 5;
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    for (int slot0 = 0; slot0 < nslots; slot0 += chunk) {
+        const int n = min(chunk, nslots - slot0);
+        if (slot0 > 0) __syncthreads();  // every wave is done reading the previous chunk
+        // wave w stages rows 8 w .. 8 w + 7 of the user tile (all four together: 32 rows) and its own 32 item rows
+        {
+            const int rsub = lane >> 3, cs = lane & 7;
+            for (int c = 0; c < (n + 7) >> 3; ++c) {
+                const int row = min(user0 + 8 * wave + rsub, n_users - 1), slot = 8 * c + cs;
+                const float4 v = reinterpret_cast<const float4 *>(P + static_cast<size_t>(row) * ldp)[slot0 + min(slot, n - 1)];
+                if (slot < n) utile[(8 * wave + rsub) * RS + slot] = user0 + 8 * wave + rsub < n_users ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        if (active) stage_rows(itile, Q, ldq, item0, n_items, slot0, n, RS, lane);
+        __syncthreads();
+        if (active) contract(acc, utile, itile, RS, n, r, h);
+    }
+    if (!active) return;
     const int item = item0 + r;  // accumulator column = lane & 31
     if (item >= n_items) return;
     const float ibv = item_bias[item];
@@ -134,11 +150,14 @@ __global__ __launch_bounds__(256) void take_top_kernel(const float *__restrict__
 
 void launch_scores(const DeviceModel &m, int user0, int n_users, float *scores, hipStream_t stream) {
     const int nslots = (m.n_factors + 3) / 4;
-    const size_t lds = static_cast<size_t>(5) * kTile * (nslots | 1) * 16;
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(scores_kernel));
+    const int chunk = nslots <= 63 ? nslots : 32;  // one chunk up to 252 factors: those scores stay what they were
+    const size_t lds = static_cast<size_t>(5) * kTile * (chunk | 1) * sizeof(float4);
+    if (lds > kMaxLds) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_scores: the score tiles need more LDS than a workgroup has");
+    ensure_max_dynamic_lds(reinterpret_cast<const void *>(scores_kernel), kMaxLds);
     const dim3 grid((m.cols + 4 * kTile - 1) / (4 * kTile), (n_users + kTile - 1) / kTile);
     hipLaunchKernelGGL(scores_kernel, grid, dim3(256), lds, stream, m.P.ptr + static_cast<size_t>(user0) * m.ld, m.ld,
-                       m.user_bias.ptr + user0, n_users, m.Q.ptr, m.ldq, m.item_bias.ptr, m.cols, m.global_bias, nslots, scores);
+                       m.user_bias.ptr + user0, n_users, m.Q.ptr, m.ldq, m.item_bias.ptr, m.cols, m.global_bias, nslots, chunk,
+                       scores);
     CU2REC_HIP(hipGetLastError());
 }
 

@@ -382,8 +382,9 @@ int cu2rec_model_loss(const cu2rec_model *m, const cu2rec_csr *ratings, double *
 int cu2rec_model_scores(const cu2rec_model *m, float *scores_device /* rows * cols floats */, void *stream);
 int cu2rec_model_scores_host(const cu2rec_model *m, float *scores_host /* rows * cols floats */);
 /* For every user the k best items it has NOT rated, best predicted rating first.  rated: a CSR whose row u holds user
- * u's ratings (NULL: nothing is excluded).  items_out / scores_out: host arrays of rows * k entries; a user with fewer
- * than k unrated items gets -1 / NaN padding. */
+ * u's ratings (NULL: nothing is excluded; users past its last row are not masked).  items_out / scores_out: host arrays of
+ * rows * k entries; a user with fewer than k unrated items gets -1 / NaN padding.  Items with equal scores come out in
+ * ascending item index (the sort is stable). */
 int cu2rec_model_recommend(const cu2rec_model *m, const cu2rec_csr *rated, int k, int *items_out, float *scores_out);
 
 /* ------------------------------------------------------------------------------------------
