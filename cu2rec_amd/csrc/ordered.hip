@@ -942,6 +942,12 @@ int OrderedSchedule::blocks_bound() const {
 void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t stream, bool blocksolve) {
     if (n_active == 0) return;
     if (blocksolve && n_hot_bs == 0) blocksolve = false;  // nothing to solve block-wise: the ordered walk, bit for bit
+    // A decay factor a = 1 - lr Q_reg or c = 1 - lr item_bias_reg at or below zero has no logarithm: the cross-tile terms
+    // exp2(d * log2 a) would be NaN (0 * -inf at d = 0).  The sequential update is still defined there: the ordered walk, bit for bit.
+    // (In double, as the decay tables are.)
+    if (blocksolve && (1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.q_reg) <= 0.0 ||
+                       1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.ib_reg) <= 0.0))
+        blocksolve = false;
     // The workspace (key / value buffers, block records, events) exists once: a call on another stream than the last one
     // starts behind that call's end.
     if (have_last && last_stream != stream) CU2REC_HIP(hipStreamWaitEvent(stream, ev_last, 0));

@@ -175,7 +175,9 @@ typedef enum cu2rec_sgd_mode {
      * the default of bin/mf and of bench.py, the mode certified against the north star's 1e-4 RMSE bar.  Equal to the
      * sequential result up to float rounding (sums are associated differently), NOT bit for bit: tests pin it at
      * |test RMSE - oracle| <= 1e-4 after 1,000 iterations of the ML-20M shape.  n_factors <= 252.  Needs a
-     * cu2rec_schedule like CU2REC_SGD_ORDERED. */
+     * cu2rec_schedule like CU2REC_SGD_ORDERED.  A call whose decay factors 1 - learning_rate * Q_reg or
+     * 1 - learning_rate * item_bias_reg (in double) are at or below zero has no block form: it runs the ordered walk and
+     * is the sequential result bit for bit. */
     CU2REC_SGD_BLOCKSOLVE = 4
 } cu2rec_sgd_mode;
 

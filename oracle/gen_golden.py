@@ -17,6 +17,8 @@ What is produced
                             is replaced by orc_sample(); everything else -- reader, CSR, init,
                             the update arithmetic, the float-accumulated loss -- is the
                             reference's own compiled code.
+  ref_tier3_band.json       the unmodified reference's run-to-run band (random_device sampler: every
+                            run differs, so a regeneration rewrites it; --no-band leaves it as it is).
 """
 import base64
 import hashlib
@@ -108,7 +110,7 @@ def pack(arr, full):
     return d
 
 
-def main():
+def main(band=True):
     os.makedirs(GOLD, exist_ok=True)
     write_toys()
     mf_cpu = os.path.join(HERE, "_ref", "mf_cpu")
@@ -157,6 +159,15 @@ def main():
             ("ML_SMALL", "ML_SMALL", [0, 5, 50, 0.01, 42, 0.02, 0.02, 0.02, 0.02]),
             ("ML_SMALL", "ML_SMALL", [0, 3, 100, 0.01, 42, 0.02, 0.02, 0.02, 0.02]),
         ]
+    # four distinct regularisers and a learning rate other than 0.01: a mix-up of any two of the five constants changes the bits
+    grid += [
+        ("toy_ratings.csv", "toy_ratings2.csv", [0, 20, 10, 0.05, 42, 0.03, 0.07, 0.11, 0.19]),
+        ("toy_ratings3.csv", "toy_ratings2.csv", [0, 10, 50, 0.05, 42, 0.03, 0.07, 0.11, 0.19]),
+        ("toy_ratings.csv", "toy_ratings2.csv", [7, 20, 10, 0.05, 42, 0.03, 0.07, 0.11, 0.19]),   # resumed stream
+        ("toy_ratings.csv", "toy_ratings2.csv", [0, 2, 4, 0.5, 42, 0.02, 2.0, 0.02, 2.0]),       # lr * Q_reg = lr * item_bias_reg = 1
+    ]
+    if have_ml:
+        grid += [("ML_SMALL", "ML_SMALL", [0, 20, 10, 0.05, 42, 0.03, 0.07, 0.11, 0.19])]
     with tempfile.TemporaryDirectory() as td:
         for train, test, fields in grid:
             tr = REF_ML_SMALL if train == "ML_SMALL" else os.path.join(GOLD, train)
@@ -179,7 +190,7 @@ def main():
     # std::random_device per update (mf_sequential.cu:109-112: no seed reaches it; inclusive range), so identical runs differ;
     # the oracle's trajectory (counter-based sampler, half-open range) must lie inside that band, statistically
     # (tests/test_oracle_golden.py::test_oracle_trajectory_lies_in_the_unmodified_reference_band).
-    if have_ml:
+    if have_ml and band:
         fields = [0, 500, 10, 0.01, 42, 0.02, 0.02, 0.02, 0.02]
         runs = [run_ref(mf_cpu, fields, REF_ML_SMALL, REF_ML_SMALL) for _ in range(TIER3_RUNS)]
         band = {}
@@ -202,4 +213,4 @@ TIER3_RUNS = 8
 
 
 if __name__ == "__main__":
-    main()
+    main(band="--no-band" not in sys.argv[1:])

@@ -81,7 +81,7 @@ def test_rccl_world1_allreduce_in_the_loop(monkeypatch):
 
 # ---- two ranks on one GPU, the all-reduce through gloo ---------------------------------------------------------------
 
-def _two_rank_worker(rank, world, port, out_dir, merge):
+def _two_rank_worker(rank, world, port, out_dir, merge, hyper=HYPER):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     sys.path.insert(0, ROOT)
     import torch
@@ -106,7 +106,8 @@ def _two_rank_worker(rank, world, port, out_dir, merge):
             return 1
 
     tr, te = synth.make_ratings(500, 150, 12000, min_degree=3, seed=21)
-    cfg = cu.default_config(total_iterations=18, n_factors=24, check_error=9, learning_rate=0.01)
+    cfg = cu.default_config(total_iterations=18, n_factors=24, check_error=9, learning_rate=hyper[0], P_reg=hyper[1], Q_reg=hyper[2],
+                            user_bias_reg=hyper[3], item_bias_reg=hyper[4])
     comm = sharded.Comm(rank, world, allreduce=allreduce)
     P, Q, losses, ub, ib, (u0, u1), stats = sharded.train_sharded(comm, tr, te, cfg, mode="ordered", sync_every=3, merge=merge,
                                                                   verbose=False)
@@ -121,9 +122,18 @@ def test_two_ranks_one_gpu_cpp_driver_matches_oracle(tmp_path, merge):
     """cu2rec_train_sharded on two ranks (ordered mode: deterministic per shard), exchanges every 3 iterations, against the
     oracle running both shards and merging with numpy: P slices and user biases bit for bit, the item side within one
     ulp-sized rounding of the merge (2e-7), identical replicas, identical logged losses on both ranks."""
+    _two_ranks_against_the_oracle(tmp_path, merge, HYPER)
+
+
+def test_two_ranks_one_gpu_cpp_driver_with_distinct_hyperparameters_matches_oracle(tmp_path):
+    """The same with every constant distinct (one merge): the configuration's five fields reach both ranks' kernels unmixed."""
+    _two_ranks_against_the_oracle(tmp_path, "weighted", (0.01, 0.015, 0.03, 0.045, 0.08))
+
+
+def _two_ranks_against_the_oracle(tmp_path, merge, hyper):
     import torch.multiprocessing as mp
     port = 29500 + (os.getpid() % 2000)
-    mp.spawn(_two_rank_worker, args=(2, port, str(tmp_path), merge), nprocs=2, join=True)
+    mp.spawn(_two_rank_worker, args=(2, port, str(tmp_path), merge, hyper), nprocs=2, join=True)
     r = [np.load(os.path.join(str(tmp_path), "r%d.npz" % k)) for k in range(2)]
     tr, te = synth.make_ratings(500, 150, 12000, min_degree=3, seed=21)
     f, sync, total = 24, 3, 18
@@ -165,7 +175,7 @@ def test_two_ranks_one_gpu_cpp_driver_matches_oracle(tmp_path, merge):
         while it <= seg_end:
             n = min(seg_end + 1 - it, sync - since)
             for k in range(2):
-                orc.sgd_iterations(masked[k], oP[k], oQ[k], oub[k], oib[k], tr.global_bias, HYPER, 42, it, n, dot_order=orc.DOT_TREE16)
+                orc.sgd_iterations(masked[k], oP[k], oQ[k], oub[k], oib[k], tr.global_bias, hyper, 42, it, n, dot_order=orc.DOT_TREE16)
             it += n
             since += n
             if since >= sync:

@@ -197,19 +197,28 @@ def test_cpp_driver_two_ranks_gloo_against_the_merge_algebra(tmp_path, merge):
 def test_cpp_driver_one_rank_is_the_oracle_bit_for_bit_and_frozen_items_terminate():
     """World 1 through the C++ driver: no exchange ever, the result is the engine's; and with update_items == 0 a run longer
     than a period terminates (the period counter starts over although nothing is exchanged)."""
+    _one_rank_against_the_oracle(HYPER)
+
+
+def test_cpp_driver_one_rank_with_distinct_hyperparameters_is_the_oracle_bit_for_bit():
+    """The same with every constant distinct: a mix-up of two of them on the way from the driver to the engine changes bits."""
+    _one_rank_against_the_oracle((0.01, 0.015, 0.03, 0.045, 0.08))
+
+
+def _one_rank_against_the_oracle(hyper):
     dist.init_process_group("gloo", rank=0, world_size=1, init_method="tcp://127.0.0.1:%d" % (38000 + os.getpid() % 2000))
     try:
         tr, te = synth.make_ratings(60, 30, 600, min_degree=2, seed=2)
         f = 8
         job = HostJob(0, 1, tr, f, orc.init_model(tr.rows, tr.cols, f), 0, tr.rows, 3, "adaptive")
-        job.run(HYPER, 42, 0, 10)
+        job.run(hyper, 42, 0, 10)
         want = orc.init_model(tr.rows, tr.cols, f)
-        orc.sgd_iterations(orc.CSR(tr.indptr, tr.indices, tr.data, tr.rows, tr.cols), *want, tr.global_bias, HYPER, 42, 0, 10, dot_order=orc.DOT_TREE16)
+        orc.sgd_iterations(orc.CSR(tr.indptr, tr.indices, tr.data, tr.rows, tr.cols), *want, tr.global_bias, hyper, 42, 0, 10, dot_order=orc.DOT_TREE16)
         for g, w in zip((job.P, job.Q, job.ub, job.ib), want):
             np.testing.assert_array_equal(g, w)
         assert job.info()["exchanges"] == 0 and job.loss(te, 0, te.rows)["n"] == te.nnz
         q_before = job.Q.copy()
-        job.run(HYPER, 42, 10, 25, update_items=False)  # 8 periods of 3 + 1
+        job.run(hyper, 42, 10, 25, update_items=False)  # 8 periods of 3 + 1
         np.testing.assert_array_equal(job.Q, q_before)
         assert job.info()["exchanges"] == 0
         job.close()
