@@ -697,50 +697,4 @@ int cu2rec_model_loss(const cu2rec_model *m, const cu2rec_csr *ratings, double *
     });
 }
 
-int cu2rec_items_delta_pack(const float *Q, const float *item_bias, const float *Q_base, const float *ib_base,
-                            int n_cols, int ldq, float *buf, void *stream) {
-    return guarded([&] {
-        require(Q && item_bias && Q_base && ib_base && buf && n_cols >= 0 && ldq > 0, "bad argument");
-        require_device();
-        if (n_cols == 0) return;
-        launch_items_delta_pack(Q, item_bias, Q_base, ib_base, n_cols, ldq, buf, as_stream(stream));
-        CU2REC_HIP(hipGetLastError());
-    });
-}
-
-int cu2rec_items_delta_apply_overlapped(float *Q, float *item_bias, float *Q_base, float *ib_base, const float *Q_snap,
-                                        const float *ib_snap, int n_cols, int ldq, const float *buf, float scale,
-                                        void *stream) {
-    return guarded([&] {
-        require(Q && item_bias && Q_base && ib_base && Q_snap && ib_snap && buf && n_cols >= 0 && ldq > 0, "bad argument");
-        require_device();
-        if (n_cols == 0) return;
-        launch_items_delta_apply_overlapped(Q, item_bias, Q_base, ib_base, Q_snap, ib_snap, n_cols, ldq, buf, scale,
-                                            as_stream(stream));
-        CU2REC_HIP(hipGetLastError());
-    });
-}
-
-int cu2rec_items_delta_pack_weighted(const float *Q, const float *item_bias, const float *Q_base, const float *ib_base,
-                                     const float *item_weight, int n_cols, int ldq, float *buf, void *stream) {
-    return guarded([&] {
-        require(Q && item_bias && Q_base && ib_base && item_weight && buf && n_cols >= 0 && ldq > 0, "bad argument");
-        require_device();
-        if (n_cols == 0) return;
-        launch_items_delta_pack_weighted(Q, item_bias, Q_base, ib_base, item_weight, n_cols, ldq, buf, as_stream(stream));
-        CU2REC_HIP(hipGetLastError());
-    });
-}
-
-int cu2rec_items_delta_apply(float *Q, float *item_bias, float *Q_base, float *ib_base, int n_cols, int ldq,
-                             const float *buf, float scale, void *stream) {
-    return guarded([&] {
-        require(Q && item_bias && Q_base && ib_base && buf && n_cols >= 0 && ldq > 0, "bad argument");
-        require_device();
-        if (n_cols == 0) return;
-        launch_items_delta_apply(Q, item_bias, Q_base, ib_base, n_cols, ldq, buf, scale, as_stream(stream));
-        CU2REC_HIP(hipGetLastError());
-    });
-}
-
 }  // extern "C"

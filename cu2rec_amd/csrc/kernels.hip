@@ -16,7 +16,7 @@
 //   pingpong_claim_kernel + sgd_pingpong_kernel   sgd_update with its Q_target / item_is_updated semantics kept
 //   loss_fused_kernel                       loss_kernel      loss.cu:19-35  + total_loss_kernel<B> :58-128 (x2)
 //   error_metrics_kernel                    total_loss_kernel<B>  loss.cu:58-128 on an explicit array
-//   items_delta_*                           (new: multi-GPU item-factor exchange)
+//   items_wire_pack / _apply_kernel         (new: multi-GPU item-factor exchange)
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
@@ -263,73 +263,8 @@ __global__ __launch_bounds__(kBlock) void sample_pairs_build_kernel(const int *_
         pairs[k] = make_uint2(static_cast<unsigned>(indices[k]), __float_as_uint(data[k]));
 }
 
-// ---- multi-GPU item-factor exchange helpers -------------------------------------------------
-__global__ __launch_bounds__(kBlock) void items_delta_pack_kernel(const float *__restrict__ Q,
-                                                                  const float *__restrict__ ib,
-                                                                  const float *__restrict__ Q_base,
-                                                                  const float *__restrict__ ib_base, size_t nq,
-                                                                  int n_cols, float *__restrict__ buf) {
-    const size_t total = nq + static_cast<size_t>(n_cols);
-    for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < total;
-         i += static_cast<size_t>(gridDim.x) * kBlock)
-        buf[i] = i < nq ? Q[i] - Q_base[i] : ib[i - nq] - ib_base[i - nq];
-}
-
-__global__ __launch_bounds__(kBlock) void items_delta_pack_weighted_kernel(const float *__restrict__ Q,
-                                                                           const float *__restrict__ ib,
-                                                                           const float *__restrict__ Q_base,
-                                                                           const float *__restrict__ ib_base,
-                                                                           const float *__restrict__ weight, size_t nq,
-                                                                           int n_cols, int ldq, float *__restrict__ buf) {
-    const size_t total = nq + static_cast<size_t>(n_cols);
-    for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < total;
-         i += static_cast<size_t>(gridDim.x) * kBlock) {
-        if (i < nq) buf[i] = weight[i / ldq] * (Q[i] - Q_base[i]);
-        else buf[i] = weight[i - nq] * (ib[i - nq] - ib_base[i - nq]);
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void items_delta_apply_kernel(float *__restrict__ Q, float *__restrict__ ib,
-                                                                   float *__restrict__ Q_base,
-                                                                   float *__restrict__ ib_base, size_t nq, int n_cols,
-                                                                   const float *__restrict__ buf, float scale) {
-    const size_t total = nq + static_cast<size_t>(n_cols);
-    for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < total;
-         i += static_cast<size_t>(gridDim.x) * kBlock) {
-        if (i < nq) {
-            const float v = Q_base[i] + scale * buf[i];
-            Q[i] = v;
-            Q_base[i] = v;
-        } else {
-            const float v = ib_base[i - nq] + scale * buf[i];
-            ib[i - nq] = v;
-            ib_base[i - nq] = v;
-        }
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void items_delta_apply_overlapped_kernel(
-    float *__restrict__ Q, float *__restrict__ ib, float *__restrict__ Q_base, float *__restrict__ ib_base,
-    const float *__restrict__ Q_snap, const float *__restrict__ ib_snap, size_t nq, int n_cols,
-    const float *__restrict__ buf, float scale) {
-    const size_t total = nq + static_cast<size_t>(n_cols);
-    for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < total;
-         i += static_cast<size_t>(gridDim.x) * kBlock) {
-        if (i < nq) {
-            const float merged = Q_base[i] + scale * buf[i];
-            Q[i] = merged + (Q[i] - Q_snap[i]);
-            Q_base[i] = merged;
-        } else {
-            const size_t j = i - nq;
-            const float merged = ib_base[j] + scale * buf[i];
-            ib[j] = merged + (ib[j] - ib_snap[j]);
-            ib_base[j] = merged;
-        }
-    }
-}
-
-// ---- the exchange in its wire format: n_cols * f item-row deltas, then n_cols bias deltas, no row padding --------------
-// (the padded form above moves ldq floats per row: 13.8 MB instead of 10.8 MB at f = 100; what crosses xGMI is this one)
+// ---- multi-GPU item-factor exchange, in its wire format: n_cols * f item-row deltas, then n_cols bias deltas, no row padding
+// (a row's padding never crosses xGMI: ldq floats per row would be 13.8 MB instead of 10.8 MB at f = 100)
 __global__ __launch_bounds__(kBlock) void items_wire_pack_kernel(const float *__restrict__ Q, const float *__restrict__ ib,
                                                                  const float *__restrict__ Q_base,
                                                                  const float *__restrict__ ib_base,
@@ -496,31 +431,6 @@ void launch_sample_pairs_build(const int *indices, const float *data, size_t nnz
     hipLaunchKernelGGL(sample_pairs_build_kernel, dim3(blocks), dim3(kBlock), 0, stream, indices, data, nnz, pairs);
 }
 
-void launch_items_delta_pack(const float *Q, const float *ib, const float *Q_base, const float *ib_base, int n_cols,
-                             int ldq, float *buf, hipStream_t stream) {
-    const size_t nq = static_cast<size_t>(n_cols) * ldq;
-    const int blocks = blocks_for(nq + n_cols, kBlock * 4, 4096);
-    hipLaunchKernelGGL(items_delta_pack_kernel, dim3(blocks), dim3(kBlock), 0, stream, Q, ib, Q_base, ib_base, nq,
-                       n_cols, buf);
-}
-
-void launch_items_delta_apply_overlapped(float *Q, float *ib, float *Q_base, float *ib_base, const float *Q_snap,
-                                         const float *ib_snap, int n_cols, int ldq, const float *buf, float scale,
-                                         hipStream_t stream) {
-    const size_t nq = static_cast<size_t>(n_cols) * ldq;
-    const int blocks = blocks_for(nq + n_cols, kBlock * 4, 4096);
-    hipLaunchKernelGGL(items_delta_apply_overlapped_kernel, dim3(blocks), dim3(kBlock), 0, stream, Q, ib, Q_base, ib_base,
-                       Q_snap, ib_snap, nq, n_cols, buf, scale);
-}
-
-void launch_items_delta_pack_weighted(const float *Q, const float *ib, const float *Q_base, const float *ib_base,
-                                      const float *weight, int n_cols, int ldq, float *buf, hipStream_t stream) {
-    const size_t nq = static_cast<size_t>(n_cols) * ldq;
-    const int blocks = blocks_for(nq + n_cols, kBlock * 4, 4096);
-    hipLaunchKernelGGL(items_delta_pack_weighted_kernel, dim3(blocks), dim3(kBlock), 0, stream, Q, ib, Q_base, ib_base,
-                       weight, nq, n_cols, ldq, buf);
-}
-
 void launch_items_wire_pack(const float *Q, const float *ib, const float *Q_base, const float *ib_base, const float *weight,
                             int n_cols, int f, int ldq, float *wire, hipStream_t stream) {
     const int blocks = blocks_for(static_cast<size_t>(n_cols) * (f + 1), kBlock * 4, 4096);
@@ -533,14 +443,6 @@ void launch_items_wire_apply(float *Q, float *ib, float *Q_base, float *ib_base,
     const int blocks = blocks_for(static_cast<size_t>(n_cols) * (f + 1), kBlock * 4, 4096);
     hipLaunchKernelGGL(items_wire_apply_kernel, dim3(blocks), dim3(kBlock), 0, stream, Q, ib, Q_base, ib_base, n_cols, f, ldq,
                        wire, scale);
-}
-
-void launch_items_delta_apply(float *Q, float *ib, float *Q_base, float *ib_base, int n_cols, int ldq,
-                              const float *buf, float scale, hipStream_t stream) {
-    const size_t nq = static_cast<size_t>(n_cols) * ldq;
-    const int blocks = blocks_for(nq + n_cols, kBlock * 4, 4096);
-    hipLaunchKernelGGL(items_delta_apply_kernel, dim3(blocks), dim3(kBlock), 0, stream, Q, ib, Q_base, ib_base, nq,
-                       n_cols, buf, scale);
 }
 
 }  // namespace cu2rec

@@ -77,15 +77,6 @@ void launch_partials_reduce(double *partials, int blocks, hipStream_t stream);
 int error_metrics_blocks(int n);
 void launch_error_metrics(const float *errors, int n, double *partials, int blocks, hipStream_t stream);
 void launch_sample_pairs_build(const int *indices, const float *data, size_t nnz, uint2 *pairs, hipStream_t stream);
-void launch_items_delta_pack(const float *Q, const float *ib, const float *Q_base, const float *ib_base, int n_cols,
-                             int ldq, float *buf, hipStream_t stream);
-void launch_items_delta_apply_overlapped(float *Q, float *ib, float *Q_base, float *ib_base, const float *Q_snap,
-                                         const float *ib_snap, int n_cols, int ldq, const float *buf, float scale,
-                                         hipStream_t stream);
-void launch_items_delta_pack_weighted(const float *Q, const float *ib, const float *Q_base, const float *ib_base,
-                                      const float *weight, int n_cols, int ldq, float *buf, hipStream_t stream);
-void launch_items_delta_apply(float *Q, float *ib, float *Q_base, float *ib_base, int n_cols, int ldq,
-                              const float *buf, float scale, hipStream_t stream);
 // wire format of the exchange: n_cols * f row deltas then n_cols bias deltas, unpadded; weight (n_cols) may be null
 void launch_items_wire_pack(const float *Q, const float *ib, const float *Q_base, const float *ib_base, const float *weight,
                             int n_cols, int f, int ldq, float *wire, hipStream_t stream);

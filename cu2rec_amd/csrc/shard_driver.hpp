@@ -5,8 +5,8 @@
 //   * the product: HipBackend in sharded.cpp (device memory, the HIP kernels, RCCL): cu2rec_shard_job_*, cu2rec_train_sharded,
 //     bin/mf -g N.  There is no other backend in libcu2rec_amd.so: the compute path stays GPU-only.
 //   * tests/host_shard/host_shard.cpp instantiates the SAME template with host arrays and the CPU oracle as the engine, so that
-//     the world-2 gloo tests of tests/test_parallel_cpu.py run this code -- the product's exchange logic, not a restatement of
-//     it -- on a box without a GPU.  Test infrastructure: never linked into the library.
+//     tests/test_shard_driver_cpu.py (one rank, and two gloo ranks) runs this code -- the product's exchange logic, not a
+//     restatement of it -- on a box without a GPU.  Test infrastructure: never linked into the library.
 // Backend B provides:
 //   types     Model, Csr, Comm, Stream, Buffer<T> (allocate(n), ptr, upload(host, n), download(host, n)), Clock (train(); the
 //             exchanges' timers: start(stream), stop(stream), done(), elapsed_ms())
@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "item_rates.hpp"
 #include "train_schedule_core.hpp"
 
 namespace cu2rec {
@@ -86,15 +87,12 @@ struct ShardDriver {
         if (sync_every <= 0)  // "each epoch" (north star): one epoch = nnz / users iterations, SURVEY.md section 8e
             sync_every = std::max(1, static_cast<int>(std::lround(nnz_total / std::max(users_total, 1.0))));
         if ((merge == CU2REC_MERGE_WEIGHTED || merge == CU2REC_MERGE_ADAPTIVE) && comm.nranks > 1) {
-            // w_k[y] = rate_k[y] / sum_j rate_j[y], rate = sum over the shard's raters of 1 / degree (host, double: the same
-            // bits every run); items nobody rates anywhere keep weight 1 / N (their delta is zero anyway)
+            // w_k[y] = rate_k[y] / sum_j rate_j[y], rate_k = the shard's item_update_rates (host, double: the same bits every
+            // run, and those of cu2rec_item_update_rates); items nobody rates anywhere keep weight 1 / N (their delta is zero anyway)
             std::vector<int> indptr, indices;
             B::csr_structure(train, indptr, indices);
             std::vector<double> rate(static_cast<size_t>(std::max(cols, 1)), 0.0);
-            for (int u = 0; u < B::csr_rows(train); ++u) {
-                const int low = indptr[u], high = indptr[u + 1];
-                for (int k = low; k < high; ++k) rate[indices[k]] += 1.0 / (high - low);
-            }
+            item_update_rates(indptr.data(), indices.data(), B::csr_rows(train), cols, rate.data());
             Buffer<double> all;
             all.allocate(rate.size());
             all.upload(rate.data(), rate.size());
@@ -235,8 +233,8 @@ void shard_train(ShardDriver<B> &job, const typename B::Csr &test, cu2rec_config
         cfg, verbose, job.comm.rank == 0, job.users_total, losses, stats, stream,
         [&](const cu2rec_hyper &h, uint64_t first, int n, typename B::Stream s) {
             job.run(h, seed, first, n, mode, cfg.is_train, s);
-            // a loss check follows: every replica must hold the same item side (an exchange out of cadence, like the
-            // Python driver's exchange(final=True))
+            // a loss check follows: every replica must hold the same item side, so the period ends here with an exchange
+            // out of cadence
             if (cfg.is_train && job.since_sync > 0) job.exchange(s);
         },
         [&](bool on_train, float *mae, float *rmse) {

@@ -1,9 +1,8 @@
 """Torch-tensor front end of the raw device-pointer C ABI.
 
-PyTorch is plumbing here: it owns the device memory (so torch.distributed / RCCL can all-reduce
-the item factors in place) and the stream.  Every computation is a call into libcu2rec_amd.so
-on the tensors' data_ptr()s; nothing is computed with torch ops, and there is no CPU path --
-constructing an Engine without a GPU raises.
+PyTorch is plumbing here: it owns the device memory and the stream.  Every computation is a
+call into libcu2rec_amd.so on the tensors' data_ptr()s; nothing is computed with torch ops, and
+there is no CPU path -- constructing an Engine without a GPU raises.
 """
 import numpy as np
 import torch
@@ -71,9 +70,6 @@ class Engine:
         self.user_bias = torch.from_numpy(init(user_bias, rows, (rows,))).to(self.device)
         self.item_bias = torch.from_numpy(init(item_bias, cols, (cols,))).to(self.device)
         self.workspace = torch.empty(lib().cu2rec_loss_workspace_bytes() // 8, dtype=torch.float64, device=self.device)
-        self.Q_base = None
-        self.item_bias_base = None
-        self.exchange = None
 
     def _padded(self, dense, ld):
         t = torch.zeros((max(dense.shape[0], 1), ld), dtype=torch.float32, device=self.device)
@@ -119,48 +115,6 @@ class Engine:
         torch.cuda.synchronize(self.device)
         return (self.P[:self.rows, :self.f].cpu().numpy().copy(), self.Q[:self.cols, :self.f].cpu().numpy().copy(),
                 self.user_bias[:self.rows].cpu().numpy().copy(), self.item_bias[:self.cols].cpu().numpy().copy())
-
-    # ---- item-factor exchange (multi-GPU) ---------------------------------------------------
-    def snapshot_items(self):
-        self.Q_base = self.Q.clone()
-        self.item_bias_base = self.item_bias.clone()
-        self.exchange = torch.empty(self.Q.numel() + self.item_bias.numel(), dtype=torch.float32, device=self.device)
-
-    def pack_item_delta(self, item_weight=None):
-        """exchange <- [Q - Q_base | item_bias - item_bias_base] (device kernel), optionally times a per-item weight."""
-        from ._lib import check
-        if item_weight is not None:
-            check(lib().cu2rec_items_delta_pack_weighted(self.Q.data_ptr(), self.item_bias.data_ptr(),
-                                                         self.Q_base.data_ptr(), self.item_bias_base.data_ptr(),
-                                                         item_weight.data_ptr(), self.item_bias.numel(), self.ldq,
-                                                         self.exchange.data_ptr(), _stream_ptr()))
-            return self.exchange
-        check(lib().cu2rec_items_delta_pack(self.Q.data_ptr(), self.item_bias.data_ptr(), self.Q_base.data_ptr(),
-                                            self.item_bias_base.data_ptr(), self.item_bias.numel(), self.ldq,
-                                            self.exchange.data_ptr(), _stream_ptr()))
-        return self.exchange
-
-    def snapshot_for_overlap(self):
-        """Remember Q / item_bias as they are now (called right after pack_item_delta, before training continues)."""
-        if getattr(self, "Q_snap", None) is None:
-            self.Q_snap, self.item_bias_snap = torch.empty_like(self.Q), torch.empty_like(self.item_bias)
-        self.Q_snap.copy_(self.Q)
-        self.item_bias_snap.copy_(self.item_bias)
-
-    def apply_item_delta_overlapped(self, scale=1.0):
-        """Q <- (Q_base + scale * exchange) + (Q - Q_snap); Q_base <- Q_base + scale * exchange (same for item_bias)."""
-        from ._lib import check
-        check(lib().cu2rec_items_delta_apply_overlapped(self.Q.data_ptr(), self.item_bias.data_ptr(), self.Q_base.data_ptr(),
-                                                        self.item_bias_base.data_ptr(), self.Q_snap.data_ptr(),
-                                                        self.item_bias_snap.data_ptr(), self.item_bias.numel(), self.ldq,
-                                                        self.exchange.data_ptr(), float(scale), _stream_ptr()))
-
-    def apply_item_delta(self, scale=1.0):
-        """Q <- Q_base + scale * exchange_Q (same for item_bias); the result is the new snapshot."""
-        from ._lib import check
-        check(lib().cu2rec_items_delta_apply(self.Q.data_ptr(), self.item_bias.data_ptr(), self.Q_base.data_ptr(),
-                                             self.item_bias_base.data_ptr(), self.item_bias.numel(), self.ldq,
-                                             self.exchange.data_ptr(), float(scale), _stream_ptr()))
 
 
 def hyper_of(cfg):

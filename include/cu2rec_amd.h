@@ -421,28 +421,9 @@ int cu2rec_shard_plan(int rows, int nranks, int *user_begin);
  * nnz in *nnz_out and the offset of its first rating in *offset_out (indices/data slices are
  * then plain sub-arrays). */
 int cu2rec_csr_slice(const int *indptr, int rows, int u0, int u1, int *indptr_out, int *offset_out, int *nnz_out);
-/* Device helpers for the item-factor exchange (one fused buffer of n_cols*(ld+1) floats):
- *   pack:   buf = [Q - Q_base | item_bias - item_bias_base]
- *   apply:  Q = Q_base + scale * buf_Q ; item_bias likewise ; then Q_base = Q (new snapshot)
- * between them the caller all-reduces `buf` (RCCL via torch.distributed or ncclAllReduce). */
-int cu2rec_items_delta_pack(const float *Q, const float *item_bias, const float *Q_base, const float *ib_base,
-                            int n_cols, int ldq, float *buf, void *stream);
-/* Overlapped exchange: the all-reduce of `buf` runs while training continues.  *_snap hold Q / item_bias as they were
- * when `buf` was packed; when the reduced `buf` arrives:
- *     merged = Q_base + scale * buf;   Q = merged + (Q - Q_snap)   (local progress made meanwhile is kept);
- *     Q_base = merged                  (so the next delta is exactly that local progress), same for item_bias. */
-int cu2rec_items_delta_apply_overlapped(float *Q, float *item_bias, float *Q_base, float *ib_base, const float *Q_snap,
-                                        const float *ib_snap, int n_cols, int ldq, const float *buf, float scale,
-                                        void *stream);
-/* Same with a per-item weight (device, n_cols floats) applied to the item's delta row and bias delta: ranks pack
- * w_k[y] * delta_k[y] with sum_k w_k[y] == 1, all-reduce(SUM), apply with scale 1 -- a per-item weighted average. */
-int cu2rec_items_delta_pack_weighted(const float *Q, const float *item_bias, const float *Q_base, const float *ib_base,
-                                     const float *item_weight, int n_cols, int ldq, float *buf, void *stream);
 /* Expected number of SGD updates per iteration that the rows of a host CSR make on each item:
  * rate[y] = sum over users u that rated y of 1 / degree(u)   (each user samples uniformly among its ratings). */
 int cu2rec_item_update_rates(const int *indptr, const int *indices, int n_rows, int n_cols, double *rate);
-int cu2rec_items_delta_apply(float *Q, float *item_bias, float *Q_base, float *ib_base, int n_cols, int ldq,
-                             const float *buf, float scale, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * User-sharded training on several GPUs, ONE PROCESS PER GPU (the reference is single device; the interface extended

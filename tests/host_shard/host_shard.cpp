@@ -1,11 +1,12 @@
 // TEST INFRASTRUCTURE (never part of libcu2rec_amd.so): the product's user-sharded driver -- the template of
 // cu2rec_amd/csrc/shard_driver.hpp: exchange cadence, wire exchange and merge weights, global loss reduction, train() over all
 // ranks -- instantiated over HOST memory, with the CPU oracle (oracle/cu2rec_oracle.c) as the engine that runs the SGD and loss
-// passes.  tests/test_parallel_cpu.py drives it with two gloo ranks on a box without a GPU, so the world-2 CPU tests run the
-// product's C++ exchange code itself.  Built by the test: g++ -shared ... -> build/test/libcu2rec_shard_host.so.
+// passes.  tests/test_shard_driver_cpu.py drives it at one rank and with two gloo ranks on a box without a GPU, so the CPU tests
+// run the product's C++ exchange code itself.  Built by build(): g++ -shared ... ->
+// build/test/libcu2rec_shard_host.so.
 //
 // Users are addressed by their GLOBAL id on every rank here: a rank's model holds full-size P / user_bias arrays and a CSR whose
-// rows outside its user range are empty (the way tests/exchange_reference.py runs the oracle), so user_offset is 0.
+// rows outside its user range are empty (so the oracle runs a shard as it runs the whole set), so user_offset is 0.
 #include <chrono>
 #include <cstring>
 #include <memory>

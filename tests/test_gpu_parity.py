@@ -456,69 +456,6 @@ def test_train_ordered_equals_serial():
         np.testing.assert_array_equal(a, b)
 
 
-# ------------------------------------------------------------------ multi-GPU plumbing on one GPU
-
-def test_item_exchange_kernels_and_rccl_world1():
-    """The exchange path on real hardware with world_size 1: RCCL all-reduce (backend nccl) of the fused delta
-    buffer, pack / apply kernels; ShardedSGD at N=1 must be bit-identical to the plain path (no exchange)."""
-    import torch
-    import torch.distributed as dist
-    from cu2rec_amd.engine import DeviceRatings, Engine
-    from exchange_reference import ShardedSGD
-    tr, te = _small_set(users=1500, items=200, nnz=30000, seed=12)
-    f = 20
-    if not dist.is_initialized():
-        dist.init_process_group("nccl", init_method="tcp://127.0.0.1:%d" % (29500 + os.getpid() % 500), rank=0,
-                                world_size=1, device_id=torch.device("cuda", 0))
-    try:
-        eng = Engine(tr.rows, tr.cols, f, tr.global_bias)
-        ref = Engine(tr.rows, tr.cols, f, tr.global_bias)
-        d = DeviceRatings(tr, eng.device)
-        job = ShardedSGD(eng, d, sync_every=3)
-        job.run(HYPER, 42, 0, 10, "ordered")
-        ref.sgd(d, HYPER, 42, 0, 10, "ordered")
-        for a, b in zip(eng.download(), ref.download()):
-            np.testing.assert_array_equal(a, b)
-        # manual exchange: snapshot, train, pack -> all_reduce -> apply(1.0) reproduces Q up to one rounding
-        eng.snapshot_items()
-        Q0 = eng.Q.clone()
-        eng.sgd(d, HYPER, 42, 10, 5, "hogwild")
-        Q1, ib1 = eng.Q.clone(), eng.item_bias.clone()
-        buf = eng.pack_item_delta()
-        torch.testing.assert_close(buf[:Q1.numel()].view_as(Q1), Q1 - Q0, rtol=0, atol=0)
-        dist.all_reduce(buf)
-        eng.apply_item_delta(1.0)
-        torch.testing.assert_close(eng.Q, Q1, rtol=0, atol=1e-6)
-        torch.testing.assert_close(eng.item_bias, ib1, rtol=0, atol=1e-6)
-        torch.testing.assert_close(eng.Q_base, eng.Q, rtol=0, atol=0)
-        # mean merge with scale 1/2 halves the step
-        eng.sgd(d, HYPER, 42, 15, 5, "hogwild")
-        Q2 = eng.Q.clone()
-        eng.pack_item_delta()
-        eng.apply_item_delta(0.5)
-        torch.testing.assert_close(eng.Q, eng.Q_base)
-        torch.testing.assert_close(eng.Q, Q1 + 0.5 * (Q2 - Q1), rtol=0, atol=1e-6)
-        out = job.loss(DeviceRatings(te, eng.device))
-        assert out["n"] == te.nnz and np.isfinite(out["rmse"])
-        # overlapped form: async RCCL all-reduce in flight while training continues, folded in afterwards
-        eng.snapshot_items()
-        base = eng.Q.clone()
-        eng.sgd(d, HYPER, 42, 20, 5, "hogwild")
-        buf = eng.pack_item_delta()
-        eng.snapshot_for_overlap()
-        snap = eng.Q.clone()
-        work = dist.all_reduce(buf, async_op=True)
-        eng.sgd(d, HYPER, 42, 25, 5, "hogwild")  # runs next to the collective
-        now = eng.Q.clone()
-        work.wait()
-        eng.apply_item_delta_overlapped(1.0)
-        torch.testing.assert_close(eng.Q_base, snap, rtol=0, atol=1e-6)          # merged = base + (snap - base)
-        torch.testing.assert_close(eng.Q, now, rtol=0, atol=2e-6)                # + local progress since the pack
-        assert not torch.equal(now, snap) and not torch.equal(snap, base)
-    finally:
-        dist.destroy_process_group()
-
-
 # ------------------------------------------------------------------ next row (SURVEY 8f-2): bin/predict
 
 def test_bin_predict_partial_fit(tmp_path):
@@ -646,55 +583,3 @@ def test_netflix_shape_full_size_bit_exact():
     model.sgd(dtr, HYPER, 42, 3, 200, mode="hogwild")
     after = model.loss(dte)["rmse"]
     assert np.isfinite(after) and after < got["rmse"]
-
-
-def test_two_logical_shards_on_one_gpu_match_the_oracle():
-    """N logical shards emulated on one device.  Two user shards, each an Engine with its own
-    replica of the item side, ordered mode (deterministic), item deltas reconciled every 3 iterations with the
-    product's pack / apply kernels (the all-reduce itself replaced by a tensor add) -- against the same schedule run
-    by the CPU oracle with numpy doing the merge: every parameter bit for bit."""
-    import torch
-    from cu2rec_amd.engine import DeviceRatings, Engine
-    from cu2rec_amd.sharded import plan_users
-    tr, _ = _small_set(users=500, items=150, nnz=12000, seed=21)
-    f, n_shards, sync, total = 24, 2, 3, 9
-    P, Q, ub, ib = orc.init_model(tr.rows, tr.cols, f)
-    b = plan_users(tr.rows, n_shards)
-    bounds = list(zip(b[:-1], b[1:]))
-    shards = [tr.slice_users(u0, u1) for u0, u1 in bounds]
-    engines = [Engine(u1 - u0, tr.cols, f, tr.global_bias, P[u0:u1], Q, ub[u0:u1], ib) for u0, u1 in bounds]
-    ratings = [DeviceRatings(s, engines[0].device) for s in shards]
-    for e in engines:
-        e.snapshot_items()
-    # oracle side: full-size arrays, each shard sees only its users' rows through a masked CSR
-    oP = [P.copy() for _ in bounds]
-    oub = [ub.copy() for _ in bounds]
-    oQ, oib = [Q.copy() for _ in bounds], [ib.copy() for _ in bounds]
-    Qb, ibb = Q.copy(), ib.copy()
-    masked = []
-    for u0, u1 in bounds:
-        ip = tr.indptr.copy()
-        ip[:u0 + 1] = tr.indptr[u0]
-        ip[u1:] = tr.indptr[u1]
-        masked.append(orc.CSR(ip, tr.indices, tr.data, tr.rows, tr.cols))
-    for it in range(0, total, sync):
-        for k, (u0, _) in enumerate(bounds):
-            engines[k].sgd(ratings[k], HYPER, 42, it, sync, mode="ordered", user_offset=u0)
-            orc.sgd_iterations(masked[k], oP[k], oQ[k], oub[k], oib[k], tr.global_bias, HYPER, 42, it, sync,
-                               dot_order=orc.DOT_TREE16)
-        bufs = [e.pack_item_delta().clone() for e in engines]
-        total_buf = bufs[0] + bufs[1]  # what the all-reduce would deliver
-        for e in engines:
-            e.exchange.copy_(total_buf)
-            e.apply_item_delta(0.5)
-        dQ = (oQ[0] - Qb) + (oQ[1] - Qb)
-        dib = (oib[0] - ibb) + (oib[1] - ibb)
-        Qb, ibb = Qb + np.float32(0.5) * dQ, ibb + np.float32(0.5) * dib
-        for k in range(n_shards):
-            oQ[k], oib[k] = Qb.copy(), ibb.copy()
-    for k, (u0, u1) in enumerate(bounds):
-        gP, gQ, gub, gib = engines[k].download()
-        np.testing.assert_array_equal(gP, oP[k][u0:u1])
-        np.testing.assert_array_equal(gub, oub[k][u0:u1])
-        np.testing.assert_array_equal(gQ, Qb)
-        np.testing.assert_array_equal(gib, ibb)

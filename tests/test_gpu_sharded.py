@@ -79,6 +79,35 @@ def test_rccl_world1_allreduce_in_the_loop(monkeypatch):
     comm.close()
 
 
+def test_rccl_world1_explicit_exchange_is_exact_and_keeps_the_padding_zero(monkeypatch):
+    """One explicit exchange (cu2rec_shard_job_exchange) through a real one-rank RCCL all-reduce after iterations without one, merge
+    `sum`, f = 20 (ldq = 32: the item rows have padding): Q and item_bias become float32(Q_base + 1 * float32(Q_pre - Q_base)) bit for
+    bit -- Q_base the item side at creation or behind the previous exchange, Q_pre the item side just before this one -- and the rows'
+    padding, read straight from device memory, is still zero."""
+    from test_gpu_row_widths import _check_padding
+    monkeypatch.setenv("CU2REC_RCCL_WORLD1", "1")
+    tr, _ = synth.make_ratings(1500, 200, 30000, min_degree=3, seed=12)
+    f = 20
+    comm = sharded.Comm(0, 1)
+    model = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
+    job = sharded.ShardJob(comm, model, cu.DeviceCSR(tr), sync_every=1000, merge="sum")
+    _, Qb, _, ibb = model.download()
+    one = np.float32(1)
+    for it0, n in ((0, 10), (10, 5)):
+        job.run(HYPER, 42, it0, n, mode="ordered")
+        _, Q_pre, _, ib_pre = model.download()
+        assert not np.array_equal(Q_pre, Qb) and not np.array_equal(ib_pre, ibb)
+        job.exchange()
+        _, Q, _, ib = model.download()
+        np.testing.assert_array_equal(Q, Qb + one * (Q_pre - Qb))
+        np.testing.assert_array_equal(ib, ibb + one * (ib_pre - ibb))
+        Qb, ibb = Q, ib
+    assert job.info()["exchanges"] == 2
+    _check_padding(model, f)
+    job.close()
+    comm.close()
+
+
 # ---- two ranks on one GPU, the all-reduce through gloo ---------------------------------------------------------------
 
 def _two_rank_worker(rank, world, port, out_dir, merge, hyper=HYPER):
@@ -273,6 +302,48 @@ class _InProcessWorld:
         if failed:
             raise failed[0]
         return out
+
+
+def test_two_thread_ranks_on_one_gpu_match_the_oracle_bit_for_bit():
+    """Two ranks of the product's driver (ShardJob) as threads of this process, ordered mode, merge `mean`, an exchange every 3 of 9
+    iterations, against the oracle on each shard and the numpy merge Qb + 0.5f (d0 + d1): P, user_bias, Q and item_bias bit for bit.
+    The driver does the same float32 operations: wire = Q - Q_base, a two-term sum in rank order, Q_base + 0.5f wire
+    (-ffp-contract=off)."""
+    tr, _ = synth.make_ratings(500, 150, 12000, min_degree=3, seed=21)
+    f, sync, total = 24, 3, 9
+    P, Q, ub, ib = orc.init_model(tr.rows, tr.cols, f)
+    b = sharded.plan_users(tr.rows, 2)
+    bounds = list(zip(b[:-1], b[1:]))
+
+    def rank_body(rank, comm):
+        u0, u1 = bounds[rank]
+        model = cu.Model(u1 - u0, tr.cols, f, tr.global_bias, P=P[u0:u1], Q=Q, user_bias=ub[u0:u1], item_bias=ib)
+        job = sharded.ShardJob(comm, model, cu.DeviceCSR(tr.slice_users(u0, u1)), user_offset=u0, sync_every=sync, merge="mean")
+        job.run(HYPER, 42, 0, total, mode="ordered")
+        exchanges = job.info()["exchanges"]
+        job.close()
+        return model.download(), exchanges
+    world = _InProcessWorld(2)
+    res = world.run(rank_body)
+    assert not world.errors, world.errors
+
+    oP, oub = [P.copy() for _ in bounds], [ub.copy() for _ in bounds]
+    oQ, oib = [Q.copy() for _ in bounds], [ib.copy() for _ in bounds]
+    Qb, ibb = Q.copy(), ib.copy()
+    half = np.float32(0.5)
+    for it in range(0, total, sync):
+        for k, (u0, u1) in enumerate(bounds):
+            orc.sgd_iterations(_masked(tr, u0, u1), oP[k], oQ[k], oub[k], oib[k], tr.global_bias, HYPER, 42, it, sync, dot_order=orc.DOT_TREE16)
+        Qb = Qb + half * ((oQ[0] - Qb) + (oQ[1] - Qb))
+        ibb = ibb + half * ((oib[0] - ibb) + (oib[1] - ibb))
+        oQ, oib = [Qb.copy() for _ in bounds], [ibb.copy() for _ in bounds]
+    for k, (u0, u1) in enumerate(bounds):
+        (gP, gQ, gub, gib), exchanges = res[k]
+        assert exchanges == total // sync
+        np.testing.assert_array_equal(gP, oP[k][u0:u1])
+        np.testing.assert_array_equal(gub, oub[k][u0:u1])
+        np.testing.assert_array_equal(gQ, Qb)
+        np.testing.assert_array_equal(gib, ibb)
 
 
 def forced_segments(checks, decays, lr0=0.01, decay=0.2):

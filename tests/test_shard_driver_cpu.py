@@ -1,13 +1,12 @@
 """The product's user-sharded driver (cu2rec_amd/csrc/shard_driver.hpp: exchange cadence, wire exchange + merge weights, global
 loss reduction, train() over all ranks -- the template cu2rec_shard_job_* / cu2rec_train_sharded / bin/mf -g N instantiate over
 HIP) driven on the CPU: tests/host_shard/host_shard.cpp instantiates the SAME template over host memory with the CPU oracle as
-the engine, and two gloo ranks run it here (world_size 2, no GPU).  What is compared against: single-process numpy emulations
-of the stated merge algebra, and the Python restatement tests/exchange_reference.py.  (The engine is the oracle: these tests
+the engine, and one rank or two gloo ranks run it here (no GPU).  What is compared against: the oracle itself (one rank), and
+single-process numpy emulations of the stated merge algebra and cadence (two ranks).  (The engine is the oracle: these tests
 check the DRIVER, the kernels have their own parity tests.)"""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,8 +17,8 @@ import torch.multiprocessing as mp
 import cu2rec_amd as cu
 from cu2rec_amd import synth
 from cu2rec_amd._lib import Config, Hyper
+from cu2rec_amd.sharded import plan_users
 from conftest import ROOT
-from exchange_reference import plan_users
 from oracle import oracle as orc
 
 HYPER = (0.01, 0.02, 0.02, 0.02, 0.02)
@@ -31,7 +30,8 @@ ALLREDUCE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.
 
 def build_host_driver():
     """g++ (no HIP): the driver template + the host backend, linked against the oracle's C library."""
-    deps = [SRC] + [os.path.join(ROOT, "cu2rec_amd", "csrc", h) for h in ("shard_driver.hpp", "train_schedule_core.hpp", "common.hpp")]
+    deps = [SRC] + [os.path.join(ROOT, "cu2rec_amd", "csrc", h) for h in ("shard_driver.hpp", "item_rates.hpp", "train_schedule_core.hpp",
+                                                                              "common.hpp")]
     if os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps):
         return LIB
     orc.lib()  # builds oracle/_build/libcu2rec_oracle.so if need be
@@ -120,7 +120,9 @@ class HostJob:
 
 
 def _emulate(tr, f, world, sync, iters, merge):
-    """Single process, numpy: `world` logical shards, the stated merge algebra at the stated cadence."""
+    """Single process, numpy: `world` logical shards, the stated merge algebra at the stated cadence.
+    -> (states, bounds, exchanges, rates, w, last): the shards' item update rates and merge weights (None: no weight), and the
+    last exchange's snapshot and per-shard deltas."""
     P, Q, ub, ib = orc.init_model(tr.rows, tr.cols, f)
     bounds = plan_users(tr.rows, world)
     shards = [orc.CSR(masked(tr, bounds[k], bounds[k + 1]), tr.indices, tr.data, tr.rows, tr.cols) for k in range(world)]
@@ -146,6 +148,7 @@ def _emulate(tr, f, world, sync, iters, merge):
             orc.sgd_iterations(shards[k], *states[k], tr.global_bias, HYPER, 42, it, n, dot_order=orc.DOT_TREE16)
         it += n
         if n == sync:
+            last = (Qb.copy(), [s[1] - Qb for s in states])
             dQ = sum((s[1] - Qb) * (wk[:, None] if wk is not None else np.float32(1)) for s, wk in zip(states, w))
             dib = sum((s[3] - ibb) * (wk if wk is not None else np.float32(1)) for s, wk in zip(states, w))
             Qb, ibb = Qb + scale * dQ, ibb + scale * dib
@@ -153,13 +156,18 @@ def _emulate(tr, f, world, sync, iters, merge):
                 s[1][...] = Qb
                 s[3][...] = ibb
             exchanges += 1
-    return states, bounds, exchanges
+    return states, bounds, exchanges, rates, w, last
+
+
+def _merge_set(merge):
+    # the weighted merge's set has more items, so that some are rated by one rank only (weights 1 and 0)
+    return synth.make_ratings(80, 120 if merge == "weighted" else 25, 900, min_degree=2, seed=5)
 
 
 def _merge_worker(rank, world, port, out_dir, merge):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    tr, te = synth.make_ratings(80, 25, 900, min_degree=2, seed=5)
+    tr, te = _merge_set(merge)
     f = 6
     bounds = plan_users(tr.rows, world)
     u0, u1 = bounds[rank], bounds[rank + 1]
@@ -179,8 +187,8 @@ def test_cpp_driver_two_ranks_gloo_against_the_merge_algebra(tmp_path, merge):
     world, port = 2, 36000 + os.getpid() % 2000 + 7 * MERGE[merge]
     mp.spawn(_merge_worker, args=(world, port, str(tmp_path), merge), nprocs=world, join=True)
     r = [np.load(str(tmp_path / ("m%d.npz" % k))) for k in range(world)]
-    tr, te = synth.make_ratings(80, 25, 900, min_degree=2, seed=5)
-    states, bounds, exchanges = _emulate(tr, 6, world, 4, 10, merge)
+    tr, te = _merge_set(merge)
+    states, bounds, exchanges, rates, w, (Qb, deltas) = _emulate(tr, 6, world, 4, 10, merge)
     assert int(r[0]["exchanges"]) == int(r[1]["exchanges"]) == exchanges == 2
     for k in range(world):  # every exchange timed, on every rank
         assert int(r[k]["timed"]) == 2 and 0 < float(r[k]["max_seconds"]) <= float(r[k]["seconds"]) <= 60.0
@@ -192,6 +200,14 @@ def test_cpp_driver_two_ranks_gloo_against_the_merge_algebra(tmp_path, merge):
         np.testing.assert_allclose(r[k]["ub"][u0:u1], states[k][2][u0:u1], atol=1e-6)
         np.testing.assert_allclose(r[k]["ib"], states[k][3], atol=1e-6)
     assert float(r[0]["rmse"]) == float(r[1]["rmse"]) and int(r[0]["n"]) == te.nnz  # the loss is reduced over the ranks
+    if merge == "weighted":
+        np.testing.assert_allclose(w[0] + w[1], 1.0, atol=1e-6)  # a per-item weighted average
+        # an item rated by one rank only lands on the snapshot plus that rank's whole step at an exchange; the other rank never
+        # moves it afterwards, so its replica still holds the last exchange's result
+        for k in range(world):
+            only = (rates[k] > 0) & (rates[1 - k] == 0)
+            assert only.any()
+            np.testing.assert_allclose(r[1 - k]["Q"][only], (Qb + deltas[k])[only], atol=1e-6)
 
 
 def test_cpp_driver_one_rank_is_the_oracle_bit_for_bit_and_frozen_items_terminate():
@@ -221,44 +237,57 @@ def _one_rank_against_the_oracle(hyper):
         job.run(hyper, 42, 10, 25, update_items=False)  # 8 periods of 3 + 1
         np.testing.assert_array_equal(job.Q, q_before)
         assert job.info()["exchanges"] == 0
+        # ... and the user side went on from the same state exactly as the engine's own frozen-item run
+        orc.sgd_iterations(orc.CSR(tr.indptr, tr.indices, tr.data, tr.rows, tr.cols), *want, tr.global_bias, hyper, 42, 10, 25,
+                           dot_order=orc.DOT_TREE16, update_items=False)
+        np.testing.assert_array_equal(job.P, want[0])
+        np.testing.assert_array_equal(job.ub, want[2])
         job.close()
     finally:
         dist.destroy_process_group()
 
 
-def _oracle_factory(rows, cols, f, gb, P0, ub0, tr, te):
-    from test_parallel_cpu import OracleEngine
-    Q = orc.normal_fill(cols * f, f).reshape(cols, f)
-    ib = orc.normal_fill(cols, f)
-    return OracleEngine(rows, cols, f, gb, P0, Q, ub0, ib), tr, te
+def test_cpp_driver_train_one_rank_matches_oracle_train(capfd):
+    """shard_train at one rank is training.cu's train(): the check iterations, the test RMSE at each, the learning rate the patience
+    rule leaves (patience 1, lr 0.05), cur_iterations and the printed lines (written by C, hence capfd)."""
+    tr, te = synth.make_ratings(60, 30, 700, min_degree=2, seed=4)
+    kw = dict(total_iterations=20, n_factors=6, check_error=5, learning_rate=0.05, patience=1.0)
+    cfg, ocfg = cu.default_config(**kw), orc.default_config(**kw)
+    P, Q, ub, ib = orc.init_model(tr.rows, tr.cols, 6)
+    log = orc.train(orc.CSR(tr.indptr, tr.indices, tr.data, tr.rows, tr.cols), orc.CSR(te.indptr, te.indices, te.data, te.rows, te.cols),
+                    ocfg, P, Q, ub, ib, tr.global_bias, dot_order=orc.DOT_TREE16, acc=orc.ACC_F64, schedule=orc.SCHED_PATIENCE)
+    job = HostJob(0, 1, tr, 6, orc.init_model(tr.rows, tr.cols, 6), 0, tr.rows, 3, "mean")
+    losses = job.train(te, 0, te.rows, cfg, verbose=True)
+    job.close()
+    assert [e["iteration"] - 1 for e in log] == [i for i in range(20) if not np.isnan(losses[i])] == [0, 4, 9, 14, 19]
+    for e in log:
+        assert abs(losses[e["iteration"] - 1] - e["test_rmse"]) < 1e-6
+    assert cfg.learning_rate == ocfg.learning_rate and cfg.cur_iterations == 20
+    C.CDLL(None).fflush(None)  # (C's stdout buffer)
+    out = capfd.readouterr().out
+    assert "TRAIN: Iteration 1 GPU MAE:" in out and "TEST: Iteration 20 GPU MAE:" in out and "Time taken for 20 of iterations" in out
 
 
 def _train_worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     tr, te = synth.make_ratings(90, 25, 1000, min_degree=2, seed=6)
     f = 5
-    kw = dict(total_iterations=12, n_factors=f, check_error=4, learning_rate=0.02)
     bounds = plan_users(tr.rows, world)
     u0, u1 = bounds[rank], bounds[rank + 1]
-    cfg = cu.default_config(**kw)
+    cfg = cu.default_config(total_iterations=12, n_factors=f, check_error=4, learning_rate=0.02)
     job = HostJob(rank, world, tr, f, orc.init_model(tr.rows, tr.cols, f), u0, u1, 3, "mean")
     losses = job.train(te, u0, u1, cfg)
-    # the Python restatement of the same driver (tests/exchange_reference.py), same ranks, same engine arithmetic up to the dot order
-    from exchange_reference import train_sharded
-    cfg_py = cu.default_config(**kw)
-    _, Qp, losses_py, _, ibp, _ = train_sharded(tr, te, cfg_py, sync_every=3, merge="mean", engine_factory=_oracle_factory, verbose=False)
-    np.savez(os.path.join(out_dir, "t%d.npz" % rank), Q=job.Q, ib=job.ib, losses=losses, lr=cfg.learning_rate, cur=cfg.cur_iterations,
-             exchanges=job.info()["exchanges"], Qp=Qp, ibp=ibp, losses_py=losses_py, lr_py=cfg_py.learning_rate)
+    np.savez(os.path.join(out_dir, "t%d.npz" % rank), P=job.P, ub=job.ub, Q=job.Q, ib=job.ib, losses=losses, lr=cfg.learning_rate,
+             cur=cfg.cur_iterations, exchanges=job.info()["exchanges"])
     job.close()
     dist.destroy_process_group()
 
 
 def test_cpp_driver_train_sharded_two_ranks_gloo(tmp_path):
     """shard_train (cu2rec_train_sharded's loop) on two ranks: both ranks hold the same item side behind the final exchange, saw the
-    same GLOBAL losses at the reference's check iterations and took the same learning-rate decisions; and the run agrees with the
-    Python restatement of the driver."""
+    same GLOBAL losses at the reference's check iterations and took the same learning-rate decisions; and the run agrees with a numpy
+    emulation: the oracle on each shard, the mean merge, the driver's cadence and the oracle's loss of the merged model."""
     world, port = 2, 39000 + os.getpid() % 2000
     mp.spawn(_train_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
     a, b = (np.load(str(tmp_path / ("t%d.npz" % k))) for k in range(2))
@@ -272,7 +301,47 @@ def test_cpp_driver_train_sharded_two_ranks_gloo(tmp_path):
     # cadence (the check at 4 falls on it); iterations 5-8 and 9-12: one in cadence after three iterations, one out of cadence in front
     # of the check behind the fourth
     assert int(a["exchanges"]) == 6
-    np.testing.assert_allclose(a["Q"], a["Qp"], atol=2e-6)
-    np.testing.assert_allclose(a["ib"], a["ibp"], atol=2e-6)
-    np.testing.assert_allclose(np.nan_to_num(a["losses"]), np.nan_to_num(a["losses_py"]), atol=2e-6)
-    assert abs(float(a["lr"]) - float(a["lr_py"])) < 1e-9
+
+    tr, te = synth.make_ratings(90, 25, 1000, min_degree=2, seed=6)
+    f, sync = 5, 3
+    bounds = plan_users(tr.rows, world)
+    shards = [orc.CSR(masked(tr, bounds[k], bounds[k + 1]), tr.indices, tr.data, tr.rows, tr.cols) for k in range(world)]
+    states = [list(orc.init_model(tr.rows, tr.cols, f)) for _ in range(world)]
+    Qb, ibb = states[0][1].copy(), states[0][3].copy()
+    # patience 2: the rate decays only behind a second check at which the test RMSE rose -- not in this run, so every iteration of
+    # the emulation runs at 0.02
+    assert float(a["lr"]) == float(np.float32(0.02))
+    hyper = (float(a["lr"]),) + HYPER[1:]
+
+    def merge_now():
+        nonlocal Qb, ibb
+        half = np.float32(0.5)
+        Qb = Qb + half * ((states[0][1] - Qb) + (states[1][1] - Qb))
+        ibb = ibb + half * ((states[0][3] - ibb) + (states[1][3] - ibb))
+        for s in states:
+            s[1][...], s[3][...] = Qb, ibb
+
+    since, it, want = 0, 0, np.full(12, np.nan, np.float32)
+    for seg_end in checked:
+        while it <= seg_end:
+            n = min(seg_end + 1 - it, sync - since)
+            for k in range(world):
+                orc.sgd_iterations(shards[k], *states[k], tr.global_bias, hyper, 42, it, n, dot_order=orc.DOT_TREE16)
+            it, since = it + n, since + n
+            if since == sync:
+                merge_now()
+                since = 0
+        if since:  # out of cadence, in front of the check
+            merge_now()
+            since = 0
+        P, ub = states[0][0].copy(), states[0][2].copy()
+        P[bounds[1]:], ub[bounds[1]:] = states[1][0][bounds[1]:], states[1][2][bounds[1]:]
+        want[seg_end] = orc.loss(orc.CSR(te.indptr, te.indices, te.data, te.rows, te.cols), P, Qb, ub, ibb, tr.global_bias,
+                                 dot_order=orc.DOT_TREE16)["rmse"]
+    np.testing.assert_allclose(a["Q"], Qb, atol=2e-6)
+    np.testing.assert_allclose(a["ib"], ibb, atol=2e-6)
+    for k, x in enumerate((a, b)):
+        u0, u1 = bounds[k], bounds[k + 1]
+        np.testing.assert_allclose(x["P"][u0:u1], states[k][0][u0:u1], atol=2e-6)
+        np.testing.assert_allclose(x["ub"][u0:u1], states[k][2][u0:u1], atol=2e-6)
+    np.testing.assert_allclose(np.nan_to_num(a["losses"]), np.nan_to_num(want), atol=2e-6)
