@@ -45,6 +45,12 @@ class TrainStats(C.Structure):
                 ("last_test_mae", C.c_float), ("last_test_rmse", C.c_float)]
 
 
+class RankMetrics(C.Structure):
+    """cu2rec_rank_metrics: means over evaluated users of the ranking metrics at k."""
+    _fields_ = [("k", C.c_int), ("users_evaluated", C.c_int), ("users_skipped", C.c_int), ("precision", C.c_double),
+                ("recall", C.c_double), ("ndcg", C.c_double), ("map", C.c_double), ("hit_rate", C.c_double)]
+
+
 class CommInfo(C.Structure):
     """cu2rec_comm_info_t: what RCCL itself reports about the attached communicator."""
     _fields_ = [("rank", C.c_int), ("nranks", C.c_int), ("rccl_nranks", C.c_int), ("rccl_rank", C.c_int), ("rccl_device", C.c_int),
@@ -124,6 +130,8 @@ SIGNATURES = {
     "cu2rec_model_scores": (C.c_int, [_P, _P, _P]),
     "cu2rec_model_scores_host": (C.c_int, [_P, _P]),
     "cu2rec_model_recommend": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "cu2rec_model_topk": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "cu2rec_model_rank_metrics": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.POINTER(RankMetrics), _P]),
     "cu2rec_train": (C.c_int, [_P, _P, C.POINTER(Config), _P, C.c_int, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_shard_plan": (C.c_int, [C.c_int, C.c_int, _P]),
     "cu2rec_comm_unique_id": (C.c_int, [_P]),

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from ._lib import Config, Cu2recError, Hyper, TrainStats, check, lib
+from ._lib import Config, Cu2recError, Hyper, RankMetrics, TrainStats, check, lib
 
 SGD_HOGWILD, SGD_SERIAL, SGD_ORDERED, SGD_PINGPONG, SGD_BLOCKSOLVE = 0, 1, 2, 3, 4
 MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "pingpong": SGD_PINGPONG,
@@ -280,6 +280,32 @@ class Model:
         items, scores = np.empty((self.rows, k), np.int32), np.empty((self.rows, k), np.float32)
         check(lib().cu2rec_model_recommend(self._h, rated._h if rated is not None else None, int(k), _ptr(items), _ptr(scores)))
         return items, scores
+
+    def topk(self, exclude, k, users=None):
+        """The k best non-excluded items of each user, without the dense score matrix (cu2rec_model_topk) -> (items,
+        scores), each (n, k): recommend's scores and order bit for bit (equal scores by ascending item; -inf never listed);
+        -1 / NaN where a user has fewer than k candidates.  exclude: DeviceCSR (row u = user u's excluded items) or None.
+        users: model row ids (duplicates allowed), or None for every row.  1 <= k <= 256."""
+        ids = None if users is None else np.ascontiguousarray(users, dtype=np.int32).reshape(-1)
+        n = self.rows if ids is None else len(ids)
+        items, scores = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_model_topk(self._h, exclude._h if exclude is not None else None, _ptr(ids), int(n), int(k),
+                                      _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def rank_metrics(self, test, k, exclude=None, threshold=None, per_user=False):
+        """Ranking quality at k of the top-k lists (topk over every row, excluding `exclude`) against `test`
+        (cu2rec_model_rank_metrics; definitions in include/cu2rec_amd.h) -> dict(precision, recall, ndcg, map, hit_rate,
+        users_evaluated, users_skipped, k), and with per_user=True also a (rows, 5) float64 array {precision, recall, ndcg,
+        ap, hit}, NaN for skipped users.  R_u = distinct items of test row u rated >= threshold (None: every rating);
+        users with an empty R_u are skipped.  test / exclude: DeviceCSR."""
+        out = RankMetrics()
+        per = np.empty((self.rows, 5), np.float64) if per_user else None
+        thr = -np.inf if threshold is None else float(threshold)
+        check(lib().cu2rec_model_rank_metrics(self._h, exclude._h if exclude is not None else None, test._h, int(k), thr,
+                                              C.byref(out), _ptr(per)))
+        res = {name: getattr(out, name) for name, _ in RankMetrics._fields_}
+        return (res, per) if per_user else res
 
     def device_ptrs(self):
         a, b, c, d = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()

@@ -3,7 +3,7 @@
 // files; built on the C ABI of libcu2rec_amd.
 //
 //   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong] [-g gpus] [-s sync_every]
-//          [-w adaptive|mean|weighted|sum] train.csv test.csv
+//          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
 // for bit).  `-m hogwild` opts into sgd.cu's own racy semantics (fastest, 1e-3 away from the sequential result while
@@ -11,6 +11,8 @@
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
+// -k K (single GPU): after the five files, one more line -- the trained model's ranking quality at K on the test file, the
+// training ratings excluded (cu2rec_model_rank_metrics); -t T: a test rating is relevant when >= T (default: every rating).
 #include <getopt.h>
 #include <hip/hip_runtime_api.h>
 #include <signal.h>
@@ -20,7 +22,9 @@
 
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <string>
@@ -268,9 +272,22 @@ int main(int argc, char **argv) {
     std::string config_path;
     int mode = CU2REC_SGD_BLOCKSOLVE;  // the mode that meets the north star's 1e-4 bar; -m hogwild is the opt-in
     int gpus = 1, sync_every = 0, merge = CU2REC_MERGE_ADAPTIVE;
+    int rank_k = 0;  // -k: 0 = no ranking line
+    bool rank_given = false;
+    float rank_threshold = -INFINITY;
     int opt;
-    while ((opt = getopt(argc, argv, "c:m:g:s:w:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:")) != -1) {
         switch (opt) {
+            case 'k':
+                rank_given = true;
+                rank_k = std::atoi(optarg);
+                break;
+            case 't': {
+                char *end = nullptr;
+                rank_threshold = std::strtof(optarg, &end);
+                if (end == optarg || *end != '\0') rank_threshold = NAN;  // not a number: refused below
+                break;
+            }
             case 'g':
                 gpus = std::atoi(optarg);
                 break;
@@ -301,8 +318,20 @@ int main(int argc, char **argv) {
     }
     if (optind + 2 > argc) {
         std::cerr << "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong] [-g gpus] [-s sync_every] "
-                     "[-w adaptive|mean|weighted|sum] train.csv test.csv\n";
+                     "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
         return -1;
+    }
+    if (rank_given && (rank_k < 1 || rank_k > 256)) {
+        std::cerr << "mf: -k must be between 1 and 256\n";
+        return 1;
+    }
+    if (std::isnan(rank_threshold)) {
+        std::cerr << "mf: -t must be a number\n";
+        return 1;
+    }
+    if (rank_given && gpus > 1) {
+        std::cerr << "mf: -k is single-GPU only (not with -g)\n";
+        return 1;
     }
     if (gpus > 1) {
         if (mode == CU2REC_SGD_PINGPONG) {
@@ -353,6 +382,13 @@ int main(int argc, char **argv) {
         cu2rec::check(cu2rec_write_component(parent_dir.c_str(), base.c_str(), "user_bias", user_bias.data(), train.rows, 1, f));
         cu2rec::check(cu2rec_write_component(parent_dir.c_str(), base.c_str(), "item_bias", item_bias.data(), train.cols, 1, f));
         cu2rec::check(cu2rec_write_component(parent_dir.c_str(), base.c_str(), "global_bias", &gb, 1, 1, f));
+        if (rank_given) {  // the trained model ranks every user's unrated items against the test file
+            cu2rec_rank_metrics rm;
+            cu2rec::check(cu2rec_model_rank_metrics(model.h, d_train.h, d_test.h, rank_k, rank_threshold, &rm, nullptr));
+            const int K = rank_k;
+            std::printf("TEST: Precision@%d: %f Recall@%d: %f NDCG@%d: %f MAP@%d: %f HitRate@%d: %f Users: %d Skipped: %d\n", K,
+                        rm.precision, K, rm.recall, K, rm.ndcg, K, rm.map, K, rm.hit_rate, rm.users_evaluated, rm.users_skipped);
+        }
     } catch (const std::exception &e) {
         std::cerr << "mf: " << e.what() << "\n";
         return 2;

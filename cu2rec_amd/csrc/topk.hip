@@ -1,0 +1,475 @@
+// Fused top-k ranking and ranking metrics (include/cu2rec_amd.h: cu2rec_model_topk, cu2rec_model_rank_metrics).
+//
+// cu2rec_model_recommend writes the dense score matrix of a batch to HBM and radix-sorts every (user, item) pair to keep k of
+// them.  Here a workgroup owns 32 users and walks the whole catalogue 128 items at a time: the four wavefronts score their
+// 32 x 32 blocks exactly as scores_kernel does (score_tile.hpp: same staging chunks, same MFMA order, same bias sums), and
+// each score goes straight into selection -- nothing of size users x items is ever written.
+//
+// Selection ("Fused top-k"): every score becomes a 64-bit key whose unsigned order is recommend's order -- the
+// high word is rocPRIM's radix code of the float (descending sort; +0.0 and -0.0 one key), the low word the item index
+// reversed, so equal scores rank by ascending item.  A user keeps a running threshold (its k-th best key so far, in LDS)
+// and a candidate buffer of S = 256 or 512 keys (k <= 128 / k <= 256) in global workspace; a score that is not excluded, not
+// -inf and above the threshold is appended (LDS atomic on the user's count).  After each 128-item step, a user whose
+// buffer could overflow in the next step (count > S - 128) is compacted by one wavefront: bitonic sort of the S keys in
+// registers, the best k written back, the threshold raised to the k-th.  A last sort emits the list.
+//
+// Excluded items are a bitmap in global workspace, one bit per (listed user, item), built for each batch of users with
+// atomicOr from the exclusion CSR (rows unsorted, repeats harmless).  Batches bound the workspace: 256 MiB, or one
+// 32-user tile where a single tile needs more (4 bytes per catalogue item: less than Q itself).
+//
+// Ranking metrics run the same selection over the model's rows, then one thread per user checks its list against a
+// relevance bitmap of the test row and reduces in double (one final block-wide sum; one host synchronisation per call).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <vector>
+
+#include "device.hpp"
+#include "hip_check.hpp"
+#include "score_tile.hpp"
+
+namespace cu2rec {
+
+namespace {
+
+constexpr int kTopkMaxK = 256;
+constexpr int kStep = 4 * kTile;                        // items scored per workgroup step
+constexpr size_t kWorkspaceBudget = size_t(256) << 20;  // per batch of users
+constexpr unsigned kEncNegInf = 0x007FFFFFu;            // radix code of -inf: never listed (recommend's mask value)
+
+// rocPRIM's float radix code (radix_key_codec, with the descending sort's -0.0 == +0.0) in the high word; the low word is
+// (0x7FFFFFFF - item) << 1, so a larger key is a better (score, smaller item) pair, and bit 0 keeps the sign of a zero score
+// so that the listed score is the computed float bit for bit.  Key 0 is never a candidate: it marks an empty slot.
+__device__ __forceinline__ unsigned long long topk_key(float s, int item) {
+    unsigned b = __float_as_uint(s);
+    const unsigned negzero = b == 0x80000000u;
+    if (negzero) b = 0u;
+    const unsigned enc = b ^ ((b & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
+    return (static_cast<unsigned long long>(enc) << 32) | (static_cast<unsigned>(0x7FFFFFFF - item) << 1) | negzero;
+}
+
+__device__ __forceinline__ void topk_decode(unsigned long long key, int &item, float &score) {
+    if (key == 0ull) {
+        item = -1;
+        score = __builtin_nanf("");
+        return;
+    }
+    const unsigned enc = static_cast<unsigned>(key >> 32);
+    const unsigned b = (key & 1ull) ? 0x80000000u : enc ^ ((enc & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu);
+    item = 0x7FFFFFFF - static_cast<int>((static_cast<unsigned>(key) >> 1) & 0x7FFFFFFFu);
+    score = __uint_as_float(b);
+}
+
+// Bitonic sort, descending, of the wavefront's 64 E keys; element e of lane l is key e * 64 + l.  Strides below 64 pair lanes
+// (shuffles), larger ones pair registers of one lane.  Every index is a compile-time constant after unrolling.
+template <int E>
+__device__ __forceinline__ void wave_sort_desc(unsigned long long (&v)[E], int lane) {
+#pragma unroll
+    for (int size = 2; size <= 64 * E; size <<= 1) {
+#pragma unroll
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            if (stride >= 64) {
+                const int es = stride >> 6;
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    if (e & es) continue;
+                    const bool desc = ((e * 64 + lane) & size) == 0;  // this block ends up descending: the lower slot takes the max
+                    const unsigned long long a = v[e], b = v[e | es];
+                    const bool swap = desc ? a < b : a > b;
+                    v[e] = swap ? b : a;
+                    v[e | es] = swap ? a : b;
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const unsigned long long o = __shfl_xor(v[e], stride);
+                    const bool lower = (lane & stride) == 0, desc = ((e * 64 + lane) & size) == 0;
+                    v[e] = lower == desc ? max(v[e], o) : min(v[e], o);
+                }
+            }
+        }
+    }
+}
+
+// loads the count keys of a candidate buffer (the rest as empty), sorts them best first
+template <int E>
+__device__ __forceinline__ void load_sorted(unsigned long long (&v)[E], const unsigned long long *buf, int count, int lane) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) v[e] = e * 64 + lane < count ? buf[e * 64 + lane] : 0ull;
+    wave_sort_desc<E>(v, lane);
+}
+
+// One workgroup = 32 listed users (positions pos0 .. pos0 + 31 of `users`, model row ids) against every item.  LDS: the user
+// tile and four item tiles of scores_kernel, then the 32 thresholds and counts.  cand: [n_pos][64 E] keys of workspace.
+template <int E>
+__global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ P, int ldp, const float *__restrict__ user_bias,
+                                                   const int *__restrict__ users, int n_pos, const float *__restrict__ Q, int ldq,
+                                                   const float *__restrict__ item_bias, int n_items, float global_bias, int nslots,
+                                                   int chunk, const unsigned *__restrict__ mask, int words, int k,
+                                                   unsigned long long *__restrict__ cand, int *__restrict__ items_out,
+                                                   float *__restrict__ scores_out) {
+    constexpr int S = 64 * E;
+    extern __shared__ float4 smem[];
+    const int RS = chunk | 1;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int pos0 = blockIdx.x * kTile;
+    float4 *utile = smem, *itile = smem + (1 + wave) * kTile * RS;
+    unsigned long long *thr = reinterpret_cast<unsigned long long *>(smem + 5 * kTile * RS);
+    int *cnt = reinterpret_cast<int *>(thr + kTile);
+    const int r = lane & 31, h = lane >> 5;
+    if (threadIdx.x < kTile) {
+        thr[threadIdx.x] = 0ull;
+        cnt[threadIdx.x] = 0;
+    }
+    float ub[16];
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int pos = pos0 + acc_row(reg, h);
+        ub[reg] = pos < n_pos ? user_bias[users[pos]] : 0.f;
+    }
+    // wave w stages rows 8 w .. 8 w + 7 of the user tile: the row of this lane, gathered from P (clamped, zero past n_pos)
+    const int srow = 8 * wave + (lane >> 3), cs = lane & 7;
+    const float4 *prow = reinterpret_cast<const float4 *>(P + static_cast<size_t>(users[min(pos0 + srow, n_pos - 1)]) * ldp);
+    const bool whole = chunk >= nslots;  // the user tile is staged once and stays
+    for (int item_base = 0; item_base < n_items; item_base += kStep) {
+        const int item0 = item_base + wave * kTile;
+        const bool active = item0 < n_items;
+        f32x16 acc;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+        for (int slot0 = 0; slot0 < nslots; slot0 += chunk) {
+            const int n = min(chunk, nslots - slot0);
+            __syncthreads();  // every wave is done reading the tiles (previous chunk or step)
+            if (!whole || item_base == 0) {
+                for (int c = 0; c < (n + 7) >> 3; ++c) {
+                    const int slot = 8 * c + cs;
+                    const float4 v = prow[slot0 + min(slot, n - 1)];
+                    if (slot < n) utile[srow * RS + slot] = pos0 + srow < n_pos ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+            }
+            if (active) stage_rows(itile, Q, ldq, item0, n_items, slot0, n, RS, lane);
+            __syncthreads();
+            if (active) contract(acc, utile, itile, RS, n, r, h);
+        }
+        const int item = item0 + r;  // accumulator column = lane & 31
+        if (active && item < n_items) {
+            const float ibv = item_bias[item];
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int row = acc_row(reg, h), pos = pos0 + row;
+                if (pos >= n_pos) continue;
+                const float s = ((global_bias + ub[reg]) + ibv) + acc[reg];  // scores_kernel's expression
+                const bool masked = mask && ((mask[static_cast<size_t>(pos) * words + (item >> 5)] >> (item & 31)) & 1u);
+                const unsigned long long key = topk_key(s, item);
+                if (!masked && static_cast<unsigned>(key >> 32) > kEncNegInf && key > thr[row]) {
+                    const int at = atomicAdd(&cnt[row], 1);
+                    cand[static_cast<size_t>(pos) * S + at] = key;
+                }
+            }
+        }
+        __syncthreads();  // every insertion of this step is in place
+        for (int row = wave; row < kTile; row += 4) {
+            const int pos = pos0 + row, count = cnt[row];
+            if (pos >= n_pos || count <= S - kStep) continue;  // room for another step
+            unsigned long long *buf = cand + static_cast<size_t>(pos) * S;
+            unsigned long long v[E];
+            load_sorted<E>(v, buf, count, lane);
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                if (e * 64 + lane < k) buf[e * 64 + lane] = v[e];
+                if (e * 64 + lane == k - 1) thr[row] = v[e];
+            }
+            if (lane == 0) cnt[row] = k;
+        }
+    }
+    __syncthreads();
+    for (int row = wave; row < kTile; row += 4) {
+        const int pos = pos0 + row;
+        if (pos >= n_pos) continue;
+        unsigned long long v[E];
+        load_sorted<E>(v, cand + static_cast<size_t>(pos) * S, cnt[row], lane);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            const int j = e * 64 + lane;
+            if (j >= k) continue;
+            int it;
+            float sc;
+            topk_decode(v[e], it, sc);
+            items_out[static_cast<size_t>(pos) * k + j] = it;
+            scores_out[static_cast<size_t>(pos) * k + j] = sc;
+        }
+    }
+}
+
+// bit (position p, item) for every excluded item of the listed users
+__global__ __launch_bounds__(256) void exclude_mask_kernel(const int *__restrict__ indptr, const int *__restrict__ indices,
+                                                           int ex_rows, const int *__restrict__ users, int n_pos, int words,
+                                                           unsigned *__restrict__ mask) {
+    for (int p = blockIdx.x; p < n_pos; p += gridDim.x) {
+        const int u = users[p];
+        if (u >= ex_rows) continue;  // rows past the CSR's last row exclude nothing
+        for (int e = indptr[u] + threadIdx.x; e < indptr[u + 1]; e += blockDim.x) {
+            const int it = indices[e];
+            atomicOr(&mask[static_cast<size_t>(p) * words + (it >> 5)], 1u << (it & 31));
+        }
+    }
+}
+
+// relevance of test rows row0 .. row0 + n_pos - 1: bit (p, item) for relevant items of the catalogue, and |R_u| -- distinct
+// relevant items, those past the catalogue included -- in n_rel[p]
+__global__ __launch_bounds__(256) void relevant_kernel(const int *__restrict__ indptr, const int *__restrict__ indices,
+                                                       const float *__restrict__ data, int row0, int n_pos, int n_items, bool all,
+                                                       float threshold, int words, unsigned *__restrict__ rel, int *__restrict__ n_rel) {
+    for (int p = blockIdx.x; p < n_pos; p += gridDim.x) {
+        const int lo = indptr[row0 + p], hi = indptr[row0 + p + 1];
+        for (int e = lo + threadIdx.x; e < hi; e += blockDim.x) {
+            if (!(all || data[e] >= threshold)) continue;
+            const int it = indices[e];
+            bool first = true;
+            if (it < n_items) {
+                const unsigned bit = 1u << (it & 31);
+                first = !(atomicOr(&rel[static_cast<size_t>(p) * words + (it >> 5)], bit) & bit);
+            } else {  // no bit to claim: the first relevant occurrence in the row counts
+                for (int e2 = lo; e2 < e && first; ++e2) first = !(indices[e2] == it && (all || data[e2] >= threshold));
+            }
+            if (first) atomicAdd(&n_rel[p], 1);
+        }
+    }
+}
+
+// per model row u = row0 + p: {precision, recall, ndcg, ap, hit} of its list (include/cu2rec_amd.h), NaN when |R_u| = 0
+__global__ __launch_bounds__(256) void rank_metrics_kernel(const int *__restrict__ items, int k, const unsigned *__restrict__ rel,
+                                                           int words, const int *__restrict__ n_rel, int row0, int n_pos,
+                                                           double *__restrict__ per_user) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pos) return;
+    double *o = per_user + static_cast<size_t>(row0 + p) * 5;
+    const int nr = n_rel[p];
+    if (nr == 0) {
+        for (int i = 0; i < 5; ++i) o[i] = __builtin_nan("");
+        return;
+    }
+    int hits = 0;
+    double dcg = 0.0, ap = 0.0;
+    for (int j = 0; j < k; ++j) {
+        const int it = items[static_cast<size_t>(p) * k + j];
+        if (it < 0) break;  // padding only follows the listed items
+        if ((rel[static_cast<size_t>(p) * words + (it >> 5)] >> (it & 31)) & 1u) {
+            ++hits;
+            dcg += 1.0 / log2(static_cast<double>(j + 2));
+            ap += static_cast<double>(hits) / static_cast<double>(j + 1);
+        }
+    }
+    const int m = min(k, nr);
+    double idcg = 0.0;
+    for (int j = 0; j < m; ++j) idcg += 1.0 / log2(static_cast<double>(j + 2));
+    o[0] = static_cast<double>(hits) / static_cast<double>(k);
+    o[1] = static_cast<double>(hits) / static_cast<double>(nr);
+    o[2] = dcg / idcg;
+    o[3] = ap / static_cast<double>(m);
+    o[4] = hits > 0 ? 1.0 : 0.0;
+}
+
+__global__ __launch_bounds__(256) void fill_nan_kernel(double *__restrict__ x, size_t n) {
+    for (size_t i = static_cast<size_t>(blockIdx.x) * 256 + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * 256)
+        x[i] = __builtin_nan("");
+}
+
+// one workgroup: sums of the five metrics over evaluated rows (first value not NaN) and their count, in double
+__global__ __launch_bounds__(256) void rank_sum_kernel(const double *__restrict__ per_user, int rows, double *__restrict__ out) {
+    __shared__ double part[6][256];
+    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int u = threadIdx.x; u < rows; u += 256) {
+        const double *o = per_user + static_cast<size_t>(u) * 5;
+        if (isnan(o[0])) continue;
+        for (int i = 0; i < 5; ++i) s[i] += o[i];
+        s[5] += 1.0;
+    }
+    for (int i = 0; i < 6; ++i) part[i][threadIdx.x] = s[i];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (static_cast<int>(threadIdx.x) < w)
+            for (int i = 0; i < 6; ++i) part[i][threadIdx.x] += part[i][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 6) out[threadIdx.x] = part[threadIdx.x][0];
+}
+
+void check_k(const char *who, int k) {
+    require(k >= 1, who);
+    if (k > kTopkMaxK)
+        fail(CU2REC_EUNSUPPORTED, std::string(who) + ": k above 256 is not supported here; cu2rec_model_recommend ranks any k");
+}
+
+void check_exclude(const DeviceModel &m, const DeviceCsr *exclude, const char *what) {
+    require(!exclude || (exclude->rows <= m.rows && exclude->max_item < m.cols), what);
+}
+
+// The selection for one list of users, in batches over a bounded workspace.  extra: further workspace bytes the caller
+// needs per listed user (rank metrics' relevance bitmap), counted in the batch size.
+struct TopkRunner {
+    TopkRunner(const DeviceModel &m_, int k_, int n_total, bool masked, size_t extra) : m(m_), k(k_) {
+        E = k + kStep <= 256 ? 4 : 8;
+        nslots = (m.n_factors + 3) / 4;
+        chunk = nslots <= 63 ? nslots : 32;  // scores_kernel's chunking: the same scores
+        lds = static_cast<size_t>(5) * kTile * (chunk | 1) * sizeof(float4) + kTile * (sizeof(unsigned long long) + sizeof(int));
+        if (lds > kMaxLds) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_topk: the score tiles need more LDS than a workgroup has");
+        words = (m.cols + 31) / 32;
+        const size_t per_pos = static_cast<size_t>(64 * E) * 8 + (masked ? static_cast<size_t>(words) * 4 : 0) +
+                               static_cast<size_t>(k) * 8 + extra;
+        const size_t fit = std::max<size_t>(kTile, kWorkspaceBudget / per_pos / kTile * kTile);
+        batch = static_cast<int>(std::min<size_t>(fit, (static_cast<size_t>(n_total) + kTile - 1) / kTile * kTile));
+        cand.allocate(static_cast<size_t>(batch) * 64 * E);
+        if (masked) mask.allocate(static_cast<size_t>(batch) * words);
+        items.allocate(static_cast<size_t>(batch) * k);
+        scores.allocate(static_cast<size_t>(batch) * k);
+    }
+    // positions users_dev[0 .. n) (model rows) -> items / scores [n x k], device
+    void run(const DeviceCsr *exclude, const int *users_dev, int n, hipStream_t stream) {
+        if (mask.ptr) {
+            CU2REC_HIP(hipMemsetAsync(mask.ptr, 0, static_cast<size_t>(n) * words * sizeof(unsigned), stream));
+            if (exclude->nnz > 0)
+                hipLaunchKernelGGL(exclude_mask_kernel, dim3(std::min(n, 4096)), dim3(256), 0, stream, exclude->indptr.ptr,
+                                   exclude->indices.ptr, exclude->rows, users_dev, n, words, mask.ptr);
+        }
+        const void *kernel = E == 4 ? reinterpret_cast<const void *>(topk_kernel<4>) : reinterpret_cast<const void *>(topk_kernel<8>);
+        ensure_max_dynamic_lds(kernel, kMaxLds);
+        const dim3 grid((n + kTile - 1) / kTile);
+        if (E == 4)
+            hipLaunchKernelGGL(topk_kernel<4>, grid, dim3(256), lds, stream, m.P.ptr, m.ld, m.user_bias.ptr, users_dev, n, m.Q.ptr,
+                               m.ldq, m.item_bias.ptr, m.cols, m.global_bias, nslots, chunk, mask.ptr, words, k, cand.ptr,
+                               items.ptr, scores.ptr);
+        else
+            hipLaunchKernelGGL(topk_kernel<8>, grid, dim3(256), lds, stream, m.P.ptr, m.ld, m.user_bias.ptr, users_dev, n, m.Q.ptr,
+                               m.ldq, m.item_bias.ptr, m.cols, m.global_bias, nslots, chunk, mask.ptr, words, k, cand.ptr,
+                               items.ptr, scores.ptr);
+        CU2REC_HIP(hipGetLastError());
+    }
+    const DeviceModel &m;
+    int k, E, nslots, chunk, words, batch;
+    size_t lds;
+    DeviceBuffer<unsigned long long> cand;
+    DeviceBuffer<unsigned> mask;
+    DeviceBuffer<int> items;
+    DeviceBuffer<float> scores;
+};
+
+}  // namespace
+
+// the k best non-excluded items of each listed user, best first (recommend's order and scores)
+void model_topk(const DeviceModel &m, const DeviceCsr *exclude, const int *users, int n_users, int k, int *items_out,
+                float *scores_out) {
+    check_k("cu2rec_model_topk: k must be at least 1", k);
+    require(items_out && scores_out, "cu2rec_model_topk: null output");
+    const int n = users ? n_users : m.rows;
+    require(n >= 0, "cu2rec_model_topk: negative n_users");
+    if (users)
+        for (int i = 0; i < n; ++i) require(users[i] >= 0 && users[i] < m.rows, "cu2rec_model_topk: user id out of range");
+    check_exclude(m, exclude, "cu2rec_model_topk: exclusions exceed the model's shape");
+    if (n == 0) return;
+    require(m.cols > 0, "cu2rec_model_topk: no items");
+    require_device();
+    hipStream_t stream = nullptr;
+    std::vector<int> ids(users ? users : nullptr, users ? users + n : nullptr);
+    if (!users) {
+        ids.resize(n);
+        for (int i = 0; i < n; ++i) ids[i] = i;
+    }
+    DeviceBuffer<int> d_ids(ids.size());
+    d_ids.upload(ids.data(), ids.size());
+    TopkRunner run(m, k, n, exclude && exclude->nnz > 0, 0);
+    for (int p0 = 0; p0 < n; p0 += run.batch) {
+        const int b = std::min(run.batch, n - p0);
+        run.run(exclude, d_ids.ptr + p0, b, stream);
+        CU2REC_HIP(hipMemcpyAsync(items_out + static_cast<size_t>(p0) * k, run.items.ptr, static_cast<size_t>(b) * k * sizeof(int),
+                                  hipMemcpyDeviceToHost, stream));
+        CU2REC_HIP(hipMemcpyAsync(scores_out + static_cast<size_t>(p0) * k, run.scores.ptr,
+                                  static_cast<size_t>(b) * k * sizeof(float), hipMemcpyDeviceToHost, stream));
+    }  // stream order: a batch's copies are done before the next batch overwrites the workspace
+    CU2REC_HIP(hipStreamSynchronize(stream));
+}
+
+void model_rank_metrics(const DeviceModel &m, const DeviceCsr *exclude, const DeviceCsr *test, int k, float threshold,
+                        cu2rec_rank_metrics *out, double *per_user) {
+    check_k("cu2rec_model_rank_metrics: k must be at least 1", k);
+    require(test && out, "cu2rec_model_rank_metrics: null argument");
+    require(!std::isnan(threshold), "cu2rec_model_rank_metrics: threshold is NaN");
+    require(test->rows <= m.rows, "cu2rec_model_rank_metrics: the test set has rows past the model's rows");
+    check_exclude(m, exclude, "cu2rec_model_rank_metrics: exclusions exceed the model's shape");
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    *out = cu2rec_rank_metrics{k, 0, m.rows, nan, nan, nan, nan, nan};
+    if (m.rows == 0) return;
+    require(m.cols > 0, "cu2rec_model_rank_metrics: no items");
+    require_device();
+    hipStream_t stream = nullptr;
+    const int n = test->rows;  // rows past the test set's last row have no relevant items
+    DeviceBuffer<double> d_per(static_cast<size_t>(m.rows) * 5), d_sum(6);
+    hipLaunchKernelGGL(fill_nan_kernel, dim3(std::min<size_t>((d_per.count + 255) / 256, 4096)), dim3(256), 0, stream, d_per.ptr,
+                       d_per.count);
+    CU2REC_HIP(hipGetLastError());
+    if (n > 0) {
+        const int words = (m.cols + 31) / 32;
+        std::vector<int> ids(n);
+        for (int i = 0; i < n; ++i) ids[i] = i;
+        DeviceBuffer<int> d_ids(n);
+        d_ids.upload(ids.data(), n);
+        TopkRunner run(m, k, n, exclude && exclude->nnz > 0, static_cast<size_t>(words) * 4 + sizeof(int));
+        DeviceBuffer<unsigned> rel(static_cast<size_t>(run.batch) * words);
+        DeviceBuffer<int> n_rel(run.batch);
+        const bool all = std::isinf(threshold) && threshold < 0;
+        for (int p0 = 0; p0 < n; p0 += run.batch) {  // stream order keeps the workspace of one batch until the next needs it
+            const int b = std::min(run.batch, n - p0);
+            run.run(exclude, d_ids.ptr + p0, b, stream);
+            CU2REC_HIP(hipMemsetAsync(rel.ptr, 0, static_cast<size_t>(b) * words * sizeof(unsigned), stream));
+            CU2REC_HIP(hipMemsetAsync(n_rel.ptr, 0, static_cast<size_t>(b) * sizeof(int), stream));
+            hipLaunchKernelGGL(relevant_kernel, dim3(std::min(b, 4096)), dim3(256), 0, stream, test->indptr.ptr, test->indices.ptr,
+                               test->data.ptr, p0, b, m.cols, all, threshold, words, rel.ptr, n_rel.ptr);
+            hipLaunchKernelGGL(rank_metrics_kernel, dim3((b + 255) / 256), dim3(256), 0, stream, run.items.ptr, k, rel.ptr, words,
+                               n_rel.ptr, p0, b, d_per.ptr);
+            CU2REC_HIP(hipGetLastError());
+        }
+    }
+    hipLaunchKernelGGL(rank_sum_kernel, dim3(1), dim3(256), 0, stream, d_per.ptr, m.rows, d_sum.ptr);
+    CU2REC_HIP(hipGetLastError());
+    double sums[6];
+    CU2REC_HIP(hipMemcpyAsync(sums, d_sum.ptr, sizeof(sums), hipMemcpyDeviceToHost, stream));
+    if (per_user) CU2REC_HIP(hipMemcpyAsync(per_user, d_per.ptr, d_per.count * sizeof(double), hipMemcpyDeviceToHost, stream));
+    CU2REC_HIP(hipStreamSynchronize(stream));
+    const int evaluated = static_cast<int>(sums[5]);
+    out->users_evaluated = evaluated;
+    out->users_skipped = m.rows - evaluated;
+    if (evaluated > 0) {
+        out->precision = sums[0] / evaluated;
+        out->recall = sums[1] / evaluated;
+        out->ndcg = sums[2] / evaluated;
+        out->map = sums[3] / evaluated;
+        out->hit_rate = sums[4] / evaluated;
+    }
+}
+
+}  // namespace cu2rec
+
+using namespace cu2rec;
+
+extern "C" {
+
+int cu2rec_model_topk(const cu2rec_model *m, const cu2rec_csr *exclude, const int *users, int n_users, int k, int *items_out,
+                      float *scores_out) {
+    return guarded([&] {
+        require(m, "model is null");
+        model_topk(unwrap(m), exclude ? &unwrap(exclude) : nullptr, users, n_users, k, items_out, scores_out);
+    });
+}
+
+int cu2rec_model_rank_metrics(const cu2rec_model *m, const cu2rec_csr *exclude, const cu2rec_csr *test, int k, float threshold,
+                              cu2rec_rank_metrics *out, double *per_user) {
+    return guarded([&] {
+        require(m, "model is null");
+        model_rank_metrics(unwrap(m), exclude ? &unwrap(exclude) : nullptr, test ? &unwrap(test) : nullptr, k, threshold, out,
+                           per_user);
+    });
+}
+
+}  // extern "C"

@@ -388,6 +388,32 @@ int cu2rec_model_scores_host(const cu2rec_model *m, float *scores_host /* rows *
  * rows * k entries; a user with fewer than k unrated items gets -1 / NaN padding.  Items with equal scores come out in
  * ascending item index (the sort is stable). */
 int cu2rec_model_recommend(const cu2rec_model *m, const cu2rec_csr *rated, int k, int *items_out, float *scores_out);
+/* The k best non-excluded items of each listed user, without the dense score matrix: scores on the matrix cores and
+ * selection on chip, workspace bounded by a batch of users (not by rows x cols).  Scores and order are recommend's, bit for
+ * bit: the same float score; descending in rocPRIM's float radix order (+0.0 and -0.0 tie, +NaN above +inf), ties by
+ * ascending item; a score of -inf is never listed; -1 / NaN padding when fewer than k candidates remain.  exclude: row u holds
+ * user u's excluded items (unsorted, repeats allowed; NULL: nothing; rows past its last row exclude nothing).  users: host
+ * list of n_users model rows (duplicates allowed), or NULL for every row of the model (n_users ignored).  items_out /
+ * scores_out: host, n_users x k.  1 <= k <= 256; a larger k is CU2REC_EUNSUPPORTED (cu2rec_model_recommend ranks any k). */
+int cu2rec_model_topk(const cu2rec_model *m, const cu2rec_csr *exclude, const int *users, int n_users, int k,
+                      int *items_out, float *scores_out);
+/* Ranking quality of the model's top-k lists (cu2rec_model_topk over every row, excluding `exclude`) against a test set.
+ * For each model row u:
+ *   R_u = distinct items of test row u with rating >= threshold (threshold -INFINITY: every rating; NaN: CU2REC_EINVAL).
+ *         Items >= the model's cols count in |R_u| but are never hit; R_u is not reduced by `exclude`.
+ *   Users with |R_u| = 0 are skipped and counted.  Test rows past the model's rows: CU2REC_EINVAL.
+ *   L_u = the top-k list without padding; hits = |L_u n R_u|.
+ *   precision = hits / k (k even when L_u is shorter); recall = hits / |R_u|; hit = [hits > 0];
+ *   ndcg = DCG / IDCG, DCG = sum over j with L_u[j] in R_u of 1 / log2(j + 2), IDCG = sum over j < min(k, |R_u|) of the same;
+ *   ap = (1 / min(k, |R_u|)) * sum over j with L_u[j] in R_u of (hits in L_u[0..j]) / (j + 1).
+ * Each reported value is the mean over evaluated users, summed in double on the device (NaN when no user is evaluated).
+ * per_user (host, may be NULL): rows x 5 doubles {precision, recall, ndcg, ap, hit}, NaN for skipped users. */
+typedef struct cu2rec_rank_metrics {
+    int k, users_evaluated, users_skipped;
+    double precision, recall, ndcg, map, hit_rate;
+} cu2rec_rank_metrics;
+int cu2rec_model_rank_metrics(const cu2rec_model *m, const cu2rec_csr *exclude, const cu2rec_csr *test, int k,
+                              float threshold, cu2rec_rank_metrics *out, double *per_user);
 
 /* ------------------------------------------------------------------------------------------
  * train() -- replaces both overloads of train (training.h:12-15, training.cu:21-217):
