@@ -9,7 +9,7 @@ import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-# CU2REC_AMD_LIB: load another build of the same library (ablation / tuning builds)
+# CU2REC_AMD_LIB: load another build of the same sources (the test-hooks library, tools/build_variant.sh)
 LIB_PATH = os.environ.get("CU2REC_AMD_LIB") or os.path.join(HERE, "libcu2rec_amd.so")
 
 
@@ -111,7 +111,6 @@ SIGNATURES = {
     "cu2rec_blocksolve_lookahead_blocks": (C.c_int, [C.c_int]),
     "cu2rec_blocksolve_topology": (C.c_int, [C.c_char_p, C.c_size_t]),
     "cu2rec_csr_blocksolve_items": (C.c_int, [_P]),
-    "cu2rec_debug_blocksolve_stamps": (C.c_int, [_P, C.c_int]),
     "cu2rec_loss_workspace_bytes": (C.c_size_t, []),
     "cu2rec_loss": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, _P, _P, C.c_float, C.c_int, _P,
                               _P, _dp, _dp, _fp, _fp, _P]),

@@ -90,63 +90,6 @@ __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * 
 
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
-// development aid: one record per wavefront, written by its first lane when it ends.  Builds with -DCU2REC_BS_TRACE=1
-// (tools/build_variant.sh) additionally drain the memory queue at four points of a kernel and record when (marks).
-#ifndef CU2REC_BS_TRACE
-#define CU2REC_BS_TRACE 0
-#endif
-#ifndef CU2REC_BS_ABLATE  // timing-only builds (tools/build_variant.sh): 1 no global stores in the solver's loop, 2 no (C) products,
-                          // 4 the loaders do not write user rows into LDS, 8 no (A) products, 16 no (B) products
-#define CU2REC_BS_ABLATE 0
-#endif
-constexpr int kStampWords = 8;
-struct WaveStamp {
-    unsigned long long t0;
-#if CU2REC_BS_TRACE
-    unsigned long long marks[4] = {0, 0, 0, 0};
-    unsigned long long c0 = clock64();  // shader clock (s_memtime): with the 100 MHz wall clock, the frequency the wavefront ran at
-#endif
-    __device__ __forceinline__ explicit WaveStamp(const BsIteration &it) : t0(it.stamps ? wall_clock64() : 0) {}
-    __device__ __forceinline__ void restart(const BsIteration &it) { t0 = it.stamps ? wall_clock64() : 0; }  // (a persistent workgroup's next unit)
-    __device__ __forceinline__ void fine(const BsIteration &it, int i) {  // -DCU2REC_BS_TRACE=2: the inside of phases 1 and 3
-#if CU2REC_BS_TRACE == 2
-        if (it.stamps) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            marks[i] = wall_clock64();
-        }
-#endif
-    }
-    __device__ __forceinline__ void mark(const BsIteration &it, int i) {
-#if CU2REC_BS_TRACE == 1
-        if (it.stamps) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // LDS / scalar only: stores in flight are not part of a phase
-            marks[i] = wall_clock64();
-        }
-#endif
-    }
-    __device__ __forceinline__ void span(int i, unsigned long long ticks) {  // trace builds: a duration, shown as a mark that far behind the start
-#if CU2REC_BS_TRACE == 1
-        marks[i] = t0 + ticks;
-#endif
-    }
-    __device__ __forceinline__ void done(const BsIteration &it, int kernel, int id) const {
-        if (!it.stamps || (threadIdx.x & 63) != 0) return;
-        const int seg = it.stamps_cap / 8;  // one segment of the buffer per kernel: no atomics, no contention
-        if (id >= seg) return;
-        unsigned long long *r = it.stamps + 1 + kStampWords * (static_cast<size_t>(kernel) * seg + id);
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        r[0] = static_cast<unsigned long long>(kernel) | (static_cast<unsigned long long>(xcc & 15u) << 32);
-        r[1] = static_cast<unsigned long long>(id);
-        r[2] = t0;
-        r[3] = wall_clock64();
-#if CU2REC_BS_TRACE
-        for (int i = 0; i < 4; ++i) r[4 + i] = marks[i];
-        if (kernel == 3 || kernel == 4) r[7] = t0 + (clock64() - c0);  // loaders, update: shader cycles in the slot of the last mark
-#endif
-    }
-};
-
 // ---- decay tables: x * a^k is applied as x - adel[k] * x so that the rounding of a^k (one ulp of 1.0, the same sign
 // every block) cannot bias a hot item's decay rate; the deltas are computed in double from the float hyper-parameters
 __global__ void bs_tables_kernel(SgdHyper h, float *__restrict__ t) {
@@ -325,7 +268,7 @@ constexpr int kGramTabFloats = 2 * kB;  // a^d | c^d, d in [0, 64)
 __host__ __device__ inline size_t gram_tile_float4s(int nslots) { return static_cast<size_t>(kB) * (nslots | 1); }
 
 // One block of phase 1 (the body of bs_gram_kernel): its rows -> LDS, the Gram tiles, (I + N)^-1, the record.  Workgroup uniform.
-__device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &it, int g, float4 *bs_smem, WaveStamp &stamp) {
+__device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &it, int g, float4 *bs_smem) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const BsBlockDesc bd = it.blocks[g];
     if (bd.n_valid == 0) return;  // (the grid is an upper bound of the iteration's blocks)
@@ -347,7 +290,6 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
         tab[lane] = it.tables[kTabApow + lane];
         tab[kB + lane] = it.tables[kTabCpow + lane];
     }
-    stamp.mark(it, 0);
     // gather: 8 lanes x 16 bytes per row piece, 8 rows per pass, this wavefront's 16 rows.  Every load is unconditional at
     // a clamped address: a predicated load makes the compiler branch around it and wait for each one separately.
     const int rsub = lane >> 3, cs = lane & 7;
@@ -372,8 +314,6 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
         }
     }
     __syncthreads();
-    stamp.mark(it, 1);
-    stamp.fine(it, 0);  // rows gathered
     const int k = lane & 31, h = lane >> 5;
     f32x16 acc;
 #pragma unroll
@@ -403,7 +343,6 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
             }
         }
     }
-    stamp.fine(it, 1);  // Gram products issued (the accumulator is read right behind)
     __syncthreads();  // every wavefront is through with the rows: the tiles take their place
     if (wave < 3) {
         // N[K][J] = lr (c^d + a^d G[K][J]), d = K - 1 - J (links of the block), for J < K < n_valid; the powers by v_exp_f32 from
@@ -427,8 +366,6 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
         }
     }
     __syncthreads();
-    stamp.mark(it, 2);
-    stamp.fine(it, 2);  // lr L in LDS
     if (wave == 0) {
     // M11 (lanes 0-31) and M22 (lanes 32-63): lane = column, m[kk] = M[kk][column]
     float m[kH];
@@ -463,7 +400,6 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
 #pragma unroll
     for (int kk = 0; kk < kH; ++kk) Ms[(h * kH + kk) * kMS + k] = m[kk];
     __builtin_amdgcn_wave_barrier();
-    stamp.fine(it, 3);  // the two triangular inverses
     // T = N10 M11, then M21 = -M22 T
     f32x16 tacc, macc;
 #pragma unroll
@@ -490,7 +426,6 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
     }
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) Ns[acc_row(reg, h) * kMS + k] = -macc[reg];  // M21 where N00 was (its last reader is done)
-    stamp.mark(it, 3);
     }  // wave 0
     __syncthreads();
     // The block's record leaves the workgroup: [M11 | M21 | M22 | base], 16 bytes per lane (phase 2 is queued behind this launch:
@@ -503,15 +438,12 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
         for (int q = 0; q < 3; ++q) *reinterpret_cast<f32x4 *>(rec + q * kH * kH + 4 * t) = *reinterpret_cast<const f32x4 *>(src[q] + row * kMS + 4 * c4);
         if (t < kB / 4) *reinterpret_cast<f32x4 *>(rec + kBsFactorFloats + 4 * t) = *reinterpret_cast<const f32x4 *>(basev + 4 * t);
     }
-    stamp.done(it, 1, 4 * g + wave);
 }
 
 __global__ __launch_bounds__(256, 4) void bs_gram_kernel(SgdArgs a, BsIteration it) {
     extern __shared__ float4 bs_smem[];
-    const int wave = threadIdx.x >> 6;
     const int g = static_cast<int>(blockIdx.x) - it.la_grid;  // (the first la_grid workgroups of the launch: the cross blocks)
     __builtin_amdgcn_s_setprio(2);  // (above the walk beside us and the schedule's kernels: this launch is on the iteration's critical path)
-    WaveStamp stamp(it);
     // (every workgroup counts itself through, used or not: the side stream's gate waits for the whole grid)
     struct Through {
         unsigned long long *count;
@@ -527,7 +459,6 @@ __global__ __launch_bounds__(256, 4) void bs_gram_kernel(SgdArgs a, BsIteration 
         const BsChainDesc last = it.chains[it.la_ranks - 1];
         const int la_end = min(last.blk0 + (last.len + kB - 1) / kB, it.la_cap);
         for (int gb = g + it.la_grid; gb < la_end; gb += it.la_grid) gram_cross_block(a, it, gb, bs_smem);
-        stamp.done(it, 7, 4 * (g + it.la_grid) + wave);
         return;
     }
     // (one workgroup per slot of the block table, max_blocks of them -- the worst case; most find their descriptor empty and leave.  Launching
@@ -535,7 +466,7 @@ __global__ __launch_bounds__(256, 4) void bs_gram_kernel(SgdArgs a, BsIteration 
     // gram_block it cost this kernel 55 spilled registers, as an out-of-line function a scratch frame -- 92 instead of 79 us per
     // iteration on the ML-20M shape either way (round 6, profiles/r06_launch_bounds.txt).  Phase 3 and the walk, whose kernels have the
     // registers to spare, do stride: bs_update_kernel, sgd_ordered_kernel.)
-    gram_block(a, it, g, bs_smem, stamp);
+    gram_block(a, it, g, bs_smem);
 }
 
 // ---- phase 2: the chains ----------------------------------------------------------------------------------------------
@@ -591,11 +522,10 @@ __device__ __forceinline__ void solvers_meet(unsigned *meet, unsigned target, in
 //                            eight groups summed across lanes (DPP row rotate, permlane16/32 swaps)              -- barrier
 //            (the barrier is the one per block all eight wavefronts share: it hands the ring slot back to the loaders)
 //   One wavefront doing all of it issued ~500 instructions per block and took 1.35 us of the block's 1.8 us; the
-//   loaders alone sustain a block per 0.42 us (tools/build_variant.sh ablations, profiles/README.md).
+//   loaders alone sustain a block per 0.42 us (measured by ablation, profiles/README.md).
 // SW: float4 slots per row quarter (4 * SW >= nslots).
 template <int SW>
-__device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration &it, float4 *bs_smem, WaveStamp &stamp, int chain,
-                                            const BsChainDesc &cd) {
+__device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration &it, float4 *bs_smem, const BsChainDesc &cd) {
     const int begin = cd.begin, len = cd.len;
     if (len <= 0) return;  // workgroup uniform
     const int nblk = (len + kB - 1) / kB;
@@ -619,7 +549,7 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
             s.next_val = load_val(t + kDepth);
             const f32x4 *row = reinterpret_cast<const f32x4 *>(a.P + static_cast<size_t>(static_cast<uint32_t>(val >> 32)) * a.ldp);
 #pragma unroll
-            for (int i = 0; i < NLT; ++i) s.rows[i] = (CU2REC_BS_ABLATE & 32) ? f32x4{0.01f, 0.01f, 0.01f, 0.01f} : row[min(tp + 4 * i, nslots - 1)];
+            for (int i = 0; i < NLT; ++i) s.rows[i] = row[min(tp + 4 * i, nslots - 1)];
         };
         auto issue_rec = [&](Stage<NLT> &s, int t) {  // phase 1's record of the block
             const float *rec = it.Mbuf + static_cast<size_t>(g0 + min(t, nblk - 1)) * kBsRecFloats;
@@ -639,7 +569,7 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
 #pragma unroll
             for (int i = 0; i < NLT; ++i) {
                 const int slot = tp + 4 * i;
-                if (!(CU2REC_BS_ABLATE & 4) && slot < nslots) sl[tr * RS + slot] = rv ? s.rows[i] : z;
+                if (slot < nslots) sl[tr * RS + slot] = rv ? s.rows[i] : z;
             }
             f32x4 *mt = sl + kB * RS;  // three tiles of 32 rows x 8 float4, rows kMS floats apart
 #pragma unroll
@@ -684,7 +614,6 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
                 __syncthreads();
             }
         }
-        stamp.done(it, 3, chain * 4 + ((tid >> 6) & 3));
         return;
     }
 
@@ -721,9 +650,7 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
     const float lr = a.h.lr;
     const int kr = k & 31;
     const bool upper = k >= kH;
-    stamp.mark(it, 0);
     __syncthreads();  // block 0 is in the ring
-    stamp.mark(it, 1);
     for (int m = 0; m < n_intervals; ++m) {
         const bool live = m < nblk;  // workgroup uniform
         const int n = min(kB, len - kB * m);
@@ -752,12 +679,10 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
                 qv[i] = lds4(qrow + w * SW + i);
             }
             f32x2 dacc[2] = {dup2(0.f), dup2(0.f)};
-            if (!(CU2REC_BS_ABLATE & 8)) {
 #pragma unroll
-                for (int i = 0; i < SW; ++i) {
-                    dacc[0] = fma2(lo2(pv[i]), lo2(qv[i]), dacc[0]);
-                    dacc[1] = fma2(hi2(pv[i]), hi2(qv[i]), dacc[1]);
-                }
+            for (int i = 0; i < SW; ++i) {
+                dacc[0] = fma2(lo2(pv[i]), lo2(qv[i]), dacc[0]);
+                dacc[1] = fma2(hi2(pv[i]), hi2(qv[i]), dacc[1]);
             }
             const f32x2 ds = dacc[0] + dacc[1];
             reinterpret_cast<float *>(dpart)[4 * k + w] = ds.x + ds.y;
@@ -773,13 +698,11 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
             __builtin_amdgcn_wave_barrier();
             const float4 *rv = reinterpret_cast<const float4 *>(rbuf) + 4 * w;
             f32x2 eacc[2] = {dup2(0.f), dup2(0.f)};
-            if (!(CU2REC_BS_ABLATE & 16)) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const f32x4 r4 = lds4(rv + t);
-                    eacc[0] = fma2(lo2(mq[t]), lo2(r4), eacc[0]);
-                    eacc[1] = fma2(hi2(mq[t]), hi2(r4), eacc[1]);
-                }
+            for (int t = 0; t < 4; ++t) {
+                const f32x4 r4 = lds4(rv + t);
+                eacc[0] = fma2(lo2(mq[t]), lo2(r4), eacc[0]);
+                eacc[1] = fma2(hi2(mq[t]), hi2(r4), eacc[1]);
             }
             const f32x2 es = eacc[0] + eacc[1];
             reinterpret_cast<float *>(epart)[4 * k + w] = es.x + es.y;
@@ -789,7 +712,7 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
         if (live) {
             const f32x4 e4 = lds4(epart + k);
             const float e = (e4.x + e4.y) + (e4.z + e4.w);
-            if (!(CU2REC_BS_ABLATE & 1) && w == 0) {  // the block's errors, four to a lane, for phase 3
+            if (w == 0) {  // the block's errors, four to a lane, for phase 3
                 const float e0 = k < n ? e : 0.f;
                 const f32x4 e4v = {e0, dpp_move<0x55>(e0), dpp_move<0xAA>(e0), dpp_move<0xFF>(e0)};  // quad lanes 0..3
                 if ((k & 3) == 0) {
@@ -808,20 +731,18 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
             for (int p = 0; p < NP; ++p) {  // lane (slot, group): sum over the group's 8 links of w_k P[k][slot]
                 const int sq = 8 * p + sl, slot = w * SW + sq;
                 const bool ok = sq < SW && slot < nslots;
-                if (!(CU2REC_BS_ABLATE & 1) && ok && kg == 0) *reinterpret_cast<f32x4 *>(qdst + 4 * slot) = q4[p];
+                if (ok && kg == 0) *reinterpret_cast<f32x4 *>(qdst + 4 * slot) = q4[p];
                 const float4 *colp = tile + (8 * kg) * RS + min(slot, nslots - 1);
                 f32x4 tb[8], wb[2];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) tb[i] = lds4(colp + i * RS);
                 wb[0] = lds4(wv), wb[1] = lds4(wv + 1);
                 f32x2 ulo = dup2(0.f), uhi = dup2(0.f);
-                if (!(CU2REC_BS_ABLATE & 2)) {
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) {
-                        const f32x2 ww = dup2(wb[i >> 2][i & 3]);
-                        ulo = fma2(ww, lo2(tb[i]), ulo);
-                        uhi = fma2(ww, hi2(tb[i]), uhi);
-                    }
+                for (int i = 0; i < 8; ++i) {
+                    const f32x2 ww = dup2(wb[i >> 2][i & 3]);
+                    ulo = fma2(ww, lo2(tb[i]), ulo);
+                    uhi = fma2(ww, hi2(tb[i]), uhi);
                 }
                 float u[4] = {ulo.x, ulo.y, uhi.x, uhi.y};
 #pragma unroll
@@ -837,8 +758,6 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
             }
         }
         __syncthreads();
-        if (m == nblk / 2) stamp.mark(it, 2);
-        if (m == nblk - 1) stamp.mark(it, 3);
     }
     {
         if (kg == 0) {
@@ -851,7 +770,6 @@ __device__ __forceinline__ void solve_chain(const SgdArgs &a, const BsIteration 
         }
         if (tid == 0) a.item_bias[y] = b;
     }
-    stamp.done(it, 2, chain * 4 + w);
 }
 
 // ---- phase 2, the longest chains: the look-ahead form ---------------------------------------------------------------------------
@@ -887,10 +805,7 @@ __host__ __device__ inline size_t la_lds_bytes(int nslots) {
 enum { kSyC0 = 0, kSyC1 = 1, kSyE = 2, kSyG = 3, kSyLdP = 4, kSyLdR = 8, kSyR = 12, kSyAbort = 13 };  // (C0 | C1, LdP[4], LdR[4]: read together)
 
 // waits until *word >= target; bounded: gives up after 2 s (or as soon as another wait of the workgroup has), sets the status word
-__device__ __forceinline__ void la_wait(unsigned *sy, int word, unsigned target, const BsIteration &it, unsigned long long *waited = nullptr) {
-#if CU2REC_BS_TRACE
-    const unsigned long long tw = wall_clock64();
-#endif
+__device__ __forceinline__ void la_wait(unsigned *sy, int word, unsigned target, const BsIteration &it) {
     unsigned polls = 0;
     unsigned long long t0 = 0;
     while (__hip_atomic_load(sy + word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < target) {
@@ -905,9 +820,6 @@ __device__ __forceinline__ void la_wait(unsigned *sy, int word, unsigned target,
         }
     }
     asm volatile("" ::: "memory");  // nothing behind the wait is read in front of it
-#if CU2REC_BS_TRACE
-    if (waited) *waited += wall_clock64() - tw;
-#endif
 }
 __device__ __forceinline__ void la_post(unsigned *sy, int word, unsigned value) {
     asm volatile("" ::: "memory");  // everything written so far is issued in front of the count
@@ -915,10 +827,7 @@ __device__ __forceinline__ void la_post(unsigned *sy, int word, unsigned value) 
 }
 
 // ... until all four counters sy[word .. word + 3] (16-byte aligned) have reached target: ONE LDS read per poll
-__device__ __forceinline__ void la_wait4(unsigned *sy, int word, unsigned target, const BsIteration &it, unsigned long long *waited = nullptr) {
-#if CU2REC_BS_TRACE
-    const unsigned long long tw = wall_clock64();
-#endif
+__device__ __forceinline__ void la_wait4(unsigned *sy, int word, unsigned target, const BsIteration &it) {
     unsigned polls = 0;
     unsigned long long t0 = 0;
     for (;;) {
@@ -938,15 +847,9 @@ __device__ __forceinline__ void la_wait4(unsigned *sy, int word, unsigned target
         }
     }
     asm volatile("" ::: "memory");
-#if CU2REC_BS_TRACE
-    if (waited) *waited += wall_clock64() - tw;
-#endif
 }
 // ... until both sy[word] and sy[word + 1] (8-byte aligned) have
-__device__ __forceinline__ void la_wait2(unsigned *sy, int word, unsigned target, const BsIteration &it, unsigned long long *waited = nullptr) {
-#if CU2REC_BS_TRACE
-    const unsigned long long tw = wall_clock64();
-#endif
+__device__ __forceinline__ void la_wait2(unsigned *sy, int word, unsigned target, const BsIteration &it) {
     unsigned polls = 0;
     unsigned long long t0 = 0;
     for (;;) {
@@ -965,14 +868,10 @@ __device__ __forceinline__ void la_wait2(unsigned *sy, int word, unsigned target
         }
     }
     asm volatile("" ::: "memory");
-#if CU2REC_BS_TRACE
-    if (waited) *waited += wall_clock64() - tw;
-#endif
 }
 
 template <int NSM>
-__device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIteration &it, float4 *smem, WaveStamp &stamp, int chain,
-                                                const BsChainDesc &cd) {
+__device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIteration &it, float4 *smem, const BsChainDesc &cd) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nslots = a.nslots, RS = nslots | 1;
     const int begin = cd.begin, len = cd.len, nblk = (len + kB - 1) / kB, g0 = cd.blk0, y = cd.item;
@@ -996,7 +895,6 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
         // around a load makes the compiler wait for everything in flight.
         const int w = wave - 4;
         __builtin_amdgcn_s_setprio(2);
-        unsigned long long wt[2] = {0, 0};
         constexpr int NQ = (NSM + 3) / 4;
         const int idx0 = w * kB * NQ + lane;
         const int row0 = idx0 / nslots, slot0 = idx0 - row0 * nslots;
@@ -1030,7 +928,7 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
         };
         auto commit = [&](const LaStage &st, int i) {
             if (i >= kLaPRing) {  // the slot's last reader: the state wavefronts, block i - 3
-                la_wait2(sy, kSyC0, static_cast<unsigned>(i - kLaPRing + 1), it, &wt[0]);
+                la_wait2(sy, kSyC0, static_cast<unsigned>(i - kLaPRing + 1), it);
             }
             {
                 f32x4 *tile = reinterpret_cast<f32x4 *>(pring + (i % kLaPRing) * kB * RS);
@@ -1045,7 +943,7 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
                 }
             }
             la_post(sy, kSyLdP + w, static_cast<unsigned>(i + 1));
-            if (i >= kLaRRing) la_wait(sy, kSyR, static_cast<unsigned>(i - kLaRRing + 1), it, &wt[1]);  // the chain wavefront has taken record i - 2
+            if (i >= kLaRRing) la_wait(sy, kSyR, static_cast<unsigned>(i - kLaRRing + 1), it);  // the chain wavefront has taken record i - 2
             f32x4 *rr = reinterpret_cast<f32x4 *>(rring + (i % kLaRRing) * kLaRec4);
             if (w < 2) {
 #pragma unroll
@@ -1086,11 +984,6 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
                 issue(st[u], i + kLaDepth, st[u].next_val);
             }
         }
-        stamp.span(0, wt[0]);
-        stamp.span(1, wt[1]);
-        stamp.span(2, 1);
-        stamp.span(3, 1);
-        stamp.done(it, 3, chain * 4 + w);
         return;
     }
 
@@ -1098,11 +991,10 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
         // ------------------------------------------------------------------------------------------------------------- dots
         __syncthreads();
         __builtin_amdgcn_s_setprio(2);
-        unsigned long long wt[2] = {0, 0};
         for (int i = 0; i < nblk; ++i) {
             const int src = max(i - 1, 0);
-            la_wait4(sy, kSyLdP, static_cast<unsigned>(i + 1), it, &wt[0]);
-            if (src > 0) la_wait2(sy, kSyC0, static_cast<unsigned>(src), it, &wt[1]);
+            la_wait4(sy, kSyLdP, static_cast<unsigned>(i + 1), it);
+            if (src > 0) la_wait2(sy, kSyC0, static_cast<unsigned>(src), it);
             const float4 *prow = pring + (i % kLaPRing) * kB * RS + lane * RS;
             const float4 *qv = qbuf + (src & 1) * kLaQ4;
             // two halves, every read of a half in flight before its first product: one LDS latency per half, not one per slot
@@ -1132,11 +1024,6 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
             gbuf[(i & 1) * kB + lane] = ds.x + ds.y;
             la_post(sy, kSyG, static_cast<unsigned>(i + 1));
         }
-        stamp.span(0, wt[0]);
-        stamp.span(1, wt[1]);
-        stamp.span(2, 1);
-        stamp.span(3, 1);
-        stamp.done(it, 2, chain * 4 + 3);
         return;
     }
 
@@ -1156,11 +1043,10 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
         }
         __syncthreads();
         __builtin_amdgcn_s_setprio(2);
-        unsigned long long wt[1] = {0};
         for (int i = 0; i < nblk; ++i) {
             const int n = min(kB, len - kB * i);
             const float adel_n = tab[kTabAdel + n];
-            la_wait(sy, kSyE, static_cast<unsigned>(i + 1), it, &wt[0]);
+            la_wait(sy, kSyE, static_cast<unsigned>(i + 1), it);
             const float4 *tile = pring + (i % kLaPRing) * kB * RS;
             const float4 *wv = reinterpret_cast<const float4 *>(wbuf + (i & 1) * kB) + 2 * kg;
             float *qdst = it.qstart + static_cast<size_t>(g0 + i) * a.ldq;
@@ -1208,11 +1094,6 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
                 if (slot < nslots) qd[slot] = q4[pp];
             }
         }
-        stamp.span(0, wt[0]);
-        stamp.span(1, 1);
-        stamp.span(2, 1);
-        stamp.span(3, 1);
-        stamp.done(it, 2, chain * 4 + wave);
         return;
     }
 
@@ -1224,16 +1105,14 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
     asm volatile("" ::"v"(b_cur));
     __syncthreads();
     __builtin_amdgcn_s_setprio(3);
-    stamp.mark(it, 0);
     const int kr = k & 31;
     const bool upper = k >= kH;
-    unsigned long long wt[2] = {0, 0};
     // record i in registers one block ahead: this lane's row of M (links 0-31: [M11 row | 0], links 32-63: [M21 row | M22 row]), its
     // row of the cross block, its base error -- read while the other wavefronts work on the item row, not on the dependent path
     f32x4 m4[16], n4[16];
     float base;
     auto take_record = [&](int i) {
-        la_wait4(sy, kSyLdR, static_cast<unsigned>(i + 1), it, &wt[0]);
+        la_wait4(sy, kSyLdR, static_cast<unsigned>(i + 1), it);
         const float4 *rr = rring + (i % kLaRRing) * kLaRec4;
         const float *Mt = reinterpret_cast<const float *>(rr);
         const float4 *mlo = reinterpret_cast<const float4 *>(Mt + ((upper ? kH : 0) + kr) * kMS);
@@ -1274,7 +1153,7 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
         const int kd = i > 0 ? k + kB : k;
         const float adel_k = tab[kTabAdel + kd], cdel_k = tab[kTabCdel + kd];
         const float bsrc = i > 0 ? b_prev : b_cur;
-        la_wait(sy, kSyG, static_cast<unsigned>(i + 1), it, &wt[1]);
+        la_wait(sy, kSyG, static_cast<unsigned>(i + 1), it);
         const float gd = gbuf[(i & 1) * kB + k];
         const float pre = k < n ? (base - (bsrc - cdel_k * bsrc)) - (gd - adel_k * gd) : 0.f;
         tbuf[k] = pre - t0;
@@ -1308,11 +1187,7 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
         b_prev = b_cur;
         b_cur = b_next;
     }
-    stamp.span(1, wt[0]);
-    stamp.span(2, wt[1]);
-    stamp.mark(it, 3);
     if (k == 0) a.item_bias[y] = b_cur;
-    stamp.done(it, 2, chain * 4);
 }
 
 // The join with the side stream: one thread of an extra workgroup in the LAST launch of the iteration on the main stream (phase 3).
@@ -1338,18 +1213,17 @@ __device__ __forceinline__ void await_iteration_end(const BsIteration &it) {
 template <int SW>
 __global__ __launch_bounds__(512) void bs_solve_kernel(SgdArgs a, BsIteration it) {
     extern __shared__ float4 bs_smem[];
-    WaveStamp stamp(it);
     if (it.gram_done && threadIdx.x == 0)  // (the side stream's gate lets the side kernel go once the chains hold their CUs)
         __hip_atomic_fetch_add(it.solve_started, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int chain = blockIdx.x;
     const BsChainDesc cd = it.chains[chain];
     if constexpr (SW <= 8) {
         if (chain_is_lookahead(it, chain, cd)) {  // workgroup uniform
-            chain_lookahead<(4 * SW < kLaMaxSlots ? 4 * SW : kLaMaxSlots)>(a, it, bs_smem, stamp, chain, cd);
+            chain_lookahead<(4 * SW < kLaMaxSlots ? 4 * SW : kLaMaxSlots)>(a, it, bs_smem, cd);
             return;
         }
     }
-    solve_chain<SW>(a, it, bs_smem, stamp, chain, cd);
+    solve_chain<SW>(a, it, bs_smem, cd);
 }
 
 // ---- phase 3: the user side of every hot block ---------------------------------------------------------------------
@@ -1362,7 +1236,7 @@ __global__ __launch_bounds__(512) void bs_solve_kernel(SgdArgs a, BsIteration it
 // 9 -- and the kernel's duration IS one wavefront's latency, every block's workgroup being resident at once.)
 constexpr int kUpdMaxWaves = (4 * kBsMaxSlots + 63) / 64;
 
-__device__ __forceinline__ void update_block(const SgdArgs &a, const BsIteration &it, int g, int nwaves, WaveStamp &stamp) {
+__device__ __forceinline__ void update_block(const SgdArgs &a, const BsIteration &it, int g) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const BsBlockDesc bd = it.blocks[g];
     if (bd.n_valid == 0) return;  // workgroup uniform
@@ -1376,7 +1250,6 @@ __device__ __forceinline__ void update_block(const SgdArgs &a, const BsIteration
     const float qs = it.qstart[static_cast<size_t>(g) * a.ldq + colc];
     const float e_all = it.ebuf[static_cast<size_t>(g) * kB + lane];
     const float e = mine ? e_all : 0.f;
-    stamp.fine(it, 0);  // user ids
     float p[kB];
 #pragma unroll
     for (int k = 0; k < kB; ++k) {
@@ -1385,7 +1258,6 @@ __device__ __forceinline__ void update_block(const SgdArgs &a, const BsIteration
     }
     float q = qs;
     const float p_reg = a.h.p_reg, q_reg = a.h.q_reg;
-    stamp.fine(it, 1);  // loads issued; errors, start row
 #pragma unroll
     for (int k = 0; k < kB; ++k) {
         const float ek = lane_value(e, k);
@@ -1398,7 +1270,6 @@ __device__ __forceinline__ void update_block(const SgdArgs &a, const BsIteration
 #pragma unroll
     for (int k = 0; k < kB; ++k) asm volatile("" : "+v"(p[k]));  // (the values exist HERE: no sinking of the walk into the stores)
     __builtin_amdgcn_sched_barrier(0);
-    stamp.fine(it, 2);  // new rows
     if (col < ncols) {
 #pragma unroll
         for (int k = 0; k < kB; ++k) {
@@ -1409,13 +1280,11 @@ __device__ __forceinline__ void update_block(const SgdArgs &a, const BsIteration
         const float ub = a.user_bias[x];
         a.user_bias[x] = ub + lr * (e - a.h.ub_reg * ub);  // mf_sequential.cu:140
     }
-    stamp.done(it, 4, g * nwaves + wave);
 }
 
 // One workgroup per block.
-__global__ __launch_bounds__(64 * kUpdMaxWaves) void bs_update_kernel(SgdArgs a, BsIteration it, int nwaves) {
+__global__ __launch_bounds__(64 * kUpdMaxWaves) void bs_update_kernel(SgdArgs a, BsIteration it) {
     const int g = blockIdx.x;
-    WaveStamp stamp(it);
     __builtin_amdgcn_s_setprio(2);
     if (g == it.launch_blocks) {  // the extra workgroup of the launch (side_seq set)
         if (threadIdx.x == 0) await_iteration_end(it);
@@ -1424,7 +1293,7 @@ __global__ __launch_bounds__(64 * kUpdMaxWaves) void bs_update_kernel(SgdArgs a,
     // (launch_blocks workgroups stride through the dense block table, like phase 1's; update_block keeps nothing in LDS)
     for (int blk = g; blk < it.max_blocks; blk += it.launch_blocks) {
         if (it.blocks[blk].n_valid == 0) break;  // workgroup uniform
-        update_block(a, it, blk, nwaves, stamp);
+        update_block(a, it, blk);
     }
 }
 
@@ -1443,9 +1312,6 @@ void launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
 }  // namespace
 
 namespace {
-unsigned long long *g_stamps = nullptr;
-int g_stamps_cap = 0;
-
 // One status word per device (set by a device-side wait that gave up) and its pinned host copy, refreshed after every
 // block-solve call; like the resident launches' (resident.hip).
 struct BsFault {
@@ -1580,16 +1446,6 @@ int bs_topology_query(std::string *why) {
     if (dev >= static_cast<int>(g_topo.size())) return -1;
     if (why) *why = g_topo[dev].why;
     return g_topo[dev].mode;
-}
-
-void bs_set_stamps(unsigned long long *buf, int cap) {
-    g_stamps = buf;
-    g_stamps_cap = buf ? cap : 0;
-}
-
-void bs_get_stamps(unsigned long long **buf, int *cap) {
-    *buf = g_stamps;
-    *cap = g_stamps_cap;
 }
 
 unsigned *bs_status_word() {
@@ -1743,7 +1599,7 @@ void bs_launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream
 void bs_launch_update(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
     if (it.n_hot <= 0 || it.max_blocks <= 0) return;
     const int nwaves = (4 * a.nslots + 63) / 64;
-    hipLaunchKernelGGL(bs_update_kernel, dim3(it.launch_blocks + (it.side_seq ? 1 : 0)), dim3(64 * nwaves), 0, stream, a, it, nwaves);
+    hipLaunchKernelGGL(bs_update_kernel, dim3(it.launch_blocks + (it.side_seq ? 1 : 0)), dim3(64 * nwaves), 0, stream, a, it);
     CU2REC_HIP(hipGetLastError());
 }
 

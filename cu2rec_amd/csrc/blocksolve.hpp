@@ -72,16 +72,9 @@ struct BsIteration {
     const unsigned long long *side_seq;  // (or null) the word the signal kernel sets ...
     unsigned long long side_target;      // ... and the number the extra workgroup of phase 3's launch waits for
     unsigned long long *gram_done;       // [32 x 16]  phase-1 workgroups through (32 shards, 128 bytes apart), over all iterations so far (or null)
-    // development aid (cu2rec_debug_blocksolve_stamps): [0] = entries appended so far, then {kernel, id, start, end}
-    // per wavefront in units of the 100 MHz s_memrealtime clock; nullptr in normal operation
     unsigned long long wait_ticks;    // bound of the device-side waits (bs_wait_ticks(): CU2REC_BS_WAIT_S, 2 s), 100 MHz ticks
-    unsigned long long *stamps;
-    int stamps_cap;
 };
 
-// process-wide stamp buffer for the launches that follow (nullptr = off)
-void bs_set_stamps(unsigned long long *buf, int cap);
-void bs_get_stamps(unsigned long long **buf, int *cap);
 unsigned long long bs_wait_ticks();
 bool bs_supported(int nslots);
 bool bs_lookahead_supported(int nslots);  // rows of at most 31 float4 slots: the look-ahead form's rings fit the LDS

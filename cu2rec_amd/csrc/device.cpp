@@ -588,13 +588,6 @@ int cu2rec_csr_blocksolve_items(const cu2rec_csr *train) {
     return rc == CU2REC_OK ? n : -1;
 }
 
-int cu2rec_debug_blocksolve_stamps(void *buffer, int capacity) {
-    return guarded([&] {
-        require(capacity >= 0, "cu2rec_debug_blocksolve_stamps: bad capacity");
-        bs_set_stamps(static_cast<unsigned long long *>(buffer), capacity);
-    });
-}
-
 size_t cu2rec_loss_workspace_bytes(void) { return sizeof(double) * (2 * kMaxPartialBlocks + 2); }
 
 int cu2rec_loss(const int *indptr, const int *indices, const float *data, int n_rows, int nnz, const float *P, int ldp,

@@ -8,10 +8,6 @@
 
 #include "sgd_device.hpp"
 
-#ifndef CU2REC_BARRIER_ABLATE
-#define CU2REC_BARRIER_ABLATE 0  // timing-only builds: 64 / 128 barrier without its release / acquire fence
-#endif
-
 namespace cu2rec {
 namespace gridbar {
 
@@ -87,8 +83,7 @@ __device__ __forceinline__ void barrier_arrive(const RA &ra, unsigned phase, Bar
                                                     __HIP_MEMORY_SCOPE_AGENT);
         const bool leader = old + 1 == phase * static_cast<unsigned>(bs->n_mine);
         if (leader) {
-            if (!(CU2REC_BARRIER_ABLATE & 64))                        // 64: timing only, no L2 write-back
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // write back this XCD's dirty L2 lines
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // write back this XCD's dirty L2 lines
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the compiler may drop its own wait here)
             __hip_atomic_fetch_add(ra.words + kWTop, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -113,8 +108,7 @@ __device__ __forceinline__ bool barrier_wait(const RA &ra, unsigned phase, Barri
         } else {
             ok = spin_until(gen, phase, ra.status);
         }
-        if (!(CU2REC_BARRIER_ABLATE & 128))                         // 128: timing only, no L1 invalidate
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the invalidate issued in barrier_arrive has completed
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the invalidate issued in barrier_arrive has completed
         bs->ok = ok ? 1 : 0;
     }
     __syncthreads();

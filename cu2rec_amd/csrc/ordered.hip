@@ -30,7 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#include <hipcub/hipcub.hpp>
+#include <cstring>  // (rocPRIM's headers call memset without including it)
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
@@ -61,13 +61,9 @@ using namespace dev;
 // its 256: ONE workgroup sorts a segment of n_rows pairs, and with the default block the kernel sat on its 64 CUs for 6.6 ms of
 // every 15 on the Netflix shape (480,189 pairs a segment) -- a quarter of the chip that the throughput-bound phases of that shape
 // then lack (iterations beside it 306 instead of 238 us).  Four times the threads: a quarter of the time.
-#ifndef CU2REC_SEG_BLOCK
-#define CU2REC_SEG_BLOCK 1024
-#endif
-#ifndef CU2REC_SEG_ITEMS
-#define CU2REC_SEG_ITEMS 8
-#endif
-using SegSortConfig = rocprim::segmented_radix_sort_config<8, rocprim::kernel_config<CU2REC_SEG_BLOCK, CU2REC_SEG_ITEMS>,
+constexpr unsigned kSegBlock = 1024;
+constexpr unsigned kSegItems = 8;
+using SegSortConfig = rocprim::segmented_radix_sort_config<8, rocprim::kernel_config<kSegBlock, kSegItems>,
                                                            rocprim::WarpSortConfig<8, 4, 256, 64, 16, 8, 256>, true>;
 
 constexpr int kHotChains = 256;  // most popular items: their chains run in the two-wave form (run_hot_block_duo)
@@ -202,10 +198,6 @@ __device__ __forceinline__ float chain_step(const SgdArgs &a, Row<J> &p, Row<J> 
     return ub + a.h.lr * (err - a.h.ub_reg * ub);                         // :140 (new user bias)
 }
 
-#ifndef CU2REC_ABLATE
-#define CU2REC_ABLATE 0  // timing-only builds of the hot path: 8 = no user-side updates, 16 = no LDS publishes by the
-#endif                   // compute wave, 32 = no row loads (results are wrong; never set in the shipped library)
-
 constexpr int kWide = 32;  // lanes per chain in the wide layout (one float4 slot per lane, 65 <= ld <= 128)
 
 typedef unsigned int uint2_t __attribute__((ext_vector_type(2)));
@@ -290,46 +282,6 @@ __device__ __forceinline__ void store_wide_row(float *__restrict__ base, size_t 
     }
 }
 
-#ifndef CU2REC_WALK_NT
-#define CU2REC_WALK_NT 0  // tuning builds (tools/build_variant.sh): 1 user rows of the chains' kernel STORED non-temporally, 2 loaded so, 3 both
-#endif
-// a user row is written once per iteration and not read again before the next one: the streaming form keeps it from displacing item
-// rows in the XCD's L2 (measured on the Netflix shape in round 6: profiles/r06_netflix_walk_experiments.txt)
-template <int W, int S>
-__device__ __forceinline__ void store_user_wide_row(float *__restrict__ base, size_t row, int ld, int nslots, int lane, const WideRow<S> &r) {
-#if CU2REC_WALK_NT & 1
-    float4 *p = reinterpret_cast<float4 *>(base + row * static_cast<size_t>(ld));
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const int slot = lane + W * s;
-        if (slot < nslots) {
-            const vec4f v = {r.v[s].x, r.v[s].y, r.v[s].z, r.v[s].w};
-            __builtin_nontemporal_store(v, reinterpret_cast<vec4f *>(&p[slot]));
-        }
-    }
-#else
-    store_wide_row<W, S>(base, row, ld, nslots, lane, r);
-#endif
-}
-
-template <int J>
-__device__ __forceinline__ void store_user_row(float *__restrict__ base, size_t row, int ld, int nslots, int lane, const Row<J> &r) {
-#if CU2REC_WALK_NT & 1
-    store_row_stream<J>(base, row, ld, nslots, lane, r);
-#else
-    store_row<J>(base, row, ld, nslots, lane, r);
-#endif
-}
-
-template <int J>
-__device__ __forceinline__ Row<J> load_user_row(const float *__restrict__ base, size_t row, int ld, int nslots, int lane) {
-#if CU2REC_WALK_NT & 2
-    return load_row_stream<J>(base, row, ld, nslots, lane);
-#else
-    return load_row<J>(base, row, ld, nslots, lane);
-#endif
-}
-
 // this wave's entries of the tile starting at tile_start, one per lane 0..part-1 (mirrored on the other lanes)
 template <int W, int S>
 __device__ __forceinline__ uint64_t duo_load_vals(const uint64_t *__restrict__ vals, int tile_start, int end, int part,
@@ -384,7 +336,7 @@ __device__ __forceinline__ void duo_update_users(DuoLds<W, S> &l, int buf, int n
                 pn.v[s].z = step(po.z, qo.z, err, a.h.lr, a.h.p_reg);
                 pn.v[s].w = step(po.w, qo.w, err, a.h.lr, a.h.p_reg);
             }
-            store_user_wide_row<W, S>(a.P, static_cast<size_t>(l.user[buf][e]), a.ldp, a.nslots, lane, pn);
+            store_wide_row<W, S>(a.P, static_cast<size_t>(l.user[buf][e]), a.ldp, a.nslots, lane, pn);
         }
     }
     const int mine = kPart * part + lane;
@@ -404,11 +356,9 @@ __device__ __forceinline__ void duo_step_a(DuoLds<W, S> &l, int buf, int t, cons
     for (int s = 1; s < S; ++s) acc = acc + slot_dot(q.v[s], po.v[s]);
     const float dot = W == kWide ? row_sum16(cross_row_sum(acc)) : row_sum16(acc);  // canonical order either way
     const float err = rating - (((a.global_bias + ub) + ib) + dot);
-#if !(CU2REC_ABLATE & 16)
 #pragma unroll
     for (int s = 0; s < S; ++s) l.qold[buf][t][s][lane] = q.v[s];
     if (lane == 0) l.err[buf][t] = err;
-#endif
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const float4 qo = q.v[s];
@@ -515,12 +465,8 @@ __device__ __forceinline__ void run_hot_block_duo(const SgdArgs &a, const uint32
     __syncthreads();
     auto b_phase = [&](int k, DuoTileRegs<W, S> &ready, DuoTileRegs<W, S> &loading) {
         const uint64_t v_after = duo_load_vals<W, S>(vals, begin + (k + 3) * kTile, end, part, lane);
-#if !(CU2REC_ABLATE & 32)
         duo_load_rows<W, S>(loading, a, v_next, lane);  // tile k + 2
-#endif
-#if !(CU2REC_ABLATE & 8)
         if (k >= 1) duo_update_users<W, S>(l, (k - 1) & 1, min(max(len - (k - 1) * kTile, 0), kTile), a, part, lane);
-#endif
         duo_publish<W, S>(l, (k + 1) & 1, ready, part, lane);  // tile k + 1, after the reads of that buffer just above
         v_next = v_after;
     };
@@ -557,10 +503,7 @@ template <int J>
 __device__ __forceinline__ void walk_group(const SgdArgs &a, const uint32_t *__restrict__ keys, const uint64_t *__restrict__ vals,
                                            int n_active, const int *__restrict__ item_of_rank, uint32_t item_mask, int n_hot,
                                            int start) {
-#ifndef CU2REC_WALK_D
-#define CU2REC_WALK_D 4  // user rows a walking group keeps in flight (tuning builds: tools/build_variant.sh)
-#endif
-    constexpr int D = CU2REC_WALK_D;
+    constexpr int D = 4;  // user rows a walking group keeps in flight
     const int lane = threadIdx.x & (kGroup - 1);
     const int gshift = threadIdx.x & 48;  // this group's lanes in the wavefront
     if (start >= n_active) return;
@@ -585,7 +528,7 @@ __device__ __forceinline__ void walk_group(const SgdArgs &a, const uint32_t *__r
 #pragma unroll
         for (int d = 0; d < D; ++d) {
             const int x = static_cast<int>(link(mv, d, nw) >> 32);
-            cur[d] = load_user_row<J>(a.P, static_cast<size_t>(x), a.ldp, a.nslots, lane);
+            cur[d] = load_row<J>(a.P, static_cast<size_t>(x), a.ldp, a.nslots, lane);
             cub[d] = a.user_bias[x];
         }
     };
@@ -612,7 +555,7 @@ __device__ __forceinline__ void walk_group(const SgdArgs &a, const uint32_t *__r
 #pragma unroll
             for (int d = 0; d < D; ++d) {
                 const int x = static_cast<int>(link(myval, b0 + D + d, nw) >> 32);
-                nxt[d] = load_user_row<J>(a.P, static_cast<size_t>(x), a.ldp, a.nslots, lane);
+                nxt[d] = load_row<J>(a.P, static_cast<size_t>(x), a.ldp, a.nslots, lane);
                 nub[d] = a.user_bias[x];
             }
 #pragma unroll
@@ -621,7 +564,7 @@ __device__ __forceinline__ void walk_group(const SgdArgs &a, const uint32_t *__r
                     const uint64_t val = link(myval, b0 + d, nw);
                     const int x = static_cast<int>(val >> 32);
                     const float new_ub = chain_step<J>(a, cur[d], q, cub[d], ib, __uint_as_float(static_cast<uint32_t>(val)));
-                    store_user_row<J>(a.P, static_cast<size_t>(x), a.ldp, a.nslots, lane, cur[d]);
+                    store_row<J>(a.P, static_cast<size_t>(x), a.ldp, a.nslots, lane, cur[d]);
                     if (lane == 0) a.user_bias[x] = new_ub;
                 }
             }
@@ -1110,7 +1053,6 @@ void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t st
                 it.status = status;
                 it.solve_started = solve_started.ptr;
                 it.wait_ticks = bs_wait_ticks();
-                bs_get_stamps(&it.stamps, &it.stamps_cap);
                 const int *ranges = chain_ranges[slot].ptr + static_cast<size_t>(off + b) * (n_range_ranks + 1);
                 if (device_join) {
                     // (the host's counts move only behind a launch that succeeded: a launch that throws leaves gate and counters in
@@ -1131,23 +1073,13 @@ void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t st
                     if (!(dbg & 16)) bs_launch_signal(side_seq.ptr, side_seq_host, upd);
                     bs_launch_update(a, it, stream);
                 } else {
-                    // (test build, TIMING ONLY, results wrong: 64 the side kernel alone, 128 the three phases alone -- what each path costs
-                    // on an otherwise idle chip, tools/path_isolation.sh)
                     if (upd_pending) CU2REC_HIP(hipStreamWaitEvent(stream, ev_upd, 0));  // join: rows the next phase 1 reads
-                    if (!(dbg & 64)) {
-                        bs_launch_gram(a, it, stream, ev_gram);
-                        CU2REC_HIP(hipStreamWaitEvent(upd, ev_gram, 0));
-                        bs_launch_solve(a, it, stream);
-                    } else {
-                        CU2REC_HIP(hipEventRecord(ev_gram, stream));
-                        CU2REC_HIP(hipStreamWaitEvent(upd, ev_gram, 0));
-                    }
-                    if (!(dbg & 128))
-                        launch_chains(a, it.keys, it.vals, n_active, item_of_rank.ptr, item_mask, std::max(n_duo_bs, n_hot_bs), upd, n_hot_bs, ranges, ev_upd,
-                                      walk_bound_bs);
-                    else
-                        CU2REC_HIP(hipEventRecord(ev_upd, upd));
-                    if (!(dbg & 64)) bs_launch_update(a, it, stream);
+                    bs_launch_gram(a, it, stream, ev_gram);
+                    CU2REC_HIP(hipStreamWaitEvent(upd, ev_gram, 0));
+                    bs_launch_solve(a, it, stream);
+                    launch_chains(a, it.keys, it.vals, n_active, item_of_rank.ptr, item_mask, std::max(n_duo_bs, n_hot_bs), upd, n_hot_bs, ranges, ev_upd,
+                                  walk_bound_bs);
+                    bs_launch_update(a, it, stream);
                     upd_pending = true;
                 }
             }

@@ -51,15 +51,6 @@
 #include "sampler.hpp"
 #include "sgd_device.hpp"
 
-#ifndef CU2REC_RES_ABLATE
-#define CU2REC_RES_ABLATE 0  // timing-only builds (tools/build_variant.sh), bits: 1 no grid barrier, 2 no updates, 4 no item-row
-                             // stores, 64 / 128 barrier without its release / acquire fence; never set in the shipped library
-#endif
-
-#ifndef CU2REC_RES_D2
-#define CU2REC_RES_D2 3  // item rows in flight per group at two float4 per lane (f = 68..128)
-#endif
-
 namespace cu2rec {
 
 namespace {
@@ -68,6 +59,7 @@ using namespace dev;
 
 constexpr int kResBlock = 512;                    // 8 wavefronts = 2 per SIMD: up to 256 VGPRs each
 constexpr int kResGroups = kResBlock / kGroup;    // 32 user groups per workgroup
+constexpr int kResD2 = 3;                         // item rows in flight per group at two float4 per lane (f = 68..128)
 
 using namespace gridbar;  // the barrier: grid_barrier.hpp
 
@@ -228,7 +220,7 @@ __global__ __launch_bounds__(kResBlock) void sgd_resident_kernel(SgdArgs a, Resi
     int item[M];
     float rating[M];
     draw(a.iter0, item, rating);
-    const bool synced = !(CU2REC_RES_ABLATE & 1) && a.iters > 1;
+    const bool synced = a.iters > 1;
     if (synced) {
         if (threadIdx.x == 0) barrier_census(ra, &s_barrier);
         __syncthreads();
@@ -267,16 +259,14 @@ __global__ __launch_bounds__(kResBlock) void sgd_resident_kernel(SgdArgs a, Resi
         // to the end of the loop, keeping err * q (4 J registers) alive per user until then: pin it to this step
 #pragma unroll
         for (int j = 0; j < J; ++j) asm volatile("" : "+v"(pc.v[j].x), "+v"(pc.v[j].y), "+v"(pc.v[j].z), "+v"(pc.v[j].w));
-        if (!(CU2REC_RES_ABLATE & 4)) {                                                              // sgd.cu:61,70
-            // the sink is addressed as a byte offset from Q / item_bias so that "real row or sink" is a select
-            // between two integers (a select between two pointers comes back as a branch around the stores)
-            const int64_t row_off = q_active[s] ? static_cast<int64_t>(q_item[s]) * a.ldq * 4 : sink_row_off;
-            store_wrapped<J>(reinterpret_cast<float *>(reinterpret_cast<char *>(a.Q) + row_off), sl, q[s]);
-            // all 16 lanes store the same value to the same address: one request, and no lane == 0 branch
-            const int64_t bias_off = q_active[s] ? static_cast<int64_t>(q_item[s]) * 4 : sink_bias_off;
-            *reinterpret_cast<float *>(reinterpret_cast<char *>(a.item_bias) + bias_off) =
-                ib + a.h.lr * (err - a.h.ib_reg * ib);  // sgd.cu:71
-        }
+        // sgd.cu:61,70.  The sink is addressed as a byte offset from Q / item_bias so that "real row or sink" is a select
+        // between two integers (a select between two pointers comes back as a branch around the stores)
+        const int64_t row_off = q_active[s] ? static_cast<int64_t>(q_item[s]) * a.ldq * 4 : sink_row_off;
+        store_wrapped<J>(reinterpret_cast<float *>(reinterpret_cast<char *>(a.Q) + row_off), sl, q[s]);
+        // all 16 lanes store the same value to the same address: one request, and no lane == 0 branch
+        const int64_t bias_off = q_active[s] ? static_cast<int64_t>(q_item[s]) * 4 : sink_bias_off;
+        *reinterpret_cast<float *>(reinterpret_cast<char *>(a.item_bias) + bias_off) =
+            ib + a.h.lr * (err - a.h.ib_reg * ib);  // sgd.cu:71
         const float ub_new = ub + a.h.lr * (err - a.h.ub_reg * ub);  // sgd.cu:67
         ub_l = (lane == src && q_active[s]) ? ub_new : ub_l;
     };
@@ -319,56 +309,54 @@ __global__ __launch_bounds__(kResBlock) void sgd_resident_kernel(SgdArgs a, Resi
 #pragma unroll
         for (int m = 0; m < M; ++m) asm volatile("" ::"v"(item[m]), "v"(rating[m]));
 
-        if (!(CU2REC_RES_ABLATE & 2)) {
 #pragma unroll
-            for (int r = 0; r < R + D; ++r) {
-                if (r >= D) {
-                    const int c = r - D;
-                    if (c < RREG) {
-                        consume(p[c < RREG ? c : 0], c, c % D);
-                    } else {  // an LDS row: in, one update, out
-                        Row<J> row = lds_load(c - RREG);
-                        consume(row, c, c % D);
-                        lds_store(c - RREG, row);
-                    }
+        for (int r = 0; r < R + D; ++r) {
+            if (r >= D) {
+                const int c = r - D;
+                if (c < RREG) {
+                    consume(p[c < RREG ? c : 0], c, c % D);
+                } else {  // an LDS row: in, one update, out
+                    Row<J> row = lds_load(c - RREG);
+                    consume(row, c, c % D);
+                    lds_store(c - RREG, row);
                 }
-                if (r < R) issue(r, r % D);
-                // keep a step's shuffles and address arithmetic inside the step: hoisted to the top of the
-                // straight-line code they cost ~10 live registers per user, which the resident rows need
-                __builtin_amdgcn_sched_barrier(0);
             }
-            if constexpr (PART) {
-                const uint64_t it_now = a.iter0 + static_cast<uint64_t>(k);
-                const int n_chunks = (ra.streamed + kGroup - 1) / kGroup;
-                Chunk cur, nxt;
-                chunk_bounds(0, cur);
-                chunk_draw(it_now, cur);
-                for (int ch = 0; ch < n_chunks; ++ch) {
-                    asm volatile("" ::"v"(cur.item), "v"(cur.rating), "v"(cur.ub), "v"(cur.n), "v"(cur.x));  // (the chunk's scalars are here)
-                    Row<J> ps[D];
+            if (r < R) issue(r, r % D);
+            // keep a step's shuffles and address arithmetic inside the step: hoisted to the top of the
+            // straight-line code they cost ~10 live registers per user, which the resident rows need
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (PART) {
+            const uint64_t it_now = a.iter0 + static_cast<uint64_t>(k);
+            const int n_chunks = (ra.streamed + kGroup - 1) / kGroup;
+            Chunk cur, nxt;
+            chunk_bounds(0, cur);
+            chunk_draw(it_now, cur);
+            for (int ch = 0; ch < n_chunks; ++ch) {
+                asm volatile("" ::"v"(cur.item), "v"(cur.rating), "v"(cur.ub), "v"(cur.n), "v"(cur.x));  // (the chunk's scalars are here)
+                Row<J> ps[D];
 #pragma unroll
-                    for (int u = 0; u < kGroup + D; ++u) {
-                        if (u >= D) {
-                            const int c = u - D;
-                            Row<J> row = ps[c % D];
-                            consume_with(row, cur.ub, c, c % D);
-                            const int64_t p_off =
-                                q_active[c % D] ? static_cast<int64_t>(__shfl(cur.x, c, kGroup)) * a.ldp * 4 : sink_p_off;
-                            store_wrapped<J>(reinterpret_cast<float *>(reinterpret_cast<char *>(a.P) + p_off), sl, row);
-                        }
-                        if (u < kGroup) {
-                            issue_from(cur.item, cur.rating, cur.n, u, u % D);
-                            ps[u % D] = load_wrapped<J>(a.P + static_cast<size_t>(__shfl(cur.x, u, kGroup)) * a.ldp, sl);
-                        }
-                        // the next chunk's scalars and draw ride along (a chunk past the last one: clamped, unused)
-                        if (u == 1) chunk_bounds(ch + 1, nxt);
-                        if (u == kGroup / 2) chunk_draw(it_now, nxt);
-                        __builtin_amdgcn_sched_barrier(0);
+                for (int u = 0; u < kGroup + D; ++u) {
+                    if (u >= D) {
+                        const int c = u - D;
+                        Row<J> row = ps[c % D];
+                        consume_with(row, cur.ub, c, c % D);
+                        const int64_t p_off =
+                            q_active[c % D] ? static_cast<int64_t>(__shfl(cur.x, c, kGroup)) * a.ldp * 4 : sink_p_off;
+                        store_wrapped<J>(reinterpret_cast<float *>(reinterpret_cast<char *>(a.P) + p_off), sl, row);
                     }
-                    // the users' biases go back (a lane without a user, or a user without ratings: its own old value, or nothing)
-                    if (cur.n > 0) a.user_bias[cur.x] = cur.ub;
-                    cur = nxt;
+                    if (u < kGroup) {
+                        issue_from(cur.item, cur.rating, cur.n, u, u % D);
+                        ps[u % D] = load_wrapped<J>(a.P + static_cast<size_t>(__shfl(cur.x, u, kGroup)) * a.ldp, sl);
+                    }
+                    // the next chunk's scalars and draw ride along (a chunk past the last one: clamped, unused)
+                    if (u == 1) chunk_bounds(ch + 1, nxt);
+                    if (u == kGroup / 2) chunk_draw(it_now, nxt);
+                    __builtin_amdgcn_sched_barrier(0);
                 }
+                // the users' biases go back (a lane without a user, or a user without ratings: its own old value, or nothing)
+                if (cur.n > 0) a.user_bias[cur.x] = cur.ub;
+                cur = nxt;
             }
         }
         if (k + 1 == a.iters) break;
@@ -415,18 +403,18 @@ const Variant kVariants[] = {
     CU2REC_RES_VARIANT(1, 20, 4),  CU2REC_RES_VARIANT(1, 24, 4),  CU2REC_RES_VARIANT(1, 28, 4),  CU2REC_RES_VARIANT(1, 32, 4),
     CU2REC_RES_VARIANT_LDS(1, 36, 4, 8), CU2REC_RES_VARIANT_LDS(1, 40, 4, 12), CU2REC_RES_VARIANT_LDS(1, 44, 4, 16),
     CU2REC_RES_VARIANT_LDS(1, 47, 4, 19),
-    CU2REC_RES_VARIANT(2, 4, CU2REC_RES_D2),  CU2REC_RES_VARIANT(2, 6, CU2REC_RES_D2),  CU2REC_RES_VARIANT(2, 8, CU2REC_RES_D2),
-    CU2REC_RES_VARIANT(2, 10, CU2REC_RES_D2), CU2REC_RES_VARIANT(2, 12, CU2REC_RES_D2), CU2REC_RES_VARIANT(2, 14, CU2REC_RES_D2),
-    CU2REC_RES_VARIANT(2, 16, CU2REC_RES_D2), CU2REC_RES_VARIANT(2, 17, CU2REC_RES_D2), CU2REC_RES_VARIANT(2, 18, CU2REC_RES_D2),
-    CU2REC_RES_VARIANT_LDS(2, 20, CU2REC_RES_D2, 4), CU2REC_RES_VARIANT_LDS(2, 22, CU2REC_RES_D2, 6),
-    CU2REC_RES_VARIANT_LDS(2, 24, CU2REC_RES_D2, 8), CU2REC_RES_VARIANT_LDS(2, 25, CU2REC_RES_D2, 9),
+    CU2REC_RES_VARIANT(2, 4, kResD2),  CU2REC_RES_VARIANT(2, 6, kResD2),  CU2REC_RES_VARIANT(2, 8, kResD2),
+    CU2REC_RES_VARIANT(2, 10, kResD2), CU2REC_RES_VARIANT(2, 12, kResD2), CU2REC_RES_VARIANT(2, 14, kResD2),
+    CU2REC_RES_VARIANT(2, 16, kResD2), CU2REC_RES_VARIANT(2, 17, kResD2), CU2REC_RES_VARIANT(2, 18, kResD2),
+    CU2REC_RES_VARIANT_LDS(2, 20, kResD2, 4), CU2REC_RES_VARIANT_LDS(2, 22, kResD2, 6),
+    CU2REC_RES_VARIANT_LDS(2, 24, kResD2, 8), CU2REC_RES_VARIANT_LDS(2, 25, kResD2, 9),
     CU2REC_RES_VARIANT(3, 4, 3),   CU2REC_RES_VARIANT(3, 6, 3),   CU2REC_RES_VARIANT(3, 8, 3),
     CU2REC_RES_VARIANT_LDS(3, 10, 3, 2), CU2REC_RES_VARIANT_LDS(3, 12, 3, 4), CU2REC_RES_VARIANT_LDS(3, 14, 3, 6),
     CU2REC_RES_VARIANT(4, 4, 2),   CU2REC_RES_VARIANT(4, 6, 2),
     CU2REC_RES_VARIANT_LDS(4, 8, 2, 2), CU2REC_RES_VARIANT_LDS(4, 10, 2, 4),
     // partial residency: one form per row width (a few register rows fewer than the largest resident form: the streamed rows'
     // pipeline and a chunk's scalars live in them)
-    CU2REC_RES_VARIANT_PART(1, 39, 4, 19), CU2REC_RES_VARIANT_PART(2, 20, CU2REC_RES_D2, 9), CU2REC_RES_VARIANT_PART(3, 11, 3, 6),
+    CU2REC_RES_VARIANT_PART(1, 39, 4, 19), CU2REC_RES_VARIANT_PART(2, 20, kResD2, 9), CU2REC_RES_VARIANT_PART(3, 11, 3, 6),
     CU2REC_RES_VARIANT_PART(4, 8, 2, 4),
 };
 #undef CU2REC_RES_VARIANT

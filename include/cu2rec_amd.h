@@ -312,11 +312,6 @@ int cu2rec_blocksolve_lookahead_blocks(int blocks);
 /* The fork / join form in force on the current device (see cu2rec_sgd_update_blocksolve): 2 device-side gate and join, 0 events,
  * -1 not decided yet (no block-solve call so far).  `why` (may be NULL): the reason, NUL-terminated, truncated to `cap` bytes. */
 int cu2rec_blocksolve_topology(char *why, size_t cap);
-/* Development aid: while `buffer` (device memory, 8 * (1 + 8 * capacity) bytes, zeroed by the caller) is set, every
- * wavefront of the block-solve kernels writes {kernel, id, start, end, 4 marks (trace builds)} in ticks of the 100 MHz device clock into record
- * kernel * (capacity / 8) + id (kernel: 1 gram, 2 solver, 3 loader, 4 update, 7 cross blocks; records never written stay
- * zero).  NULL switches it off. */
-int cu2rec_debug_blocksolve_stamps(void *buffer, int capacity);
 
 /* Replaces calculate_loss_gpu + get_error_metrics_gpu (loss.cu:19-49,150-200) in ONE pass:
  * residual e = r - (gb + ub + ib + p.q) per rating, sum |e| and sum e^2 accumulated in

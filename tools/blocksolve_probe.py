@@ -21,7 +21,6 @@ def main():
     ap.add_argument("--rate", type=float, default=0.0)
     ap.add_argument("--skip-small", action="store_true")
     ap.add_argument("--skip-big", action="store_true")
-    ap.add_argument("--stamps", action="store_true", help="wavefront timelines of one block-solve iteration")
     args = ap.parse_args()
     import cu2rec_amd as cu
     from cu2rec_amd import api, synth
@@ -51,66 +50,6 @@ def main():
     users = int(np.count_nonzero(np.diff(tr.indptr)))
     f = args.factors
     d_tr, d_te = cu.DeviceCSR(tr), cu.DeviceCSR(te)
-    if args.stamps:
-        import torch
-        from cu2rec_amd._lib import check, lib
-        cap = 1 << 18
-        buf = torch.zeros(1 + 8 * cap, dtype=torch.int64, device="cuda")
-        model = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
-        model.sgd(d_tr, hyper, 42, 0, 66, mode="blocksolve")
-        torch.cuda.synchronize()
-        check(lib().cu2rec_debug_blocksolve_stamps(buf.data_ptr(), cap))
-        model.sgd(d_tr, hyper, 42, 66, 1, mode="blocksolve")
-        torch.cuda.synchronize()
-        check(lib().cu2rec_debug_blocksolve_stamps(None, 0))
-        h = buf.cpu().numpy()
-        rec = h[1:1 + 8 * cap].reshape(cap, 8)
-        rec = rec[rec[:, 0] > 0]
-        xcc = rec[:, 0] >> 32
-        rec[:, 0] &= 0xffffffff
-        for kid, nm in ((2, "solver"), (6, "build")):
-            sel = rec[:, 0] == kid
-            print("xcc of", nm, "records (id -> xcc):", [(int(i), int(x)) for i, x in zip(rec[sel, 1][:24], xcc[sel][:24])])
-        n = len(rec)
-        t_min = rec[:, 2].min()
-        names = {1: "gram", 2: "solver", 3: "loader", 4: "update", 5: "walk", 6: "build", 7: "cross"}
-        print("stamps: %d wavefront records; times in us from the first start" % n)
-        for kid in sorted(names):
-            r = rec[rec[:, 0] == kid]
-            if not len(r):
-                continue
-            st, en = (r[:, 2] - t_min) / 100.0, (r[:, 3] - t_min) / 100.0
-            dur = en - st
-            print("%-7s waves %6d  start %7.2f..%7.2f  end %7.2f..%7.2f  dur mean %6.2f p50 %6.2f p90 %6.2f max %6.2f" %
-                  (names[kid], len(r), st.min(), st.max(), en.min(), en.max(), dur.mean(), np.percentile(dur, 50),
-                   np.percentile(dur, 90), dur.max()))
-            if r[:, 4:].any():
-                rr = r[(r[:, 4:] > 0).all(axis=1)]
-                mk = (rr[:, 4:] - rr[:, 2:3]) / 100.0
-                print("   marks after start (mean us over %d waves):" % len(rr), [round(float(v), 2) for v in mk.mean(axis=0)])
-                if kid in (2, 3):
-                    for row in list(rr[:8]) + list(rr[-4:]):
-                        print("     chain %d wave %d:" % (row[1] // 4, row[1] % 4), [round(float(v - row[2]) / 100.0, 2) for v in row[4:]], "end", round(float(row[3] - row[2]) / 100.0, 2))
-            if kid in (3, 4) and not os.environ.get("CU2REC_PROBE_FINE"):
-                cyc = (r[:, 7] - r[:, 2]).astype(np.float64)
-                tick = (r[:, 3] - r[:, 2]).astype(np.float64)
-                ok = tick > 0
-                ghz = cyc[ok] / (tick[ok] * 10.0)
-                print("   shader clock over the wavefront's life: mean %.3f GHz (p10 %.3f, p90 %.3f)" % (ghz.mean(), np.percentile(ghz, 10), np.percentile(ghz, 90)))
-            if kid in (1, 4) and os.environ.get("CU2REC_PROBE_FINE") and r[:, 4:].any():
-                rr = r[(r[:, 4:] > 0).all(axis=1)]
-                mk = (rr[:, 4:] - rr[:, 2:3]) / 100.0
-                d = (rr[:, 3] - rr[:, 2]) / 100.0
-                for q in (50, 90, 100):
-                    print("   fine marks p%d:" % q, [round(float(v), 2) for v in np.percentile(mk, q, axis=0)], "end", round(float(np.percentile(d, q)), 2))
-            if kid == 1:
-                order = np.argsort(-en)[:6]
-                for i in order:
-                    print("     last gram waves: id %d start %.2f end %.2f marks" % (r[i, 1], st[i], en[i]), [round(float(v - r[i, 2]) / 100.0, 2) for v in r[i, 4:]])
-            if kid == 2:
-                order = np.argsort(-dur)[:8]
-                print("   longest solver waves (chain, start, end):", [(int(r[i, 1]) // 4, round(float(st[i]), 2), round(float(en[i]), 2)) for i in order])
-        return
     res = {}
     for mode in ("blocksolve", "ordered"):
         model = cu.Model(tr.rows, tr.cols, f, tr.global_bias)

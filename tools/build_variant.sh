@@ -1,5 +1,6 @@
 #!/bin/bash
-# Timing-only builds of the library with ablation / tuning macros (never shipped, never loaded by default):
+# Another build of the library from the same sources, with extra compiler flags (never shipped, never loaded by default) -- e.g.
+# the cooperative-launch refusal check of tools/resident_refusal_check.py (-DCU2REC_RES_TEST_OVERSUBSCRIBE=2):
 #   tools/build_variant.sh <name> "<extra hipcc flags>"   ->  build/variants/<name>/libcu2rec_amd.so
 # Load one with CU2REC_AMD_LIB=build/variants/<name>/libcu2rec_amd.so (cu2rec_amd/_lib.py).
 set -euo pipefail

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
 """Microseconds per Hogwild iteration of the resident launch vs the streaming launches, same data (GPU box).
-  python tools/resident_probe.py [--workload ml-20m --factors 100 --iters 115 --reps 6]
-With CU2REC_AMD_LIB pointing at a tools/build_variant.sh build this times ablations."""
+  python tools/resident_probe.py [--workload ml-20m --factors 100 --iters 115 --reps 6]"""
 import argparse
 import os
 import sys
