@@ -286,6 +286,35 @@ def test_bench_times_exactly_k_steps_and_dumps_the_model_they_leave(tmp_path):
         np.testing.assert_array_equal(got, want, err_msg=name)
 
 
+def test_bench_side_legs_run_with_full_only(tmp_path):
+    """A plain `bench.py` run prints the headline without the side legs; `--full` adds them and the CPU baselines to the same line,
+    with the same headline model (ML-1M shape, f=50: the timed mode IS the ordered walk, so its gap to the sequential result is 0;
+    100 iterations, past the side legs' own warm-up of 64)."""
+    import json
+    import subprocess
+    import sys
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    lines = {}
+    for extra in ((), ("--full",)):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "50",
+                              "--workload", "ml-1m", "--factors", "50", *extra], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                             text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines[extra] = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines[()], lines[("--full",)]
+    legs = ("rmse_gap_vs_sequential", "ordered_mode", "hogwild_streaming_mode", "tier2_converged", "loss_kernel", "cpu_baseline")
+    assert not [k for k in legs if k in plain], plain.keys()
+    assert all(k in full for k in legs), full.keys()
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "timed_steps", "iterations_run", "test_rmse"):
+        assert plain[k] == full[k], k
+    assert full["rmse_gap_vs_sequential"]["gap"] == 0.0 and full["rmse_gap_vs_sequential"]["iterations"] == 100
+    assert full["ordered_mode"]["value"] > 0 and full["hogwild_streaming_mode"]["value"] > 0 and full["loss_kernel"]["ms"] > 0
+    assert set(full["tier2_converged"]["modes"]) >= {"blocksolve", "hogwild-streaming"}
+    assert full["cpu_baseline"]["value"] > 0
+
+
 @pytest.mark.parametrize("policy,name", [(2, "resident"), (0, "streaming")])
 def test_hogwild_mid_trajectory_gap_to_sequential_stays_bounded_at_full_shape(policy, name):
     """A regression bound on the racy modes while the model is still moving (popular items lose most of their updates to the

@@ -1,5 +1,6 @@
 """Host-side logic of the measurement tools (no GPU): the schedule replay of tools/tier2_converged.py against the reference's rule
 (training.cu:129,146-155: patience consumed when the test RMSE got worse, never restored; decay and reset at zero)."""
+import hashlib
 import os
 import sys
 
@@ -124,3 +125,33 @@ def test_bench_dump_outputs_keeps_the_budget_with_a_fixed_row_sample(tmp_path, m
         assert np.array_equal(a[n], b[n]) and not np.array_equal(a[n], c[n]), n
         rows = [int(np.flatnonzero((full == r).all(axis=1))[0]) for r in a[n]]
         assert rows == sorted(set(rows)), n  # rows of the full matrix, each once, in order
+
+
+# sha256 of synth.make_named("ml-20m", seed=20240917) as _sets_digest takes it: the benchmark's inputs
+ML20M_SETS_SHA256 = "89e312be9e45986625533cfbec839aa54eb59079c18a648f9fb34c1a5ec4343b"
+
+
+def _sets_digest(pair):
+    h = hashlib.sha256()
+    for m in pair:
+        for a in (m.indptr, m.indices, m.data, np.array([m.rows, m.cols], np.int64), np.array([m.global_bias], np.float64)):
+            h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def test_bench_generates_synths_sets_bit_for_bit():
+    """bench.py generates its set in-process, split over threads by user range: the same train / test CSR as synth.make_ratings
+    whatever the thread count -- few users (one piece), few items (Zipf draws collide: top-up rounds), integer ratings (the Netflix shape),
+    min_degree 1 -- and, pinned by digest, the benchmark's own ML-20M set (taken from synth.make_named('ml-20m'))."""
+    import bench
+    from cu2rec_amd import synth
+    shapes = [(50, 40, 900, 3, 1, False), (943, 1682, 100_000, 20, 20240917, False), (1000, 17, 12_000, 1, 7, True),
+              (3000, 500, 60_000, 1, 11, True), (6040, 3706, 1_000_209, 20, 20240917, False)]
+    for users, items, nnz, min_degree, seed, integer in shapes:
+        want = _sets_digest(synth.make_ratings(users, items, nnz, min_degree=min_degree, seed=seed, integer_ratings=integer))
+        for threads in (1, 3, 16):
+            got = bench.make_ratings(users, items, nnz, min_degree, seed, integer, threads)
+            assert _sets_digest(got) == want, (users, items, nnz, threads)
+    assert _sets_digest(bench.make_dataset("ml-1m", 20240917, 4)) == _sets_digest(synth.make_named("ml-1m", seed=20240917))
+    assert _sets_digest(bench.make_dataset("ml-20m", 20240917, bench.host_threads())) == ML20M_SETS_SHA256
+
