@@ -13,12 +13,24 @@ import numpy as np
 from ._lib import Config, Cu2recError, Hyper, RankMetrics, TrainStats, check, lib
 
 SGD_HOGWILD, SGD_SERIAL, SGD_ORDERED, SGD_PINGPONG, SGD_BLOCKSOLVE = 0, 1, 2, 3, 4
+SIDE_USERS, SIDE_ITEMS = 0, 1
+SIM_DOT, SIM_COSINE = 0, 1
+SIDES = {"users": SIDE_USERS, "items": SIDE_ITEMS}
+METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE}
 MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "pingpong": SGD_PINGPONG,
          "blocksolve": SGD_BLOCKSOLVE}
 
 
 def _mode(mode):
     return MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def _choice(table, value, what):
+    if not isinstance(value, str):
+        return int(value)
+    if value not in table:
+        raise ValueError("%s must be one of %s, not %r" % (what, sorted(table), value))
+    return table[value]
 
 
 def _ptr(a):
@@ -94,6 +106,15 @@ class HostCSR:
         check(lib().cu2rec_csr_slice(_ptr(self.indptr), self.rows, u0, u1, _ptr(out), C.byref(off), C.byref(nnz)))
         return HostCSR(out, self.indices[off.value:off.value + nnz.value], self.data[off.value:off.value + nnz.value],
                        u1 - u0, self.cols, self.global_bias)
+
+    def transpose(self):
+        """The column-major view as its own CSR: row i holds the rows that name column i (for a rating matrix, the users of
+        item i -- Model.top_users' exclusion), in ascending row order, repeats kept, data carried along."""
+        rows_of = np.repeat(np.arange(self.rows, dtype=np.int32), np.diff(self.indptr))
+        order = np.argsort(self.indices, kind="stable")
+        indptr = np.zeros(self.cols + 1, np.int64)
+        np.cumsum(np.bincount(self.indices, minlength=self.cols), out=indptr[1:])
+        return HostCSR(indptr, rows_of[order], self.data[order], self.cols, self.rows, self.global_bias)
 
 
 def readCSV(path):
@@ -292,6 +313,31 @@ class Model:
         check(lib().cu2rec_model_topk(self._h, exclude._h if exclude is not None else None, _ptr(ids), int(n), int(k),
                                       _ptr(items), _ptr(scores)))
         return items, scores
+
+    def similar(self, ids=None, k=10, side="items", metric="cosine", exclude=None):
+        """Nearest neighbours among the rows of one factor matrix (cu2rec_model_similar) -> (ids, scores), each (n, k).
+        side: "items" (rows of Q) or "users" (rows of P); metric: "cosine" or "dot" (no biases).  ids: rows of that side
+        (duplicates allowed), or None for every row; a query row is never its own neighbour.  exclude: DeviceCSR whose row a
+        holds the rows excluded for row a, or None.  Order, ties and -1 / NaN padding are topk's.  1 <= k <= 256."""
+        side, metric = _choice(SIDES, side, "side"), _choice(METRICS, metric, "metric")
+        q = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n = (self.rows if side == SIDE_USERS else self.cols) if q is None else len(q)
+        out, scores = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_model_similar(self._h, side, metric, exclude._h if exclude is not None else None, _ptr(q), int(n),
+                                         int(k), _ptr(out), _ptr(scores)))
+        return out, scores
+
+    def top_users(self, exclude, k, items=None):
+        """The k users with the best predicted rating for each item (cu2rec_model_top_users) -> (users, scores), each (n, k):
+        the floats of scores()[:, i], in topk's order (equal scores by ascending user; -inf never listed; -1 / NaN padding).
+        exclude: DeviceCSR whose row i holds item i's excluded users (e.g. DeviceCSR(train.transpose())), or None.  items:
+        item ids (duplicates allowed), or None for every item.  1 <= k <= 256."""
+        ids = None if items is None else np.ascontiguousarray(items, dtype=np.int32).reshape(-1)
+        n = self.cols if ids is None else len(ids)
+        users, scores = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_model_top_users(self._h, exclude._h if exclude is not None else None, _ptr(ids), int(n), int(k),
+                                           _ptr(users), _ptr(scores)))
+        return users, scores
 
     def rank_metrics(self, test, k, exclude=None, threshold=None, per_user=False):
         """Ranking quality at k of the top-k lists (topk over every row, excluding `exclude`) against `test`

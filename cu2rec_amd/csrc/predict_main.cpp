@@ -13,10 +13,16 @@
 // fitted in one batch (frozen items: no update crosses users, so every fit equals the one-user result), scored with one
 // dense product on the matrix cores and ranked by one segmented sort on the device (cu2rec_model_scores /
 // cu2rec_model_recommend); output is one block per user, headed "User: <id>".  -k K limits the recommendations listed.
+//
+//   bin/predict -c config -q q.csv -S [-k K] item_ids.txt
+//
+// -S fits no user: for each 0-based item index of the file (one per line, the numbers the "Item:" lines print) it lists the
+// K (default 10) items whose rows of Q are nearest by cosine (cu2rec_model_similar), the item itself never among them.
 #include <getopt.h>
 
 #include <algorithm>
 #include <cstdio>
+#include <fstream>
 #include <iostream>
 #include <string>
 #include <utility>
@@ -35,18 +41,74 @@ struct FloatTable {
     ~FloatTable() { cu2rec_free(data); }
 };
 
+// -S: one 0-based item index per line (blank lines skipped)
+std::vector<int> read_ids(const std::string &path) {
+    std::ifstream in(path);
+    if (!in) throw std::runtime_error("cannot open " + path);
+    std::vector<int> ids;
+    std::string line;
+    for (int no = 1; std::getline(in, line); ++no) {
+        const size_t b = line.find_first_not_of(" \t\r"), e = line.find_last_not_of(" \t\r");
+        if (b == std::string::npos) continue;
+        const std::string t = line.substr(b, e - b + 1);
+        size_t used = 0;
+        long v = -1;
+        try {
+            v = std::stol(t, &used);
+        } catch (const std::exception &) {
+            used = 0;
+        }
+        if (used != t.size() || v < 0 || v > 0x7FFFFFFF) throw std::runtime_error(path + ":" + std::to_string(no) + ": not an item index: " + t);
+        ids.push_back(static_cast<int>(v));
+    }
+    return ids;
+}
+
+// the cosine-nearest items of each listed item, from Q alone
+int similar_items(const cu2rec_config &cfg, const std::string &q_path, const std::string &ids_path, int k) {
+    const FloatTable Q(q_path);
+    const int n_items = Q.rows, f = cfg.n_factors;
+    if (n_items <= 0 || Q.cols != f) throw std::runtime_error("q file does not have n_factors columns");
+    const std::vector<int> ids = read_ids(ids_path);
+    for (int id : ids)
+        if (id >= n_items) throw std::runtime_error("item index " + std::to_string(id) + " is not below the model's " + std::to_string(n_items) + " items");
+    const std::vector<float> p(f, 0.f), ub(1, 0.f), ib(n_items, 0.f);  // no user is fitted; biases do not enter cosine
+    cu2rec::ModelHandle model(1, n_items, f, 0.f, p.data(), Q.data, ub.data(), ib.data());
+    const int n = static_cast<int>(ids.size());
+    std::vector<int> near(static_cast<size_t>(n) * k);
+    std::vector<float> cosine(static_cast<size_t>(n) * k);
+    if (n > 0)
+        cu2rec::check(cu2rec_model_similar(model.h, CU2REC_SIDE_ITEMS, CU2REC_SIM_COSINE, nullptr, ids.data(), n, k, near.data(),
+                                           cosine.data()));
+    for (int q = 0; q < n; ++q) {
+        std::cout << "Item: " << ids[q] << "\n" << "Similar items:" << "\n";
+        for (int j = 0; j < k; ++j) {
+            const int item = near[static_cast<size_t>(q) * k + j];
+            if (item < 0) break;
+            std::printf("Rank: %d\tItem: %d\tCosine similarity: %f\n", j + 1, item, cosine[static_cast<size_t>(q) * k + j]);
+        }
+        std::fflush(stdout);
+    }
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
     if (argc < 2) return 2;  // predict.cu:73-75
     std::string config_path, item_bias_path, global_bias_path, q_path;
-    bool many_users = false;
+    bool many_users = false, similar = false;
     int top_k = 0;  // 0: every unrated item, as the reference prints
+    const char *k_arg = nullptr;
     int opt;
-    while ((opt = getopt(argc, argv, "c:i:g:q:uk:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:i:g:q:uk:S")) != -1) {
         switch (opt) {
             case 'u': many_users = true; break;
-            case 'k': top_k = std::max(0, std::atoi(optarg)); break;
+            case 'S': similar = true; break;
+            case 'k':
+                top_k = std::max(0, std::atoi(optarg));
+                k_arg = optarg;
+                break;
             case 'c': config_path = optarg; break;
             case 'i': item_bias_path = optarg; break;
             case 'g': global_bias_path = optarg; break;
@@ -54,6 +116,25 @@ int main(int argc, char **argv) {
             default:
                 std::cout << "Unknown option.\n";  // predict.cu:96-98
                 return 1;
+        }
+    }
+    if (similar) {
+        const char *usage = "usage: predict -c config -q q.csv -S [-k K] item_ids.txt   (1 <= K <= 256; -S fits no user: no -u)\n";
+        char *end = nullptr;
+        const long k = k_arg ? std::strtol(k_arg, &end, 10) : 10;
+        if (optind + 1 != argc || config_path.empty() || q_path.empty() || many_users || (k_arg && (*end || end == k_arg)) || k < 1 ||
+            k > 256) {
+            std::cerr << usage;
+            return 2;
+        }
+        try {
+            cu2rec_config cfg;
+            cu2rec::check(cu2rec_config_default(&cfg));
+            cu2rec::check(cu2rec_config_read(config_path.c_str(), &cfg));
+            return similar_items(cfg, q_path, argv[optind], static_cast<int>(k));
+        } catch (const std::exception &e) {
+            std::cerr << "predict: " << e.what() << "\n";
+            return 3;
         }
     }
     if (optind >= argc || config_path.empty() || item_bias_path.empty() || global_bias_path.empty() || q_path.empty()) {

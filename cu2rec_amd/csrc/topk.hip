@@ -19,6 +19,9 @@
 //
 // Ranking metrics run the same selection over the model's rows, then one thread per user checks its list against a
 // relevance bitmap of the test row and reduces in double (one final block-wide sum; one host synchronisation per call).
+//
+// The neighbour queries (cu2rec_model_similar, cu2rec_model_top_users) are the same kernel over other query and candidate
+// matrices (TopkKind below): "user" and "item" in the comments here stand for query and candidate.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -101,21 +104,32 @@ __device__ __forceinline__ void load_sorted(unsigned long long (&v)[E], const un
     wave_sort_desc<E>(v, lane);
 }
 
-// One workgroup = 32 listed users (positions pos0 .. pos0 + 31 of `users`, model row ids) against every item.  LDS: the user
-// tile and four item tiles of scores_kernel, then the 32 thresholds and counts.  cand: [n_pos][64 E] keys of workspace.
-template <int E>
-__global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ P, int ldp, const float *__restrict__ user_bias,
-                                                   const int *__restrict__ users, int n_pos, const float *__restrict__ Q, int ldq,
-                                                   const float *__restrict__ item_bias, int n_items, float global_bias, int nslots,
+// What a selection ranks (include/cu2rec_amd.h): the query rows X and the candidate rows Y of the score tile, and the score
+//   kUserItems   X = P, Y = Q                  ((gb + ub[query]) + ib[cand]) + x . y            cu2rec_model_topk
+//   kSimilarDot  X = Y = P or Q                x . y, the query row itself not a candidate       cu2rec_model_similar, DOT
+//   kSimilarCos  X = Y = P or Q                (x . y * inv_norm[query]) * inv_norm[cand], ditto  cu2rec_model_similar, COSINE
+//   kItemUsers   X = Q, Y = P                  ((gb + ub[cand]) + ib[query]) + y . x            cu2rec_model_top_users
+// kItemUsers keeps P in the MFMA A operand as scores_kernel does (the candidate tile is A): the accumulator's rows are then
+// candidates and its columns queries, so a lane owns one query and 16 candidates -- the same floats as cu2rec_model_scores.
+enum TopkKind { kUserItems = 0, kSimilarDot = 1, kSimilarCos = 2, kItemUsers = 3 };
+
+// One workgroup = 32 listed queries (positions pos0 .. pos0 + 31 of `qids`, rows of X) against every row of Y.  LDS: the query
+// tile and four candidate tiles of scores_kernel, then the 32 thresholds and counts.  cand: [n_pos][64 E] keys of workspace.
+// qbias / cbias: per-row values of the score (biases, or inverse norms for kSimilarCos; unused by kSimilarDot).
+template <int E, int Kind>
+__global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ X, int ldx, const float *__restrict__ qbias,
+                                                   const int *__restrict__ qids, int n_pos, const float *__restrict__ Y, int ldy,
+                                                   const float *__restrict__ cbias, int n_cand, float global_bias, int nslots,
                                                    int chunk, const unsigned *__restrict__ mask, int words, int k,
                                                    unsigned long long *__restrict__ cand, int *__restrict__ items_out,
                                                    float *__restrict__ scores_out) {
     constexpr int S = 64 * E;
+    constexpr bool self = Kind == kSimilarDot || Kind == kSimilarCos;
     extern __shared__ float4 smem[];
     const int RS = chunk | 1;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pos0 = blockIdx.x * kTile;
-    float4 *utile = smem, *itile = smem + (1 + wave) * kTile * RS;
+    float4 *qtile = smem, *ctile = smem + (1 + wave) * kTile * RS;
     unsigned long long *thr = reinterpret_cast<unsigned long long *>(smem + 5 * kTile * RS);
     int *cnt = reinterpret_cast<int *>(thr + kTile);
     const int r = lane & 31, h = lane >> 5;
@@ -123,49 +137,82 @@ __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ P, 
         thr[threadIdx.x] = 0ull;
         cnt[threadIdx.x] = 0;
     }
-    float ub[16];
+    float qb[16];  // the bias (inverse norm) of the query of each accumulator row
+    int qid[16];   // and its row id, for the self-exclusion
+    float lane_qb = 0.f;  // kItemUsers: the bias of this lane's query (accumulator column r)
+    if constexpr (Kind == kItemUsers) {
+        lane_qb = pos0 + r < n_pos ? qbias[qids[pos0 + r]] : 0.f;
+    } else {
 #pragma unroll
-    for (int reg = 0; reg < 16; ++reg) {
-        const int pos = pos0 + acc_row(reg, h);
-        ub[reg] = pos < n_pos ? user_bias[users[pos]] : 0.f;
+        for (int reg = 0; reg < 16; ++reg) {
+            const int pos = pos0 + acc_row(reg, h);
+            if constexpr (Kind != kSimilarDot) qb[reg] = pos < n_pos ? qbias[qids[pos]] : 0.f;
+            if constexpr (self) qid[reg] = pos < n_pos ? qids[pos] : -1;
+        }
     }
-    // wave w stages rows 8 w .. 8 w + 7 of the user tile: the row of this lane, gathered from P (clamped, zero past n_pos)
+    // wave w stages rows 8 w .. 8 w + 7 of the query tile: the row of this lane, gathered from X (clamped, zero past n_pos)
     const int srow = 8 * wave + (lane >> 3), cs = lane & 7;
-    const float4 *prow = reinterpret_cast<const float4 *>(P + static_cast<size_t>(users[min(pos0 + srow, n_pos - 1)]) * ldp);
-    const bool whole = chunk >= nslots;  // the user tile is staged once and stays
-    for (int item_base = 0; item_base < n_items; item_base += kStep) {
-        const int item0 = item_base + wave * kTile;
-        const bool active = item0 < n_items;
+    const float4 *xrow = reinterpret_cast<const float4 *>(X + static_cast<size_t>(qids[min(pos0 + srow, n_pos - 1)]) * ldx);
+    const bool whole = chunk >= nslots;  // the query tile is staged once and stays
+    for (int cand_base = 0; cand_base < n_cand; cand_base += kStep) {
+        const int cand0 = cand_base + wave * kTile;
+        const bool active = cand0 < n_cand;
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
         for (int slot0 = 0; slot0 < nslots; slot0 += chunk) {
             const int n = min(chunk, nslots - slot0);
             __syncthreads();  // every wave is done reading the tiles (previous chunk or step)
-            if (!whole || item_base == 0) {
+            if (!whole || cand_base == 0) {
                 for (int c = 0; c < (n + 7) >> 3; ++c) {
                     const int slot = 8 * c + cs;
-                    const float4 v = prow[slot0 + min(slot, n - 1)];
-                    if (slot < n) utile[srow * RS + slot] = pos0 + srow < n_pos ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+                    const float4 v = xrow[slot0 + min(slot, n - 1)];
+                    if (slot < n) qtile[srow * RS + slot] = pos0 + srow < n_pos ? v : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
             }
-            if (active) stage_rows(itile, Q, ldq, item0, n_items, slot0, n, RS, lane);
+            if (active) stage_rows(ctile, Y, ldy, cand0, n_cand, slot0, n, RS, lane);
             __syncthreads();
-            if (active) contract(acc, utile, itile, RS, n, r, h);
+            if constexpr (Kind == kItemUsers) {
+                if (active) contract(acc, ctile, qtile, RS, n, r, h);  // A: users (P), B: items (Q), as scores_kernel
+            } else {
+                if (active) contract(acc, qtile, ctile, RS, n, r, h);
+            }
         }
-        const int item = item0 + r;  // accumulator column = lane & 31
-        if (active && item < n_items) {
-            const float ibv = item_bias[item];
+        if constexpr (Kind == kItemUsers) {
+            const int pos = pos0 + r;  // accumulator column = lane & 31 = query; rows = candidates cand0 + acc_row
+            if (active && pos < n_pos) {
+                const unsigned word = mask ? mask[static_cast<size_t>(pos) * words + (cand0 >> 5)] : 0u;  // cand0 % 32 == 0
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) {
-                const int row = acc_row(reg, h), pos = pos0 + row;
-                if (pos >= n_pos) continue;
-                const float s = ((global_bias + ub[reg]) + ibv) + acc[reg];  // scores_kernel's expression
-                const bool masked = mask && ((mask[static_cast<size_t>(pos) * words + (item >> 5)] >> (item & 31)) & 1u);
-                const unsigned long long key = topk_key(s, item);
-                if (!masked && static_cast<unsigned>(key >> 32) > kEncNegInf && key > thr[row]) {
-                    const int at = atomicAdd(&cnt[row], 1);
-                    cand[static_cast<size_t>(pos) * S + at] = key;
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int row = acc_row(reg, h), c = cand0 + row;
+                    if (c >= n_cand) continue;
+                    const float s = ((global_bias + cbias[c]) + lane_qb) + acc[reg];  // scores_kernel's expression
+                    const unsigned long long key = topk_key(s, c);
+                    if (!((word >> row) & 1u) && static_cast<unsigned>(key >> 32) > kEncNegInf && key > thr[r]) {
+                        const int at = atomicAdd(&cnt[r], 1);
+                        cand[static_cast<size_t>(pos) * S + at] = key;
+                    }
+                }
+            }
+        } else {
+            const int item = cand0 + r;  // accumulator column = lane & 31
+            if (active && item < n_cand) {
+                const float ibv = Kind == kSimilarDot ? 0.f : cbias[item];
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int row = acc_row(reg, h), pos = pos0 + row;
+                    if (pos >= n_pos) continue;
+                    float s;
+                    if constexpr (Kind == kUserItems) s = ((global_bias + qb[reg]) + ibv) + acc[reg];  // scores_kernel's expression
+                    else if constexpr (Kind == kSimilarDot) s = acc[reg];
+                    else s = (acc[reg] * qb[reg]) * ibv;
+                    bool masked = mask && ((mask[static_cast<size_t>(pos) * words + (item >> 5)] >> (item & 31)) & 1u);
+                    if constexpr (self) masked = masked || item == qid[reg];
+                    const unsigned long long key = topk_key(s, item);
+                    if (!masked && static_cast<unsigned>(key >> 32) > kEncNegInf && key > thr[row]) {
+                        const int at = atomicAdd(&cnt[row], 1);
+                        cand[static_cast<size_t>(pos) * S + at] = key;
+                    }
                 }
             }
         }
@@ -200,6 +247,21 @@ __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ P, 
             items_out[static_cast<size_t>(pos) * k + j] = it;
             scores_out[static_cast<size_t>(pos) * k + j] = sc;
         }
+    }
+}
+
+// inv_norm[row] = 1 / |x_row| of rows 0 .. n - 1 of X (0 for a zero row: cosine 0 with everything), one wavefront per row;
+// squares summed in double, so that no row of finite floats overflows or underflows to a false zero
+__global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__ X, int ld, int n_factors, int n,
+                                                       float *__restrict__ inv_norm) {
+    const int lane = threadIdx.x & 63;
+    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += gridDim.x * 4) {
+        const float *x = X + static_cast<size_t>(row) * ld;
+        double s = 0.0;
+        for (int j = lane; j < n_factors; j += 64) s += static_cast<double>(x[j]) * static_cast<double>(x[j]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        if (lane == 0) inv_norm[row] = s > 0.0 ? static_cast<float>(1.0 / sqrt(s)) : 0.f;
     }
 }
 
@@ -303,20 +365,48 @@ void check_k(const char *who, int k) {
         fail(CU2REC_EUNSUPPORTED, std::string(who) + ": k above 256 is not supported here; cu2rec_model_recommend ranks any k");
 }
 
-void check_exclude(const DeviceModel &m, const DeviceCsr *exclude, const char *what) {
-    require(!exclude || (exclude->rows <= m.rows && exclude->max_item < m.cols), what);
+// exclusions of rows x cols: rows past the CSR's rows exclude nothing; every excluded id names a candidate
+void check_exclude(const DeviceCsr *exclude, int rows, int cols, const char *what) {
+    require(!exclude || (exclude->rows <= rows && exclude->max_item < cols), what);
 }
 
-// The selection for one list of users, in batches over a bounded workspace.  extra: further workspace bytes the caller
-// needs per listed user (rank metrics' relevance bitmap), counted in the batch size.
+// One selection: queries are rows of X (ids on the device), candidates rows 0 .. n_cand - 1 of Y; qbias / cbias as topk_kernel.
+struct TopkProblem {
+    int kind;
+    const float *X;
+    int ldx;
+    const float *qbias;
+    const float *Y;
+    int ldy;
+    const float *cbias;
+    int n_cand, n_factors;
+    float global_bias;
+};
+
+TopkProblem user_items(const DeviceModel &m) {
+    return {kUserItems, m.P.ptr, m.ld, m.user_bias.ptr, m.Q.ptr, m.ldq, m.item_bias.ptr, m.cols, m.n_factors, m.global_bias};
+}
+
+template <int E>
+const void *topk_kernel_ptr(int kind) {
+    switch (kind) {
+        case kUserItems: return reinterpret_cast<const void *>(topk_kernel<E, kUserItems>);
+        case kSimilarDot: return reinterpret_cast<const void *>(topk_kernel<E, kSimilarDot>);
+        case kSimilarCos: return reinterpret_cast<const void *>(topk_kernel<E, kSimilarCos>);
+        default: return reinterpret_cast<const void *>(topk_kernel<E, kItemUsers>);
+    }
+}
+
+// The selection for one list of queries, in batches over a bounded workspace.  extra: further workspace bytes the caller
+// needs per listed query (rank metrics' relevance bitmap), counted in the batch size.
 struct TopkRunner {
-    TopkRunner(const DeviceModel &m_, int k_, int n_total, bool masked, size_t extra) : m(m_), k(k_) {
+    TopkRunner(const TopkProblem &pb_, int k_, int n_total, bool masked, size_t extra) : pb(pb_), k(k_) {
         E = k + kStep <= 256 ? 4 : 8;
-        nslots = (m.n_factors + 3) / 4;
+        nslots = (pb.n_factors + 3) / 4;
         chunk = nslots <= 63 ? nslots : 32;  // scores_kernel's chunking: the same scores
         lds = static_cast<size_t>(5) * kTile * (chunk | 1) * sizeof(float4) + kTile * (sizeof(unsigned long long) + sizeof(int));
-        if (lds > kMaxLds) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_topk: the score tiles need more LDS than a workgroup has");
-        words = (m.cols + 31) / 32;
+        if (lds > kMaxLds) fail(CU2REC_EUNSUPPORTED, "top-k selection: the score tiles need more LDS than a workgroup has");
+        words = (pb.n_cand + 31) / 32;
         const size_t per_pos = static_cast<size_t>(64 * E) * 8 + (masked ? static_cast<size_t>(words) * 4 : 0) +
                                static_cast<size_t>(k) * 8 + extra;
         const size_t fit = std::max<size_t>(kTile, kWorkspaceBudget / per_pos / kTile * kTile);
@@ -326,28 +416,25 @@ struct TopkRunner {
         items.allocate(static_cast<size_t>(batch) * k);
         scores.allocate(static_cast<size_t>(batch) * k);
     }
-    // positions users_dev[0 .. n) (model rows) -> items / scores [n x k], device
-    void run(const DeviceCsr *exclude, const int *users_dev, int n, hipStream_t stream) {
+    // positions ids_dev[0 .. n) (rows of X) -> items / scores [n x k], device
+    void run(const DeviceCsr *exclude, const int *ids_dev, int n, hipStream_t stream) {
         if (mask.ptr) {
             CU2REC_HIP(hipMemsetAsync(mask.ptr, 0, static_cast<size_t>(n) * words * sizeof(unsigned), stream));
             if (exclude->nnz > 0)
                 hipLaunchKernelGGL(exclude_mask_kernel, dim3(std::min(n, 4096)), dim3(256), 0, stream, exclude->indptr.ptr,
-                                   exclude->indices.ptr, exclude->rows, users_dev, n, words, mask.ptr);
+                                   exclude->indices.ptr, exclude->rows, ids_dev, n, words, mask.ptr);
         }
-        const void *kernel = E == 4 ? reinterpret_cast<const void *>(topk_kernel<4>) : reinterpret_cast<const void *>(topk_kernel<8>);
+        const void *kernel = E == 4 ? topk_kernel_ptr<4>(pb.kind) : topk_kernel_ptr<8>(pb.kind);
         ensure_max_dynamic_lds(kernel, kMaxLds);
         const dim3 grid((n + kTile - 1) / kTile);
-        if (E == 4)
-            hipLaunchKernelGGL(topk_kernel<4>, grid, dim3(256), lds, stream, m.P.ptr, m.ld, m.user_bias.ptr, users_dev, n, m.Q.ptr,
-                               m.ldq, m.item_bias.ptr, m.cols, m.global_bias, nslots, chunk, mask.ptr, words, k, cand.ptr,
-                               items.ptr, scores.ptr);
-        else
-            hipLaunchKernelGGL(topk_kernel<8>, grid, dim3(256), lds, stream, m.P.ptr, m.ld, m.user_bias.ptr, users_dev, n, m.Q.ptr,
-                               m.ldq, m.item_bias.ptr, m.cols, m.global_bias, nslots, chunk, mask.ptr, words, k, cand.ptr,
-                               items.ptr, scores.ptr);
-        CU2REC_HIP(hipGetLastError());
+        const float *X = pb.X, *qbias = pb.qbias, *Y = pb.Y, *cbias = pb.cbias;
+        int ldx = pb.ldx, ldy = pb.ldy, n_cand = pb.n_cand;
+        float global_bias = pb.global_bias;
+        void *args[] = {&X, &ldx, &qbias, &ids_dev, &n, &Y, &ldy, &cbias, &n_cand, &global_bias, &nslots, &chunk, &mask.ptr, &words,
+                        &k, &cand.ptr, &items.ptr, &scores.ptr};  // topk_kernel's parameters, in order
+        CU2REC_HIP(hipLaunchKernel(kernel, grid, dim3(256), args, lds, stream));
     }
-    const DeviceModel &m;
+    const TopkProblem pb;
     int k, E, nslots, chunk, words, batch;
     size_t lds;
     DeviceBuffer<unsigned long long> cand;
@@ -356,30 +443,25 @@ struct TopkRunner {
     DeviceBuffer<float> scores;
 };
 
-}  // namespace
-
-// the k best non-excluded items of each listed user, best first (recommend's order and scores)
-void model_topk(const DeviceModel &m, const DeviceCsr *exclude, const int *users, int n_users, int k, int *items_out,
-                float *scores_out) {
-    check_k("cu2rec_model_topk: k must be at least 1", k);
-    require(items_out && scores_out, "cu2rec_model_topk: null output");
-    const int n = users ? n_users : m.rows;
-    require(n >= 0, "cu2rec_model_topk: negative n_users");
-    if (users)
-        for (int i = 0; i < n; ++i) require(users[i] >= 0 && users[i] < m.rows, "cu2rec_model_topk: user id out of range");
-    check_exclude(m, exclude, "cu2rec_model_topk: exclusions exceed the model's shape");
-    if (n == 0) return;
-    require(m.cols > 0, "cu2rec_model_topk: no items");
-    require_device();
-    hipStream_t stream = nullptr;
-    std::vector<int> ids(users ? users : nullptr, users ? users + n : nullptr);
-    if (!users) {
-        ids.resize(n);
-        for (int i = 0; i < n; ++i) ids[i] = i;
+// the ids of a query list: `ids` (validated against rows) or, when null, every row
+std::vector<int> query_ids(const int *ids, int n_ids, int rows, const char *who) {
+    const int n = ids ? n_ids : rows;
+    require(n >= 0, who);
+    std::vector<int> out(n);
+    for (int i = 0; i < n; ++i) {
+        out[i] = ids ? ids[i] : i;
+        require(out[i] >= 0 && out[i] < rows, who);
     }
+    return out;
+}
+
+// every listed query's k best candidates -> host items_out / scores_out [n x k], batch by batch
+void select_to_host(const TopkProblem &pb, const DeviceCsr *exclude, const std::vector<int> &ids, int k, int *items_out,
+                    float *scores_out, hipStream_t stream) {
+    const int n = static_cast<int>(ids.size());
     DeviceBuffer<int> d_ids(ids.size());
     d_ids.upload(ids.data(), ids.size());
-    TopkRunner run(m, k, n, exclude && exclude->nnz > 0, 0);
+    TopkRunner run(pb, k, n, exclude && exclude->nnz > 0, 0);
     for (int p0 = 0; p0 < n; p0 += run.batch) {
         const int b = std::min(run.batch, n - p0);
         run.run(exclude, d_ids.ptr + p0, b, stream);
@@ -391,13 +473,71 @@ void model_topk(const DeviceModel &m, const DeviceCsr *exclude, const int *users
     CU2REC_HIP(hipStreamSynchronize(stream));
 }
 
+}  // namespace
+
+// the k best non-excluded items of each listed user, best first (recommend's order and scores)
+void model_topk(const DeviceModel &m, const DeviceCsr *exclude, const int *users, int n_users, int k, int *items_out,
+                float *scores_out) {
+    check_k("cu2rec_model_topk: k must be at least 1", k);
+    require(items_out && scores_out, "cu2rec_model_topk: null output");
+    const std::vector<int> ids = query_ids(users, n_users, m.rows, "cu2rec_model_topk: user id out of range (or negative n_users)");
+    check_exclude(exclude, m.rows, m.cols, "cu2rec_model_topk: exclusions exceed the model's shape");
+    if (ids.empty()) return;
+    require(m.cols > 0, "cu2rec_model_topk: no items");
+    require_device();
+    select_to_host(user_items(m), exclude, ids, k, items_out, scores_out, nullptr);
+}
+
+// the k nearest other rows of the same side (include/cu2rec_amd.h: cu2rec_model_similar)
+void model_similar(const DeviceModel &m, int side, int metric, const DeviceCsr *exclude, const int *ids_in, int n_ids, int k,
+                   int *ids_out, float *scores_out) {
+    check_k("cu2rec_model_similar: k must be at least 1", k);
+    require(ids_out && scores_out, "cu2rec_model_similar: null output");
+    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, "cu2rec_model_similar: side is neither users nor items");
+    require(metric == CU2REC_SIM_DOT || metric == CU2REC_SIM_COSINE, "cu2rec_model_similar: metric is neither dot nor cosine");
+    const bool users = side == CU2REC_SIDE_USERS;
+    const int rows = users ? m.rows : m.cols;
+    const std::vector<int> ids = query_ids(ids_in, n_ids, rows, "cu2rec_model_similar: id out of range (or negative n_ids)");
+    check_exclude(exclude, rows, rows, "cu2rec_model_similar: exclusions exceed the side's rows");
+    if (ids.empty()) return;
+    require_device();
+    hipStream_t stream = nullptr;
+    const float *X = users ? m.P.ptr : m.Q.ptr;
+    const int ld = users ? m.ld : m.ldq;
+    DeviceBuffer<float> inv_norm;
+    if (metric == CU2REC_SIM_COSINE) {  // recomputed on every call: one read of the side's rows, nothing to keep in sync
+        inv_norm.allocate(rows);
+        hipLaunchKernelGGL(inv_norm_kernel, dim3(std::min((rows + 3) / 4, 8192)), dim3(256), 0, stream, X, ld, m.n_factors, rows,
+                           inv_norm.ptr);
+        CU2REC_HIP(hipGetLastError());
+    }
+    const TopkProblem pb{metric == CU2REC_SIM_COSINE ? kSimilarCos : kSimilarDot, X, ld, inv_norm.ptr, X, ld, inv_norm.ptr, rows,
+                         m.n_factors, 0.f};
+    select_to_host(pb, exclude, ids, k, ids_out, scores_out, stream);
+}
+
+// the k best non-excluded users of each listed item, with cu2rec_model_scores' floats
+void model_top_users(const DeviceModel &m, const DeviceCsr *exclude, const int *items, int n_items, int k, int *users_out,
+                     float *scores_out) {
+    check_k("cu2rec_model_top_users: k must be at least 1", k);
+    require(users_out && scores_out, "cu2rec_model_top_users: null output");
+    const std::vector<int> ids = query_ids(items, n_items, m.cols, "cu2rec_model_top_users: item id out of range (or negative n_items)");
+    check_exclude(exclude, m.cols, m.rows, "cu2rec_model_top_users: exclusions exceed the model's shape (items x users)");
+    if (ids.empty()) return;
+    require(m.rows > 0, "cu2rec_model_top_users: no users");
+    require_device();
+    const TopkProblem pb{kItemUsers, m.Q.ptr, m.ldq, m.item_bias.ptr, m.P.ptr, m.ld, m.user_bias.ptr, m.rows, m.n_factors,
+                         m.global_bias};
+    select_to_host(pb, exclude, ids, k, users_out, scores_out, nullptr);
+}
+
 void model_rank_metrics(const DeviceModel &m, const DeviceCsr *exclude, const DeviceCsr *test, int k, float threshold,
                         cu2rec_rank_metrics *out, double *per_user) {
     check_k("cu2rec_model_rank_metrics: k must be at least 1", k);
     require(test && out, "cu2rec_model_rank_metrics: null argument");
     require(!std::isnan(threshold), "cu2rec_model_rank_metrics: threshold is NaN");
     require(test->rows <= m.rows, "cu2rec_model_rank_metrics: the test set has rows past the model's rows");
-    check_exclude(m, exclude, "cu2rec_model_rank_metrics: exclusions exceed the model's shape");
+    check_exclude(exclude, m.rows, m.cols, "cu2rec_model_rank_metrics: exclusions exceed the model's shape");
     const double nan = std::numeric_limits<double>::quiet_NaN();
     *out = cu2rec_rank_metrics{k, 0, m.rows, nan, nan, nan, nan, nan};
     if (m.rows == 0) return;
@@ -415,7 +555,7 @@ void model_rank_metrics(const DeviceModel &m, const DeviceCsr *exclude, const De
         for (int i = 0; i < n; ++i) ids[i] = i;
         DeviceBuffer<int> d_ids(n);
         d_ids.upload(ids.data(), n);
-        TopkRunner run(m, k, n, exclude && exclude->nnz > 0, static_cast<size_t>(words) * 4 + sizeof(int));
+        TopkRunner run(user_items(m), k, n, exclude && exclude->nnz > 0, static_cast<size_t>(words) * 4 + sizeof(int));
         DeviceBuffer<unsigned> rel(static_cast<size_t>(run.batch) * words);
         DeviceBuffer<int> n_rel(run.batch);
         const bool all = std::isinf(threshold) && threshold < 0;
@@ -469,6 +609,22 @@ int cu2rec_model_rank_metrics(const cu2rec_model *m, const cu2rec_csr *exclude, 
         require(m, "model is null");
         model_rank_metrics(unwrap(m), exclude ? &unwrap(exclude) : nullptr, test ? &unwrap(test) : nullptr, k, threshold, out,
                            per_user);
+    });
+}
+
+int cu2rec_model_similar(const cu2rec_model *m, int side, int metric, const cu2rec_csr *exclude, const int *ids, int n_ids, int k,
+                         int *ids_out, float *scores_out) {
+    return guarded([&] {
+        require(m, "model is null");
+        model_similar(unwrap(m), side, metric, exclude ? &unwrap(exclude) : nullptr, ids, n_ids, k, ids_out, scores_out);
+    });
+}
+
+int cu2rec_model_top_users(const cu2rec_model *m, const cu2rec_csr *exclude, const int *items, int n_items, int k, int *users_out,
+                           float *scores_out) {
+    return guarded([&] {
+        require(m, "model is null");
+        model_top_users(unwrap(m), exclude ? &unwrap(exclude) : nullptr, items, n_items, k, users_out, scores_out);
     });
 }
 

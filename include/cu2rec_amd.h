@@ -392,6 +392,29 @@ int cu2rec_model_recommend(const cu2rec_model *m, const cu2rec_csr *rated, int k
  * scores_out: host, n_users x k.  1 <= k <= 256; a larger k is CU2REC_EUNSUPPORTED (cu2rec_model_recommend ranks any k). */
 int cu2rec_model_topk(const cu2rec_model *m, const cu2rec_csr *exclude, const int *users, int n_users, int k,
                       int *items_out, float *scores_out);
+/* Nearest neighbours of factor rows among the rows of the same matrix, on cu2rec_model_topk's tile and selection.
+ * side: CU2REC_SIDE_USERS (rows of P) or CU2REC_SIDE_ITEMS (rows of Q).  ids: host list of n_ids rows of that side
+ * (duplicates allowed), or NULL for every row (n_ids ignored).  The candidates of query row a are every row b != a of the
+ * side: the query row itself is never listed, however often it is asked for.
+ *   CU2REC_SIM_DOT:    score = x_a . x_b, no biases; the same MFMA contraction as cu2rec_model_scores.
+ *   CU2REC_SIM_COSINE: score = (x_a . x_b * inv_a) * inv_b, inv_r = 1 / |x_r| rounded to float (|x_r| summed in double by a
+ *                      pre-pass over the side's rows, recomputed on every call: nothing is cached on the model).  A row of
+ *                      norm 0 has inv 0: cosine 0 (+0.0 or -0.0) with every row, as query and as candidate.
+ * exclude: row a holds the rows excluded for query row a (topk's rules: unsorted, repeats allowed, NULL: nothing, rows past its
+ * last row exclude nothing; rows and ids must be below the side's row count).  Order, ties, -inf and padding are topk's, with
+ * row ids in place of items.  ids_out / scores_out: host, n x k.  1 <= k <= 256, else CU2REC_EUNSUPPORTED; a bad side, metric
+ * or id is CU2REC_EINVAL, checked before the device is touched. */
+enum { CU2REC_SIDE_USERS = 0, CU2REC_SIDE_ITEMS = 1 };
+enum { CU2REC_SIM_DOT = 0, CU2REC_SIM_COSINE = 1 };
+int cu2rec_model_similar(const cu2rec_model *m, int side, int metric, const cu2rec_csr *exclude, const int *ids, int n_ids,
+                         int k, int *ids_out, float *scores_out);
+/* The k users with the best predicted rating for each listed item: score ((gb + ub[u]) + ib[i]) + p_u . q_i, bit for bit the
+ * float cu2rec_model_scores writes at [u, i] (P stays the A operand of the contraction).  exclude: row i holds item i's excluded
+ * users, e.g. the training set transposed (HostCSR.transpose() in Python); topk's rules otherwise.  items: host list of n_items
+ * item ids (duplicates allowed), or NULL for every item.  Order, ties, -inf, padding and the range of k are topk's, with user
+ * ids in place of items.  users_out / scores_out: host, n x k. */
+int cu2rec_model_top_users(const cu2rec_model *m, const cu2rec_csr *exclude, const int *items, int n_items, int k,
+                           int *users_out, float *scores_out);
 /* Ranking quality of the model's top-k lists (cu2rec_model_topk over every row, excluding `exclude`) against a test set.
  * For each model row u:
  *   R_u = distinct items of test row u with rating >= threshold (threshold -INFINITY: every rating; NaN: CU2REC_EINVAL).
