@@ -316,7 +316,9 @@ class Model:
 
     def similar(self, ids=None, k=10, side="items", metric="cosine", exclude=None):
         """Nearest neighbours among the rows of one factor matrix (cu2rec_model_similar) -> (ids, scores), each (n, k).
-        side: "items" (rows of Q) or "users" (rows of P); metric: "cosine" or "dot" (no biases).  ids: rows of that side
+        side: "items" (rows of Q) or "users" (rows of P); metric: "cosine" or "dot" (no biases).  Cosine is the dot product of
+        the unit rows x / |x| (computed in double, rounded to float), so it holds at any row magnitude; a zero row has cosine
+        0 with everything, and a row holding an inf or a NaN scores +NaN with everything (listed first).  ids: rows of that side
         (duplicates allowed), or None for every row; a query row is never its own neighbour.  exclude: DeviceCSR whose row a
         holds the rows excluded for row a, or None.  Order, ties and -1 / NaN padding are topk's.  1 <= k <= 256."""
         side, metric = _choice(SIDES, side, "side"), _choice(METRICS, metric, "metric")

@@ -89,12 +89,15 @@ __global__ __launch_bounds__(256) void iota_items_kernel(int *__restrict__ items
         items[i] = static_cast<int>(i % n_items);
 }
 
+// The first k sorted pairs of each user; a key whose radix code is at or below -inf's (-inf itself: rated, and every NaN with
+// its sign bit set, which the descending sort puts after -inf) is padding, as in cu2rec_model_topk.  Nothing listable follows it.
 __global__ __launch_bounds__(256) void take_top_kernel(const float *__restrict__ keys, const int *__restrict__ items, int n_users,
                                                        int n_items, int k, float *__restrict__ top_scores, int *__restrict__ top_items) {
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n_users * k; i += gridDim.x * 256) {
         const int u = i / k, j = i - u * k;
-        const bool have = j < n_items && keys[static_cast<size_t>(u) * n_items + j] != -__builtin_inff();
-        top_scores[i] = have ? keys[static_cast<size_t>(u) * n_items + j] : __builtin_nanf("");
+        const float key = j < n_items ? keys[static_cast<size_t>(u) * n_items + j] : -__builtin_inff();
+        const bool have = __float_as_uint(key) < 0xFF800000u;  // sign clear, or a negative above -inf
+        top_scores[i] = have ? key : __builtin_nanf("");
         top_items[i] = have ? items[static_cast<size_t>(u) * n_items + j] : -1;
     }
 }

@@ -107,7 +107,7 @@ __device__ __forceinline__ void load_sorted(unsigned long long (&v)[E], const un
 // What a selection ranks (include/cu2rec_amd.h): the query rows X and the candidate rows Y of the score tile, and the score
 //   kUserItems   X = P, Y = Q                  ((gb + ub[query]) + ib[cand]) + x . y            cu2rec_model_topk
 //   kSimilarDot  X = Y = P or Q                x . y, the query row itself not a candidate       cu2rec_model_similar, DOT
-//   kSimilarCos  X = Y = P or Q                (x . y * inv_norm[query]) * inv_norm[cand], ditto  cu2rec_model_similar, COSINE
+//   kSimilarCos  X = Y = unit rows of P or Q   x . y, ditto; +NaN where bad[query] or bad[cand]  cu2rec_model_similar, COSINE
 //   kItemUsers   X = Q, Y = P                  ((gb + ub[cand]) + ib[query]) + y . x            cu2rec_model_top_users
 // kItemUsers keeps P in the MFMA A operand as scores_kernel does (the candidate tile is A): the accumulator's rows are then
 // candidates and its columns queries, so a lane owns one query and 16 candidates -- the same floats as cu2rec_model_scores.
@@ -115,7 +115,7 @@ enum TopkKind { kUserItems = 0, kSimilarDot = 1, kSimilarCos = 2, kItemUsers = 3
 
 // One workgroup = 32 listed queries (positions pos0 .. pos0 + 31 of `qids`, rows of X) against every row of Y.  LDS: the query
 // tile and four candidate tiles of scores_kernel, then the 32 thresholds and counts.  cand: [n_pos][64 E] keys of workspace.
-// qbias / cbias: per-row values of the score (biases, or inverse norms for kSimilarCos; unused by kSimilarDot).
+// qbias / cbias: per-row values of the score (biases, or unit_rows_kernel's flags for kSimilarCos; unused by kSimilarDot).
 template <int E, int Kind>
 __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ X, int ldx, const float *__restrict__ qbias,
                                                    const int *__restrict__ qids, int n_pos, const float *__restrict__ Y, int ldy,
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ X, 
         thr[threadIdx.x] = 0ull;
         cnt[threadIdx.x] = 0;
     }
-    float qb[16];  // the bias (inverse norm) of the query of each accumulator row
+    float qb[16];  // the bias (cosine: the flag) of the query of each accumulator row
     int qid[16];   // and its row id, for the self-exclusion
     float lane_qb = 0.f;  // kItemUsers: the bias of this lane's query (accumulator column r)
     if constexpr (Kind == kItemUsers) {
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ X, 
                     float s;
                     if constexpr (Kind == kUserItems) s = ((global_bias + qb[reg]) + ibv) + acc[reg];  // scores_kernel's expression
                     else if constexpr (Kind == kSimilarDot) s = acc[reg];
-                    else s = (acc[reg] * qb[reg]) * ibv;
+                    else s = qb[reg] != 0.f || ibv != 0.f ? __uint_as_float(0x7FC00000u) : acc[reg];
                     bool masked = mask && ((mask[static_cast<size_t>(pos) * words + (item >> 5)] >> (item & 31)) & 1u);
                     if constexpr (self) masked = masked || item == qid[reg];
                     const unsigned long long key = topk_key(s, item);
@@ -250,18 +250,26 @@ __global__ __launch_bounds__(256) void topk_kernel(const float *__restrict__ X, 
     }
 }
 
-// inv_norm[row] = 1 / |x_row| of rows 0 .. n - 1 of X (0 for a zero row: cosine 0 with everything), one wavefront per row;
-// squares summed in double, so that no row of finite floats overflows or underflows to a false zero
-__global__ __launch_bounds__(256) void inv_norm_kernel(const float *__restrict__ X, int ld, int n_factors, int n,
-                                                       float *__restrict__ inv_norm) {
+// The cosine pre-pass, one wavefront per row of X: unit[row] = x / |x| with |x| and the quotient in double, rounded to float, so
+// that every row of finite floats with a nonzero norm -- subnormal elements or elements near FLT_MAX -- becomes a unit row and
+// cosine is the plain dot product of two of them.  A zero row stays zero (cosine 0 with everything).  A row holding an inf or a
+// NaN (its sum of squares is not finite: no square of a finite float overflows a double) is written as zeros and flagged:
+// bad[row] = 1, and every score with it is +NaN (topk_kernel, kSimilarCos).  Columns n_factors .. ld - 1 are written as zeros.
+__global__ __launch_bounds__(256) void unit_rows_kernel(const float *__restrict__ X, int ld, int n_factors, int n,
+                                                        float *__restrict__ unit, float *__restrict__ bad) {
     const int lane = threadIdx.x & 63;
     for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += gridDim.x * 4) {
         const float *x = X + static_cast<size_t>(row) * ld;
+        float *y = unit + static_cast<size_t>(row) * ld;
         double s = 0.0;
         for (int j = lane; j < n_factors; j += 64) s += static_cast<double>(x[j]) * static_cast<double>(x[j]);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (lane == 0) inv_norm[row] = s > 0.0 ? static_cast<float>(1.0 / sqrt(s)) : 0.f;
+        const bool finite = s <= __DBL_MAX__;  // false for +inf and NaN
+        const double norm = sqrt(s);
+        for (int j = lane; j < ld; j += 64)
+            y[j] = j < n_factors && finite && s > 0.0 ? static_cast<float>(static_cast<double>(x[j]) / norm) : 0.f;
+        if (lane == 0) bad[row] = finite ? 0.f : 1.f;
     }
 }
 
@@ -504,15 +512,17 @@ void model_similar(const DeviceModel &m, int side, int metric, const DeviceCsr *
     hipStream_t stream = nullptr;
     const float *X = users ? m.P.ptr : m.Q.ptr;
     const int ld = users ? m.ld : m.ldq;
-    DeviceBuffer<float> inv_norm;
-    if (metric == CU2REC_SIM_COSINE) {  // recomputed on every call: one read of the side's rows, nothing to keep in sync
-        inv_norm.allocate(rows);
-        hipLaunchKernelGGL(inv_norm_kernel, dim3(std::min((rows + 3) / 4, 8192)), dim3(256), 0, stream, X, ld, m.n_factors, rows,
-                           inv_norm.ptr);
+    const bool cosine = metric == CU2REC_SIM_COSINE;
+    DeviceBuffer<float> unit, bad;
+    if (cosine) {  // recomputed on every call: one read of the side's rows, nothing to keep in sync
+        unit.allocate(static_cast<size_t>(rows) * ld);
+        bad.allocate(rows);
+        hipLaunchKernelGGL(unit_rows_kernel, dim3(std::min((rows + 3) / 4, 8192)), dim3(256), 0, stream, X, ld, m.n_factors, rows,
+                           unit.ptr, bad.ptr);
         CU2REC_HIP(hipGetLastError());
     }
-    const TopkProblem pb{metric == CU2REC_SIM_COSINE ? kSimilarCos : kSimilarDot, X, ld, inv_norm.ptr, X, ld, inv_norm.ptr, rows,
-                         m.n_factors, 0.f};
+    const float *Xs = cosine ? unit.ptr : X;
+    const TopkProblem pb{cosine ? kSimilarCos : kSimilarDot, Xs, ld, bad.ptr, Xs, ld, bad.ptr, rows, m.n_factors, 0.f};
     select_to_host(pb, exclude, ids, k, ids_out, scores_out, stream);
 }
 

@@ -380,8 +380,9 @@ int cu2rec_model_scores(const cu2rec_model *m, float *scores_device /* rows * co
 int cu2rec_model_scores_host(const cu2rec_model *m, float *scores_host /* rows * cols floats */);
 /* For every user the k best items it has NOT rated, best predicted rating first.  rated: a CSR whose row u holds user
  * u's ratings (NULL: nothing is excluded; users past its last row are not masked).  items_out / scores_out: host arrays of
- * rows * k entries; a user with fewer than k unrated items gets -1 / NaN padding.  Items with equal scores come out in
- * ascending item index (the sort is stable). */
+ * rows * k entries.  Rated items score -inf; a score whose radix code is at or below -inf's (-inf itself, and every NaN with its
+ * sign bit set, which the descending sort puts after -inf) is never listed, so a user with fewer than k listable items gets
+ * those, then -1 / NaN padding, never a hole.  Items with equal scores come out in ascending item index (the sort is stable). */
 int cu2rec_model_recommend(const cu2rec_model *m, const cu2rec_csr *rated, int k, int *items_out, float *scores_out);
 /* The k best non-excluded items of each listed user, without the dense score matrix: scores on the matrix cores and
  * selection on chip, workspace bounded by a batch of users (not by rows x cols).  Scores and order are recommend's, bit for
@@ -397,9 +398,13 @@ int cu2rec_model_topk(const cu2rec_model *m, const cu2rec_csr *exclude, const in
  * (duplicates allowed), or NULL for every row (n_ids ignored).  The candidates of query row a are every row b != a of the
  * side: the query row itself is never listed, however often it is asked for.
  *   CU2REC_SIM_DOT:    score = x_a . x_b, no biases; the same MFMA contraction as cu2rec_model_scores.
- *   CU2REC_SIM_COSINE: score = (x_a . x_b * inv_a) * inv_b, inv_r = 1 / |x_r| rounded to float (|x_r| summed in double by a
- *                      pre-pass over the side's rows, recomputed on every call: nothing is cached on the model).  A row of
- *                      norm 0 has inv 0: cosine 0 (+0.0 or -0.0) with every row, as query and as candidate.
+ *   CU2REC_SIM_COSINE: score = u_a . u_b on the same contraction, u_r = x_r / |x_r| computed in double and rounded to float
+ *                      by a pre-pass over the side's rows (recomputed on every call: nothing is cached on the model), so
+ *                      any row of finite floats with a nonzero norm, subnormal or near FLT_MAX, is scored within float
+ *                      rounding of its float64 cosine.  The pre-pass holds the unit rows in rows x ld floats of device memory
+ *                      for the call (55 MB for the users of ML-20M at f = 100).  A row of norm 0 has cosine 0 (+0.0 or -0.0) with every
+ *                      row, as query and as candidate.  A row holding an inf or a NaN scores +NaN (0x7FC00000) with every
+ *                      row, as query and as candidate: listed first by the radix order, whatever the NaN's origin.
  * exclude: row a holds the rows excluded for query row a (topk's rules: unsorted, repeats allowed, NULL: nothing, rows past its
  * last row exclude nothing; rows and ids must be below the side's row count).  Order, ties, -inf and padding are topk's, with
  * row ids in place of items.  ids_out / scores_out: host, n x k.  1 <= k <= 256, else CU2REC_EUNSUPPORTED; a bad side, metric

@@ -59,6 +59,72 @@ def test_host_selection_order_ties_and_padding():
     np.testing.assert_array_equal(nr.select(s, allowed, 2)[0], [3, 0])
 
 
+def _f32(bits):
+    return np.array(bits, np.uint32).view(np.float32)
+
+
+def test_radix_code_hand_values():
+    # rocPRIM's codes: sign clear -> bits ^ 0x80000000, sign set -> ~bits, with -0.0 first turned into +0.0
+    bits = [0x00000000, 0x80000000, 0x3F800000, 0xBF800000, 0x7F800000, 0xFF800000, 0x7FC00000, 0x7F800001, 0x7FFFFFFF,
+            0xFFC00000, 0xFF800001, 0x00000001, 0x80000001]
+    want = [0x80000000, 0x80000000, 0xBF800000, 0x407FFFFF, 0xFF800000, 0x007FFFFF, 0xFFC00000, 0xFF800001, 0xFFFFFFFF,
+            0x003FFFFF, 0x007FFFFE, 0x80000001, 0x7FFFFFFE]
+    np.testing.assert_array_equal(nr.radix_code(_f32(bits)), np.array(want, np.uint32))
+    assert nr.radix_code(_f32([0xFF800000]))[0] == nr.NEG_INF_CODE
+
+
+def test_select_signed_zeros_tie_by_ascending_id():
+    s = _f32([0x80000000, 0x00000000, 0x80000000, 0x3F800000, 0x00000000])  # -0, +0, -0, 1, +0
+    ids, sc = nr.select(s, np.ones(5, bool), 5)
+    np.testing.assert_array_equal(ids, [3, 0, 1, 2, 4])
+    np.testing.assert_array_equal(sc.view(np.uint32), [0x3F800000, 0x80000000, 0x00000000, 0x80000000, 0x00000000])
+
+
+def test_select_positive_nans_above_inf_and_negative_nans_never():
+    # ids: 0 +inf, 1 quiet +NaN, 2 +NaN of payload 1, 3 -inf, 4 -NaN (x86's default), 5 2.0, 6 +NaN of the largest payload,
+    # 7 -NaN of payload 1, 8 +inf, 9 -3.0, 10 quiet +NaN again
+    bits = [0x7F800000, 0x7FC00000, 0x7F800001, 0xFF800000, 0xFFC00000, 0x40000000, 0x7FFFFFFF, 0xFF800001, 0x7F800000,
+            0xC0400000, 0x7FC00000]
+    s = _f32(bits)
+    ids, sc = nr.select(s, np.ones(len(bits), bool), 12)
+    # +NaNs by their codes (payload), equal NaNs by ascending id; then the two +inf by ascending id; 2.0, -3.0; -inf and
+    # the sign-set NaNs never; padding only at the end
+    np.testing.assert_array_equal(ids, [6, 1, 10, 2, 0, 8, 5, 9, -1, -1, -1, -1])
+    np.testing.assert_array_equal(sc[:8].view(np.uint32), [bits[i] for i in (6, 1, 10, 2, 0, 8, 5, 9)])
+    assert np.isnan(sc[8:]).all()
+    # a short list is the head of the long one
+    for k in (1, 3, 5, 8):
+        np.testing.assert_array_equal(nr.select(s, np.ones(len(bits), bool), k)[0], ids[:k])
+
+
+def test_select_padding_comes_only_at_the_end():
+    # m listable entries, r excluded ones and some unlistable ones, m + r < k: the m entries, then padding
+    rng = np.random.RandomState(3)
+    for trial in range(200):
+        n = rng.randint(1, 40)
+        kinds = rng.randint(0, 6, n)
+        vals = np.where(kinds == 0, -np.inf, np.where(kinds == 1, np.inf, rng.randn(n))).astype(np.float32)
+        b = vals.view(np.uint32)
+        b[kinds == 2] = 0xFFC00000 | rng.randint(0, 1 << 22, (kinds == 2).sum()).astype(np.uint32)  # -NaN
+        b[kinds == 3] = 0x7FC00000 | rng.randint(0, 1 << 22, (kinds == 3).sum()).astype(np.uint32)  # +NaN
+        allowed = rng.rand(n) < 0.7
+        k = rng.randint(1, n + 5)
+        ids, sc = nr.select(vals, allowed, k)
+        listable = allowed & ~((kinds == 0) | (kinds == 2))
+        m = min(k, int(listable.sum()))
+        assert (ids[:m] >= 0).all() and (ids[m:] == -1).all() and np.isnan(sc[m:]).all()
+        assert listable[ids[:m]].all() and len(set(ids[:m].tolist())) == m
+        code = nr.radix_code(vals).astype(np.int64)
+        key = code[ids[:m]] * 64 - ids[:m]  # (code, smaller id) descending: one strictly falling key
+        assert (np.diff(key) < 0).all()
+        if m < k:
+            assert m == int(listable.sum())
+        elif m:
+            rest = listable.copy()
+            rest[ids[:m]] = False
+            assert not rest.any() or (code[rest] * 64 - np.nonzero(rest)[0]).max() < key[-1]
+
+
 def test_cosine64_zero_rows():
     X = np.array([[1.0, 0.0], [0.0, 0.0], [3.0, 4.0]])
     c = nr.cosine64(X)
