@@ -13,12 +13,17 @@ import numpy as np
 from ._lib import Config, Cu2recError, Hyper, RankMetrics, TrainStats, check, lib
 
 SGD_HOGWILD, SGD_SERIAL, SGD_ORDERED, SGD_PINGPONG, SGD_BLOCKSOLVE = 0, 1, 2, 3, 4
+ALS = 5  # alternating least squares: a training method of train() / cu2rec_train only (Model.sgd refuses it)
+# length thresholds of the ALS half-step (include/cu2rec_amd.h, CU2REC_ALS_*): ratings staged per step, the longest row one
+# workgroup solves alone, the most chunks a long row is cut into, and the bound of the partial-Gram workspace in bytes
+ALS_MAX_FACTORS, ALS_STEP, ALS_CHUNK, ALS_MAX_CHUNKS, ALS_WORKSPACE_BYTES = 252, 32, 1024, 64, 64 << 20
 SIDE_USERS, SIDE_ITEMS = 0, 1
 SIM_DOT, SIM_COSINE = 0, 1
 SIDES = {"users": SIDE_USERS, "items": SIDE_ITEMS}
 METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE}
 MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "pingpong": SGD_PINGPONG,
-         "blocksolve": SGD_BLOCKSOLVE}
+         "blocksolve": SGD_BLOCKSOLVE, "als": ALS}
+ALS_SIDES = {"users": (SIDE_USERS,), "items": (SIDE_ITEMS,), "both": (SIDE_USERS, SIDE_ITEMS)}
 
 
 def _mode(mode):
@@ -275,6 +280,22 @@ class Model:
         check(lib().cu2rec_model_sgd(self._h, train._h, C.byref(h), int(seed), int(iter0), int(n_iters), _mode(mode),
                                      1 if update_items else 0))
 
+    def als(self, train, hyper, side="both", sweeps=1):
+        """Exact alternating-least-squares half-steps on the SGD modes' objective (cu2rec_model_als): side "users" solves P and
+        user_bias against the frozen items, "items" the reverse, "both" a sweep (users, then items); repeated `sweeps` times.
+        hyper: Hyper or (learning_rate, P_reg, Q_reg, user_bias_reg, item_bias_reg) -- the learning rate is ignored.
+        Returns the number of rows left unchanged by a failed pivot (summed over the half-steps)."""
+        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        if side not in ALS_SIDES:
+            raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        total = 0
+        for _ in range(int(sweeps)):
+            for s in ALS_SIDES[side]:
+                n = C.c_int()
+                check(lib().cu2rec_model_als(self._h, train._h, C.byref(h), s, C.byref(n)))
+                total += n.value
+        return total
+
     def loss(self, ratings):
         """calculate_loss_gpu + get_error_metrics_gpu (loss.cu:40-49,195-200) -> dict(mae, rmse, sum_abs, sum_sq)."""
         sa, ss, mae, rmse = C.c_double(), C.c_double(), C.c_float(), C.c_float()
@@ -386,7 +407,8 @@ def default_mode(n_factors):
 
 def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=None, mode=None, verbose=True,
           P=None, user_bias=None, return_stats=False):
-    """train() (training.h:12-15).  mode None = default_mode(cfg.n_factors); "hogwild" opts into sgd.cu's racy semantics.  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
+    """train() (training.h:12-15).  mode None = default_mode(cfg.n_factors); "hogwild" opts into sgd.cu's racy semantics; "als"
+    trains by alternating least squares (one iteration = one sweep; no learning rate, so no decay).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
     otherwise everything starts from the seed-42 normal init.  Returns (P, Q, losses, user_bias,
     item_bias) like the reference's out-pointers; cfg.learning_rate / cfg.cur_iterations are

@@ -1,0 +1,77 @@
+// Alternating least squares (include/cu2rec_amd.h: cu2rec_model_als): one exact half-step solves every row of one side of
+// the model against the other side, frozen.  For a row with n ratings, Z is the n x (f + 2) matrix of its gathered partner
+// rows [x_i, 1, t_i] (t_i = r - gb - partner bias); the augmented Gram Z^T Z is formed on the matrix cores and the row's
+// (f + 1)-order system is solved by Cholesky in LDS (als.hip).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <memory>
+#include <vector>
+
+#include "hip_check.hpp"
+
+namespace cu2rec {
+
+// Length thresholds (include/cu2rec_amd.h mirrors them as CU2REC_ALS_*; the tests read them there).  A row's ratings are
+// staged kAlsStep at a time; a row of at most kAlsChunk ratings is gathered, reduced and solved by ONE workgroup; a longer row
+// is cut into ceil(n / kAlsChunk) chunks -- at most kAlsMaxChunks, beyond which the chunks grow instead, in whole steps --
+// whose partial Grams are summed in chunk order.  Either way the order of every sum is a function of n alone.
+constexpr int kAlsStep = CU2REC_ALS_STEP;                // 32
+constexpr int kAlsChunk = CU2REC_ALS_CHUNK;              // 1024
+constexpr int kAlsMaxChunks = CU2REC_ALS_MAX_CHUNKS;     // 64
+constexpr size_t kAlsWorkspaceBytes = CU2REC_ALS_WORKSPACE_BYTES;  // 64 MiB of partial Grams at once: the workspace bound
+constexpr int kAlsMaxFactors = CU2REC_ALS_MAX_FACTORS;   // 252: system order f + 1 <= 253, the packed factor fits one workgroup's LDS
+
+__host__ __device__ inline int als_chunks(int n) {
+    const int c = (n + kAlsChunk - 1) / kAlsChunk;
+    return c < kAlsMaxChunks ? c : kAlsMaxChunks;
+}
+__host__ __device__ inline int als_chunk_len(int n) {  // ratings per chunk (the last one may be shorter)
+    const int c = als_chunks(n);
+    const int per = (n + c - 1) / c;
+    return (per + kAlsStep - 1) / kAlsStep * kAlsStep;
+}
+
+// One side's CSR as the half-step reads it, plus the host list of its long rows (cut into chunks).
+struct AlsSide {
+    const int *indptr = nullptr, *indices = nullptr;
+    const float *data = nullptr;
+    int rows = 0, nnz = 0;
+    int rows_with_ratings = 0;
+    int max_len = 0;
+    std::vector<int> long_rows, long_first_chunk;  // long_first_chunk[r + 1] - long_first_chunk[r]: chunks of long row r
+    DeviceBuffer<int> d_long_rows, d_long_first_chunk, d_chunk_lo, d_chunk_hi;
+};
+
+// Cached on a cu2rec_csr: the user side reads the CSR itself; the item side reads its transpose, built on the device the first
+// time it is needed (a stable radix sort by item of the rating positions: users stay in ascending order within an item).
+struct AlsCache {
+    AlsSide users, items;
+    bool users_ready = false, items_ready = false;
+    DeviceBuffer<int> t_indptr, t_indices;
+    DeviceBuffer<float> t_data;
+    DeviceBuffer<float> workspace;  // the partial Grams of one batch of long rows, kAlsWorkspaceBytes at most
+    DeviceBuffer<int> unsolved;
+};
+
+struct AlsProblem {
+    const float *X;   // partner rows (stride ldx) and biases
+    int ldx;
+    const float *xb;
+    float *Y;         // solved rows (stride ldy) and biases
+    int ldy;
+    float *yb;
+    int n_factors;
+    float global_bias, reg, reg_bias;
+};
+
+// builds the transpose of (indptr, indices, data) [rows x cols] into the cache's t_* buffers
+void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, const float *data, int rows, int cols, int nnz,
+                         hipStream_t stream);
+// fills side.long_rows / chunk lists from the device indptr (once per side)
+void als_plan_side(AlsSide &side, hipStream_t stream);
+// one half-step over every row of `side` (rows < max_rows); returns the number of rows left unchanged by a failed pivot
+int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream);
+
+}  // namespace cu2rec

@@ -397,6 +397,51 @@ void DeviceModel::sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t se
                stream, pairs);
 }
 
+// Argument checks first: nothing on the device or in the model is touched by a call that fails them.
+int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream) {
+    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, "cu2rec_model_als: side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    const bool users = side == CU2REC_SIDE_USERS;
+    const float reg = users ? h.P_reg : h.Q_reg, reg_bias = users ? h.user_bias_reg : h.item_bias_reg;
+    require(std::isfinite(reg) && reg > 0.f, "cu2rec_model_als: the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
+    require(std::isfinite(reg_bias) && reg_bias >= 0.f, "cu2rec_model_als: the bias regulariser must be finite and >= 0");
+    require(train.rows <= rows && train.max_item < cols, "cu2rec_model_als: ratings exceed the model's shape");
+    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als: n_factors above 252 is not supported");
+    require_device();
+    check_faults();
+    finish_swap();
+    if (!train.als) train.als.reset(new AlsCache);
+    AlsCache &c = *train.als;
+    int unsolved = 0;
+    if (users) {
+        if (!c.users_ready) {
+            c.users.indptr = train.indptr.ptr;
+            c.users.indices = train.indices.ptr;
+            c.users.data = train.data.ptr;
+            c.users.rows = train.rows;
+            c.users.nnz = train.nnz;
+            als_plan_side(c.users, stream);
+            c.users_ready = true;
+        }
+        const AlsProblem p{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, global_bias, reg, reg_bias};
+        unsolved = als_half_step(c, c.users, p, rows, stream);
+    } else {
+        if (!c.items_ready) {  // the item-major view, built on the device once per rating matrix
+            als_build_transpose(c, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz, stream);
+            c.items.indptr = c.t_indptr.ptr;
+            c.items.indices = c.t_indices.ptr;
+            c.items.data = c.t_data.ptr;
+            c.items.rows = train.cols;
+            c.items.nnz = train.nnz;
+            als_plan_side(c.items, stream);
+            c.items_ready = true;
+        }
+        const AlsProblem p{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, global_bias, reg, reg_bias};
+        unsolved = als_half_step(c, c.items, p, cols, stream);
+    }
+    other_in_sync = false;  // Q moved on without the ping-pong pair
+    return unsolved;
+}
+
 void DeviceModel::loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
                        hipStream_t stream) const {
     // Appendix quirk 6: a test file may have fewer users than train, never more
@@ -679,6 +724,14 @@ int cu2rec_model_sgd(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hype
     return guarded([&] {
         require(m && train && hyper, "null argument");
         m->impl.sgd(train->impl, *hyper, seed, iter0, n_iters, mode, update_items, nullptr);
+    });
+}
+
+int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *unsolved) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_als: null argument");
+        const int n = m->impl.als(train->impl, *hyper, side, nullptr);
+        if (unsolved) *unsolved = n;
     });
 }
 

@@ -7,6 +7,7 @@
 
 #include <memory>
 
+#include "als.hpp"
 #include "hip_check.hpp"
 #include "ordered.hpp"
 
@@ -59,6 +60,7 @@ struct DeviceCsr {
     int users_with_ratings;
     mutable std::unique_ptr<OrderedSchedule> schedule;  // created on first CU2REC_SGD_ORDERED use
     mutable DeviceBuffer<uint2> pairs;                   // sample array, created on first Hogwild use (SgdArgs::pairs)
+    mutable std::unique_ptr<AlsCache> als;               // item-major view and row plans, created on first cu2rec_model_als use
 };
 
 // P, Q, biases on the device with padded rows (see include/cu2rec_amd.h "Device data layout").
@@ -71,6 +73,8 @@ struct DeviceModel {
     void sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, uint64_t iter0, int n_iters, int mode,
              int update_items, hipStream_t stream, bool defer_last_swap = false, int user_offset = 0);
     void finish_swap();
+    // one exact ALS half-step (side: CU2REC_SIDE_USERS / CU2REC_SIDE_ITEMS); returns the rows a failed pivot left unchanged
+    int als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream);
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
               hipStream_t stream) const;
     DeviceBuffer<float> P, Q, user_bias, item_bias;

@@ -2,12 +2,13 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong] [-g gpus] [-s sync_every]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als] [-g gpus] [-s sync_every]
 //          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
 // for bit).  `-m hogwild` opts into sgd.cu's own racy semantics (fastest, 1e-3 away from the sequential result while
-// the model is still moving).
+// the model is still moving).  `-m als` trains by alternating least squares instead of SGD: total_iterations sweeps (user
+// half-step, item half-step) with the config's regularisers, no learning rate; single GPU, n_factors up to 252.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -268,7 +269,12 @@ int run_multi_gpu(int nranks, int mode, int sync_every, int merge, const std::st
 }  // namespace
 
 int main(int argc, char **argv) {
-    if (argc < 2) return -1;  // mf.cu:17-19
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als] [-g gpus] [-s sync_every] "
+                        "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
+    if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
+        std::cerr << usage;
+        return -1;
+    }
     std::string config_path;
     int mode = CU2REC_SGD_BLOCKSOLVE;  // the mode that meets the north star's 1e-4 bar; -m hogwild is the opt-in
     int gpus = 1, sync_every = 0, merge = CU2REC_MERGE_ADAPTIVE;
@@ -309,6 +315,7 @@ int main(int argc, char **argv) {
                        : std::strcmp(optarg, "ordered") == 0 ? CU2REC_SGD_ORDERED
                        : std::strcmp(optarg, "pingpong") == 0 ? CU2REC_SGD_PINGPONG
                        : std::strcmp(optarg, "blocksolve") == 0 ? CU2REC_SGD_BLOCKSOLVE
+                       : std::strcmp(optarg, "als") == 0 ? CU2REC_ALS
                                                              : CU2REC_SGD_HOGWILD;
                 break;
             default:
@@ -317,8 +324,7 @@ int main(int argc, char **argv) {
         }
     }
     if (optind + 2 > argc) {
-        std::cerr << "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong] [-g gpus] [-s sync_every] "
-                     "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
+        std::cerr << usage;
         return -1;
     }
     if (rank_given && (rank_k < 1 || rank_k > 256)) {
@@ -334,6 +340,10 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (gpus > 1) {
+        if (mode == CU2REC_ALS) {
+            std::cerr << "mf: -m als is single-GPU only (not with -g)\n";
+            return 1;
+        }
         if (mode == CU2REC_SGD_PINGPONG) {
             std::cerr << "mf: -m pingpong is single-GPU only\n";
             return 1;

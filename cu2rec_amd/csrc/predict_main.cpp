@@ -1,7 +1,7 @@
 // bin/predict -- partial fit for new users against a trained model, then recommendations.
 // Drop-in for the reference CLI (predict.cu:72-146):
 //
-//   bin/predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-k K] user_ratings.csv
+//   bin/predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-k K] user_ratings.csv
 //
 // Q, item_bias and global_bias come from the files bin/mf wrote; only the users' factor rows and biases are
 // trained (is_train = false).  Unlike the reference, the frozen-item flag really reaches the device (there
@@ -13,6 +13,10 @@
 // fitted in one batch (frozen items: no update crosses users, so every fit equals the one-user result), scored with one
 // dense product on the matrix cores and ranked by one segmented sort on the device (cu2rec_model_scores /
 // cu2rec_model_recommend); output is one block per user, headed "User: <id>".  -k K limits the recommendations listed.
+//
+// -A: the new users are fitted by ONE exact alternating-least-squares user half-step against the frozen item side
+// (cu2rec_model_als, the config's P_reg and user_bias_reg) instead of the SGD loop: the optimum of each user's regularised
+// objective in one call.  Works with and without -u; scoring, ranking and output are unchanged.
 //
 //   bin/predict -c config -q q.csv -S [-k K] item_ids.txt
 //
@@ -97,14 +101,15 @@ int similar_items(const cu2rec_config &cfg, const std::string &q_path, const std
 int main(int argc, char **argv) {
     if (argc < 2) return 2;  // predict.cu:73-75
     std::string config_path, item_bias_path, global_bias_path, q_path;
-    bool many_users = false, similar = false;
+    bool many_users = false, similar = false, als = false;
     int top_k = 0;  // 0: every unrated item, as the reference prints
     const char *k_arg = nullptr;
     int opt;
-    while ((opt = getopt(argc, argv, "c:i:g:q:uk:S")) != -1) {
+    while ((opt = getopt(argc, argv, "c:i:g:q:uk:SA")) != -1) {
         switch (opt) {
             case 'u': many_users = true; break;
             case 'S': similar = true; break;
+            case 'A': als = true; break;
             case 'k':
                 top_k = std::max(0, std::atoi(optarg));
                 k_arg = optarg;
@@ -138,7 +143,7 @@ int main(int argc, char **argv) {
         }
     }
     if (optind >= argc || config_path.empty() || item_bias_path.empty() || global_bias_path.empty() || q_path.empty()) {
-        std::cerr << "usage: predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-k K] user_ratings.csv\n";
+        std::cerr << "usage: predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-k K] user_ratings.csv\n";
         return 2;
     }
     try {
@@ -200,11 +205,18 @@ int main(int argc, char **argv) {
             ub0[u] = one_ub[0];
         }
         cu2rec::ModelHandle model(B, n_items, f, global_bias, P0.data(), Q.data, ub0.data(), item_bias.data);
-        std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
-        // frozen items: no two updates can conflict, every mode gives the sequential result; Hogwild runs all of a call's
-        // iterations for all users in one launch
-        cu2rec::check(cu2rec_train(d_users.h, d_users.h, &cfg, model.h, B == 1 ? CU2REC_SGD_SERIAL : CU2REC_SGD_HOGWILD, 1,
-                                   losses.data(), nullptr));  // predict.cu:126
+        if (als) {  // one exact user half-step: every user's optimum against the frozen items
+            const cu2rec_hyper h{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
+            int unsolved = 0;
+            cu2rec::check(cu2rec_model_als(model.h, d_users.h, &h, CU2REC_SIDE_USERS, &unsolved));
+            if (unsolved) std::cerr << "predict: " << unsolved << " user(s) could not be fitted (non-finite values); they keep the initial factors\n";
+        } else {
+            std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
+            // frozen items: no two updates can conflict, every mode gives the sequential result; Hogwild runs all of a call's
+            // iterations for all users in one launch
+            cu2rec::check(cu2rec_train(d_users.h, d_users.h, &cfg, model.h, B == 1 ? CU2REC_SGD_SERIAL : CU2REC_SGD_HOGWILD, 1,
+                                       losses.data(), nullptr));  // predict.cu:126
+        }
 
         // predict_ratings (predict.cu:18-30) and get_recommendations (predict.cu:50-65), on the device
         std::vector<float> predictions(static_cast<size_t>(B) * n_items);

@@ -337,6 +337,7 @@ int cu2rec_shard_job_run(cu2rec_shard_job *job, const cu2rec_hyper *hyper, uint6
                          int mode, int update_items) {
     return guarded([&] {
         require(job && hyper, "cu2rec_shard_job_run: null argument");
+        require(mode != CU2REC_ALS, "cu2rec_shard_job_run: alternating least squares (CU2REC_ALS) is not available in sharded training");
         job->impl.run(*hyper, seed, iter0, n_iters, mode, update_items, nullptr);
     });
 }
@@ -379,6 +380,7 @@ int cu2rec_train_sharded(cu2rec_shard_job *job, const cu2rec_csr *test, cu2rec_c
                          float *losses, cu2rec_train_stats *stats) {
     return guarded([&] {
         require(job && test && cfg, "cu2rec_train_sharded: null argument");
+        require(mode != CU2REC_ALS, "cu2rec_train_sharded: alternating least squares (CU2REC_ALS) is not available in sharded training");
         train_sharded(job->impl, unwrap(test), *cfg, mode, verbose != 0, losses, stats);
     });
 }

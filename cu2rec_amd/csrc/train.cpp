@@ -4,6 +4,7 @@
 // stream and timed by HIP events.  No ping-pong buffers, no per-iteration memset, no RNG state:
 // item rows are updated in place (mf_sequential.cu semantics, the parity target) -- except in
 // CU2REC_SGD_PINGPONG, which keeps the reference GPU loop's two item buffers and its loss-before-swap order.
+// CU2REC_ALS runs the same schedule with exact half-steps (als.hip) in place of the SGD iterations.
 #include "train_schedule.hpp"
 
 namespace cu2rec {
@@ -15,6 +16,30 @@ void train(const DeviceCsr &train_csr, const DeviceCsr &test_csr, cu2rec_config 
     require(test_csr.rows <= model.rows && test_csr.max_item < model.cols,
             "cu2rec_train: test ratings name users/items the model does not have");
     hipStream_t stream = nullptr;  // the reference runs everything on the default stream
+    if (mode == CU2REC_ALS) {
+        // one "iteration" is one sweep: the user half-step, then the item half-step unless the items are frozen.  The same loss
+        // cadence and lines; no learning rate, so no patience / decay; stats->updates = rows solved
+        if (cfg.n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_train: CU2REC_ALS supports n_factors up to 252");
+        double solved = 0.0;
+        train_schedule(
+            cfg, verbose, true, 0.0, losses, stats, stream,
+            [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
+                for (int k = 0; k < n; ++k) {
+                    const int u = model.als(train_csr, h, CU2REC_SIDE_USERS, s);
+                    solved += train_csr.als->users.rows_with_ratings - u;
+                    if (cfg.is_train) {
+                        const int i = model.als(train_csr, h, CU2REC_SIDE_ITEMS, s);
+                        solved += train_csr.als->items.rows_with_ratings - i;
+                    }
+                }
+            },
+            [&](bool on_train, float *mae, float *rmse) {
+                model.loss(on_train ? train_csr : test_csr, nullptr, nullptr, mae, rmse, stream);
+            },
+            [] {}, /*decay_lr=*/false);
+        if (stats) stats->updates = solved;
+        return;
+    }
     const uint64_t seed = static_cast<uint64_t>(static_cast<uint32_t>(cfg.seed));
     train_schedule(
         cfg, verbose, true, static_cast<double>(train_csr.users_with_ratings), losses, stats, stream,

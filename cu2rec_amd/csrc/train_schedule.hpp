@@ -37,8 +37,8 @@ struct HipClock {  // the SGD stretch between two loss checks, by events on the 
 
 template <class Sgd, class Loss, class After>
 void train_schedule(cu2rec_config &cfg, bool verbose, bool print, double updates_per_iteration, float *losses,
-                    cu2rec_train_stats *stats, hipStream_t stream, Sgd sgd, Loss loss, After after_check) {
-    train_schedule_with<HipClock>(cfg, verbose, print, updates_per_iteration, losses, stats, stream, sgd, loss, after_check);
+                    cu2rec_train_stats *stats, hipStream_t stream, Sgd sgd, Loss loss, After after_check, bool decay_lr = true) {
+    train_schedule_with<HipClock>(cfg, verbose, print, updates_per_iteration, losses, stats, stream, sgd, loss, after_check, decay_lr);
 }
 
 }  // namespace cu2rec

@@ -20,10 +20,11 @@ inline bool is_check_iteration(int i, const cu2rec_config &cfg) {  // training.c
 
 // sgd(hyper, first_iteration, n, stream): queue n iterations; loss(train?, &mae, &rmse): evaluate on train / test (blocking);
 // after_check(): what follows a loss check (CU2REC_SGD_PINGPONG's deferred swap).  `print`: this rank writes the lines.
+// decay_lr == false (CU2REC_ALS, which has no learning rate): no patience / learning-rate decay, no "New Learning Rate" line.
 // Clock: start(stream), stop(stream), elapsed_ms() (after a blocking loss call), drain() (training.cu:172).
 template <class Clock, class Stream, class Sgd, class Loss, class After>
 void train_schedule_with(cu2rec_config &cfg, bool verbose, bool print, double updates_per_iteration, float *losses,
-                         cu2rec_train_stats *stats, Stream stream, Sgd sgd, Loss loss, After after_check) {
+                         cu2rec_train_stats *stats, Stream stream, Sgd sgd, Loss loss, After after_check, bool decay_lr = true) {
     require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train: bad iteration counts");
     const int total = cfg.total_iterations;
     if (losses)
@@ -58,8 +59,8 @@ void train_schedule_with(cu2rec_config &cfg, bool verbose, bool print, double up
             std::printf("TEST: Iteration %d GPU MAE: %f RMSE: %f\n", seg_end + 1, validation_mae, validation_rmse);
         }
         // training.cu:146-155: patience is consumed when the test RMSE got worse, never restored on improvement
-        if (last_validation_rmse < validation_rmse) current_patience--;
-        if (current_patience <= 0) {
+        if (decay_lr && last_validation_rmse < validation_rmse) current_patience--;
+        if (decay_lr && current_patience <= 0) {
             current_patience = static_cast<int>(cfg.patience);
             cfg.learning_rate *= cfg.learning_rate_decay;
             if (verbose && print) std::printf("New Learning Rate: %f\n: ", cfg.learning_rate);

@@ -178,7 +178,10 @@ typedef enum cu2rec_sgd_mode {
      * cu2rec_schedule like CU2REC_SGD_ORDERED.  A call whose decay factors 1 - learning_rate * Q_reg or
      * 1 - learning_rate * item_bias_reg (in double) are at or below zero has no block form: it runs the ordered walk and
      * is the sequential result bit for bit. */
-    CU2REC_SGD_BLOCKSOLVE = 4
+    CU2REC_SGD_BLOCKSOLVE = 4,
+    /* Not an SGD mode: alternating least squares (cu2rec_model_als below), accepted by cu2rec_train only.  cu2rec_model_sgd,
+     * the raw-pointer entry points and the sharded driver refuse it (CU2REC_EINVAL). */
+    CU2REC_ALS = 5
 } cu2rec_sgd_mode;
 
 /* Replaces sgd_update (sgd.cu:22-75) + the per-iteration launch loop of train()
@@ -439,6 +442,37 @@ int cu2rec_model_rank_metrics(const cu2rec_model *m, const cu2rec_csr *exclude, 
                               float threshold, cu2rec_rank_metrics *out, double *per_user);
 
 /* ------------------------------------------------------------------------------------------
+ * Alternating least squares.  SGD (every mode above) takes stochastic steps on
+ *   L = 1/2 sum_(u,i) in train (r_ui - gb - ub_u - ib_i - p_u . q_i)^2
+ *     + 1/2 sum_u n_u (P_reg |p_u|^2 + user_bias_reg ub_u^2) + 1/2 sum_i m_i (Q_reg |q_i|^2 + item_bias_reg ib_i^2)
+ * (n_u: ratings of user u in the CSR, m_i: entries naming item i; repeated pairs count separately; gb fixed).  One ALS half-step
+ * minimises L exactly over one side with the other frozen.  Users: for each user u with n_u >= 1, x = [p_u; ub_u], z_i = [q_i; 1],
+ * t_ui = r_ui - gb - ib_i, solve (sum_i z_i z_i^T + n_u diag(P_reg, ..., P_reg, user_bias_reg)) x = sum_i t_ui z_i.  Items: the
+ * same with y = [q_i; ib_i], w_u = [p_u; 1], t = r - gb - ub_u, Q_reg, item_bias_reg and m_i.
+ * The Gram is formed on the matrix cores in f32 (v_mfma_f32_32x32x2_f32), the system solved by Cholesky in LDS (f32).  A row's
+ * result depends only on its own ratings and the partner side -- never on the batch, the other rows or the run: bit-identical
+ * across runs, and a user fitted from a one-user CSR equals the same user fitted with all the others.  The result overwrites the
+ * row's factors (padding floats written as zero) and its bias.  Left unchanged: rows with no ratings, model rows past the CSR's
+ * rows / items, the other side, and every row whose factorisation meets a pivot that is not a finite positive float or whose
+ * solution is not finite (e.g. a row that gathers an inf or a NaN) -- these are counted in *unsolved (may be NULL).
+ * side: CU2REC_SIDE_USERS (solve P, user_bias given Q, item_bias) or CU2REC_SIDE_ITEMS (the reverse).  hyper->learning_rate is
+ * ignored.  CU2REC_EINVAL, checked before the device or the model is touched: a null m / train / hyper, a bad side, a factor
+ * regulariser of the side (P_reg for users, Q_reg for items) that is not finite and > 0, a bias regulariser of the side that is
+ * not finite and >= 0 (negative, NaN, inf), ratings past the model's shape.  n_factors > CU2REC_ALS_MAX_FACTORS: CU2REC_EUNSUPPORTED.
+ * A pending ping-pong swap is finished first.  The first item half-step on a cu2rec_csr builds its item-major view on the device
+ * (nnz x 8 bytes, kept with the cu2rec_csr).
+ * Length thresholds: a row's ratings are staged CU2REC_ALS_STEP at a time; rows of at most CU2REC_ALS_CHUNK ratings are solved by
+ * one workgroup; longer rows are cut into ceil(n / CU2REC_ALS_CHUNK) chunks (at most CU2REC_ALS_MAX_CHUNKS: longer rows get longer
+ * chunks, in whole steps) whose partial Grams are summed in chunk order.  Workspace: the long rows go in batches of whole rows whose
+ * partial Grams (P x 4 KiB each, P = T (T + 1) / 2 tile pairs, T = ceil((n_factors + 2) / 32)) fit CU2REC_ALS_WORKSPACE_BYTES
+ * (64 MiB: 1,638 chunks at n_factors 100, 455 at 252) -- whatever the row count; allocated on the first long row, kept with the
+ * cu2rec_csr.
+ * ---------------------------------------------------------------------------------------- */
+enum { CU2REC_ALS_MAX_FACTORS = 252, CU2REC_ALS_STEP = 32, CU2REC_ALS_CHUNK = 1024, CU2REC_ALS_MAX_CHUNKS = 64,
+       CU2REC_ALS_WORKSPACE_BYTES = 64 << 20 };
+int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *unsolved);
+
+/* ------------------------------------------------------------------------------------------
  * train() -- replaces both overloads of train (training.h:12-15, training.cu:21-217):
  * total_iterations iterations; loss on train and test when i == 0, (i+1) % check_error == 0
  * or last (training.cu:118) printed as "TRAIN: Iteration %d GPU MAE: %f RMSE: %f" / "TEST: ..."
@@ -448,6 +482,9 @@ int cu2rec_model_rank_metrics(const cu2rec_model *m, const cu2rec_csr *exclude, 
  * reference does (training.cu:152,170).  losses (host, total_iterations floats, may be NULL):
  * losses[i] = test RMSE at the checked iterations (training.cu:158), NaN elsewhere.
  * The model is updated in place; download it afterwards.
+ * mode CU2REC_ALS: one iteration is one sweep -- cu2rec_model_als on the users, then on the items when cfg->is_train -- with the
+ * same loss cadence, lines and losses; there is no learning rate, so no patience / decay: cfg->learning_rate stays as it is and no
+ * "New Learning Rate" line is printed; stats->updates counts the rows solved.  n_factors > 252: CU2REC_EUNSUPPORTED.
  * ---------------------------------------------------------------------------------------- */
 typedef struct cu2rec_train_stats {
     double seconds_total;  /* wall time of the loop, loss checks included (training.cu:106,172-177) */

@@ -1,0 +1,73 @@
+"""Times the alternating-least-squares half-steps (cu2rec_model_als) on the synthetic ML-20M and Netflix shapes and prints each time
+next to its Gram roofline.
+
+    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3]
+
+For every shape: the item half-step's first call on a fresh cu2rec_csr (it builds the item-major view), the item half-step again
+(view cached), the user half-step, and a whole sweep (users then items).  Times are wall clock around the synchronous call (the
+call returns after a device-to-host read of its unsolved count), best of --reps.  Roofline: the Gram of a half-step is
+2 nnz (f + 2)^2 flop when formed whole; its lower triangle half that; at 155 TF/s (fp32 MFMA peak of the MI355X) -- the partner-row
+gather (nnz x 4 (f + 1) bytes) and the per-row Cholesky (about rows x (f + 1)^3 / 3 flop) come on top."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+import cu2rec_amd as cu  # noqa: E402
+from cu2rec_amd import synth  # noqa: E402
+
+PEAK = 155e12
+HYPER = (0.01, 0.05, 0.05, 0.02, 0.02)
+
+
+def best(fn, reps):
+    t = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        t.append(time.perf_counter() - t0)
+    return min(t)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="ml-20m,netflix")
+    ap.add_argument("--factors", type=int, default=100)
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    f = args.factors
+    for name in args.shapes.split(","):
+        tr, _ = synth.make_named(name)
+        d = cu.DeviceCSR(tr)
+        m = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
+        gram = 2.0 * tr.nnz * (f + 2) ** 2
+        roof_full, roof_lower = gram / PEAK * 1e3, gram / 2 / PEAK * 1e3
+        gather_gb = tr.nnz * 4.0 * (f + 1) / 1e9
+        users = int((np.diff(tr.indptr) > 0).sum())
+        items = int((np.bincount(tr.indices, minlength=tr.cols) > 0).sum())
+        print("%s: %d users, %d items, %d ratings, f = %d; Gram %.2e flop per half-step -> roofline %.2f ms whole, %.2f ms lower "
+              "triangle; gather %.1f GB; Cholesky ~%.1e flop (users), ~%.1e (items)"
+              % (name, tr.rows, tr.cols, tr.nnz, f, gram, roof_full, roof_lower, gather_gb, users * (f + 1) ** 3 / 3.0,
+                 items * (f + 1) ** 3 / 3.0), flush=True)
+        t0 = time.perf_counter()
+        assert m.als(d, HYPER, "items") == 0  # first item half-step: builds the item-major view
+        first = time.perf_counter() - t0
+        rows = [("items, first call (builds the view)", first)]
+        rows.append(("items", best(lambda: m.als(d, HYPER, "items"), args.reps)))
+        rows.append(("users", best(lambda: m.als(d, HYPER, "users"), args.reps)))
+        rows.append(("sweep (users + items)", best(lambda: m.als(d, HYPER, "both"), args.reps)))
+        for label, t in rows:
+            roof = 2 * roof_lower if label.startswith("sweep") else roof_lower
+            print("  %-38s %9.2f ms   (lower-triangle Gram roofline %.2f ms: %.1fx)" % (label, 1e3 * t, roof, 1e3 * t / roof),
+                  flush=True)
+        m.close()
+        d.close()
+
+
+if __name__ == "__main__":
+    main()
