@@ -28,7 +28,10 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <atomic>
+#include <cmath>
 #include <cstdlib>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -67,7 +70,7 @@ __device__ __forceinline__ unsigned ld_agent(const unsigned *p) {  // global_loa
 __device__ __forceinline__ unsigned long long ld_agent(const unsigned long long *p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// every device-side wait in here is bounded: BsIteration::wait_ticks (bs_wait_ticks(): CU2REC_BS_WAIT_S seconds, default 2) of the 100 MHz wall clock
+// every device-side wait in here is bounded: BsIteration::wait_ticks (wait_ticks(): CU2REC_BS_WAIT_S seconds, default 2) of the 100 MHz wall clock
 
 // v[l] + v[l ^ 16] in every lane
 __device__ __forceinline__ float row_pair_sum(float v) {
@@ -804,7 +807,10 @@ __host__ __device__ inline size_t la_lds_bytes(int nslots) {
 
 enum { kSyC0 = 0, kSyC1 = 1, kSyE = 2, kSyG = 3, kSyLdP = 4, kSyLdR = 8, kSyR = 12, kSyAbort = 13 };  // (C0 | C1, LdP[4], LdR[4]: read together)
 
-// waits until *word >= target; bounded: gives up after 2 s (or as soon as another wait of the workgroup has), sets the status word
+// waits until *word >= target; bounded: gives up after 2 s (or as soon as another wait of the workgroup has) and sets the workgroup's abort
+// flag and the status word to 2 -- a wait inside one workgroup: the fork / join topology had no part in it (check_faults, device.cpp).  The
+// store is unconditional (a load in front of it costs the loader's hot loop its wait-count schedule): a join that gave up earlier in the
+// same call (1) is then reported as this wait.
 __device__ __forceinline__ void la_wait(unsigned *sy, int word, unsigned target, const BsIteration &it) {
     unsigned polls = 0;
     unsigned long long t0 = 0;
@@ -813,8 +819,8 @@ __device__ __forceinline__ void la_wait(unsigned *sy, int word, unsigned target,
         if ((++polls & 1023u) == 0) {
             if (t0 == 0) t0 = wall_clock64();
             if (__hip_atomic_load(sy + kSyAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u || wall_clock64() - t0 > it.wait_ticks) {
-                __hip_atomic_store(sy + kSyAbort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if ((threadIdx.x & 63) == 0) __hip_atomic_store(it.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(sy + kSyAbort, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if ((threadIdx.x & 63) == 0) __hip_atomic_store(it.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
         }
@@ -840,8 +846,8 @@ __device__ __forceinline__ void la_wait4(unsigned *sy, int word, unsigned target
         if ((++polls & 1023u) == 0) {
             if (t0 == 0) t0 = wall_clock64();
             if (__hip_atomic_load(sy + kSyAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u || wall_clock64() - t0 > it.wait_ticks) {
-                __hip_atomic_store(sy + kSyAbort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if ((threadIdx.x & 63) == 0) __hip_atomic_store(it.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(sy + kSyAbort, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if ((threadIdx.x & 63) == 0) __hip_atomic_store(it.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
         }
@@ -861,8 +867,8 @@ __device__ __forceinline__ void la_wait2(unsigned *sy, int word, unsigned target
         if ((++polls & 1023u) == 0) {
             if (t0 == 0) t0 = wall_clock64();
             if (__hip_atomic_load(sy + kSyAbort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u || wall_clock64() - t0 > it.wait_ticks) {
-                __hip_atomic_store(sy + kSyAbort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if ((threadIdx.x & 63) == 0) __hip_atomic_store(it.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(sy + kSyAbort, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if ((threadIdx.x & 63) == 0) __hip_atomic_store(it.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 break;
             }
         }
@@ -1196,15 +1202,19 @@ __device__ __forceinline__ void chain_lookahead(const SgdArgs &a, const BsIterat
 // per iteration).  (The side kernel's workgroups counting THEMSELVES through, each behind an agent-scope release of its rows, was
 // tried in round 4: 9350 L2 write-backs per launch, the side kernel took 292 us instead of 46.)
 // This wait guards DATA -- the next phase 1 reads rows the side kernel and phase 3 write -- so it gives up only when the GPU must be
-// taken for wedged: 15 x the bound of the other waits, 30 s by default; then the status word is set and the call reports it.
+// taken for wedged: 15 x the bound of the other waits, 30 s by default; then the status word is set to 1 and the call reports it.  A word
+// that another wait has set already (a ring wait's 2) ends the wait too, and is left as it is: the first cause is the one reported.
 __device__ __forceinline__ void await_iteration_end(const BsIteration &it) {
     const unsigned long long t0 = wall_clock64();
     unsigned polls = 0;
     while (it.side_seq && ld_agent(it.side_seq) < it.side_target) {
         __builtin_amdgcn_s_sleep(8);
-        if ((++polls & 63u) == 0 && (ld_agent(it.status) != 0u || wall_clock64() - t0 > 15ull * it.wait_ticks)) {
-            __hip_atomic_store(it.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
+        if ((++polls & 63u) == 0) {
+            if (ld_agent(it.status) != 0u) break;
+            if (wall_clock64() - t0 > 15ull * it.wait_ticks) {
+                __hip_atomic_store(it.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
         }
     }
 }
@@ -1290,7 +1300,8 @@ __global__ __launch_bounds__(64 * kUpdMaxWaves) void bs_update_kernel(SgdArgs a,
         if (threadIdx.x == 0) await_iteration_end(it);
         return;
     }
-    // (launch_blocks workgroups stride through the dense block table, like phase 1's; update_block keeps nothing in LDS)
+    // (launch_blocks workgroups stride through the dense block table -- only phase 3 strides, phase 1 keeps the full grid of max_blocks
+    // workgroups; update_block keeps nothing in LDS)
     for (int blk = g; blk < it.max_blocks; blk += it.launch_blocks) {
         if (it.blocks[blk].n_valid == 0) break;  // workgroup uniform
         update_block(a, it, blk);
@@ -1298,7 +1309,7 @@ __global__ __launch_bounds__(64 * kUpdMaxWaves) void bs_update_kernel(SgdArgs a,
 }
 
 template <int SW>
-void launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
+void launch_solve_sw(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
     size_t lds = solve_lds_bytes(a.nslots, SW);
     if (it.la_ranks > 0) lds = std::max(lds, la_lds_bytes(a.nslots));
     ensure_max_dynamic_lds(reinterpret_cast<const void *>(bs_solve_kernel<SW>));
@@ -1311,50 +1322,18 @@ void launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
 
 }  // namespace
 
-namespace {
-// One status word per device (set by a device-side wait that gave up) and its pinned host copy, refreshed after every
-// block-solve call; like the resident launches' (resident.hip).
-struct BsFault {
-    unsigned *dev_word = nullptr;
-    unsigned *host_word = nullptr;
-};
-std::mutex g_fault_mutex;
-std::vector<BsFault> g_faults;
-
-BsFault &fault_for_current_device() {  // caller holds g_fault_mutex
-    int dev = 0;
-    CU2REC_HIP(hipGetDevice(&dev));
-    if (static_cast<int>(g_faults.size()) <= dev) g_faults.resize(dev + 1);
-    BsFault &f = g_faults[dev];
-    if (!f.dev_word) {
-        CU2REC_HIP(hipMalloc(reinterpret_cast<void **>(&f.dev_word), 128));
-        CU2REC_HIP(hipMemset(f.dev_word, 0, 128));
-        CU2REC_HIP(hipHostMalloc(reinterpret_cast<void **>(&f.host_word), sizeof(unsigned), hipHostMallocDefault));
-        *f.host_word = 0;
-    }
-    return f;
-}
-}  // namespace
-
-// ---- the launch topology of an iteration's fork / join, per device: decided on first use, revisable ------------------------------
-// kBsTopoDevice: gate kernel + device-side join (cross-stream spin waits: they need kernels of the two streams RUNNING SIDE BY SIDE);
-// kBsTopoEvents: events both ways (works wherever HIP works; 5.4 + 2.5-3.3 us per iteration on the main stream).  What decides:
+// ---- the launch topology of an iteration's fork / join, per device (DeviceRuntime::topology): decided on first use, revisable -------
+// kTopologyDevice: gate kernel + device-side join (cross-stream spin waits: they need kernels of the two streams RUNNING SIDE BY SIDE);
+// kTopologyEvents: events both ways (works wherever HIP works; 5.4 + 2.5-3.3 us per iteration on the main stream).  What decides:
 //   1. CU2REC_BS_GATE in the environment (0: events, anything else: device) -- a force, never revised;
 //   2. a counter pass of rocprofv3 (--pmc exports ROCPROF_COUNTER_COLLECTION: kernels are serialised across streams): events;
-//   3. otherwise a two-stream handshake PROBE on the very streams the iterations will use (bs_probe_streams below): a wait kernel queued
+//   3. otherwise a two-stream handshake PROBE on the very streams the iterations will use (probe_streams below): a wait kernel queued
 //      FIRST on one stream, satisfied by a signal kernel queued behind it on the other, bounded by 10 ms -- both directions.  Streams
 //      that share a hardware queue (GPU_MAX_HW_QUEUES=1), a tool that serialises dispatches, a tenant holding the CUs: the waiter times
 //      out, and the process uses events for good;
-//   4. a join that gives up mid-run (bs_check_fault) switches the device to events for every later call, and says so in its error.
+//   4. a join that gives up mid-run (check_faults, device.cpp) switches the device to events for every later call, and says so in its
+//      error.  A wait inside a phase-2 workgroup that gives up (la_wait*: status 2, not 1) leaves the topology as it is.
 namespace {
-struct BsTopology {
-    int mode = -1;  // -1: not decided yet
-    bool forced = false;
-    std::string why = "not decided yet";
-};
-std::mutex g_topo_mutex;
-std::vector<BsTopology> g_topo;  // per device
-
 __global__ void bs_probe_wait_kernel(const unsigned *word, unsigned *result, unsigned long long ticks) {
     if (threadIdx.x != 0) return;
     const unsigned long long t0 = wall_clock64();
@@ -1376,7 +1355,7 @@ __global__ void bs_probe_signal_kernel(unsigned *word) {
 
 // Do kernels of `waiter` and `signaller` run side by side?  The waiter is queued FIRST: if the two streams are served one after the
 // other it can only time out (10 ms), and the signal kernel runs behind it.  Every wave reaches its exit: the wait is bounded.
-bool bs_probe_streams(hipStream_t waiter, hipStream_t signaller, unsigned *scratch) {
+bool probe_streams(hipStream_t waiter, hipStream_t signaller, unsigned *scratch) {
     CU2REC_HIP(hipMemsetAsync(scratch, 0, 64 * sizeof(unsigned), waiter));
     CU2REC_HIP(hipStreamSynchronize(waiter));
     CU2REC_HIP(hipStreamSynchronize(signaller));
@@ -1390,113 +1369,37 @@ bool bs_probe_streams(hipStream_t waiter, hipStream_t signaller, unsigned *scrat
     return result == 1u;
 }
 
-BsTopology &topology_for_current_device() {  // caller holds g_topo_mutex
-    int dev = 0;
-    CU2REC_HIP(hipGetDevice(&dev));
-    if (static_cast<int>(g_topo.size()) <= dev) g_topo.resize(dev + 1);
-    return g_topo[dev];
-}
-}  // namespace
-
-int bs_topology(hipStream_t stream, hipStream_t side) {
-    std::lock_guard<std::mutex> lock(g_topo_mutex);
-    BsTopology &t = topology_for_current_device();
-    if (t.mode >= 0) return t.mode;
+// the topology of the current device (the caller holds device_runtime_mutex()).  The probe runs once per device, on its first block-solve
+// call, under that mutex: check_faults and other devices' first launches wait for it (two bounded waits of 10 ms and the stream
+// synchronisations around them).
+int topology(DeviceRuntime &r, hipStream_t stream, hipStream_t side) {
+    if (r.topology >= 0) return r.topology;
     if (const char *env = std::getenv("CU2REC_BS_GATE")) {
-        t.mode = std::atoi(env) != 0 ? kBsTopoDevice : kBsTopoEvents;
-        t.forced = true;
-        t.why = std::string("CU2REC_BS_GATE=") + env;
-        return t.mode;
+        r.topology = std::atoi(env) != 0 ? DeviceRuntime::kTopologyDevice : DeviceRuntime::kTopologyEvents;
+        r.topology_forced = true;
+        r.topology_why = std::string("CU2REC_BS_GATE=") + env;
+        return r.topology;
     }
     if (const char *pmc = std::getenv("ROCPROF_COUNTER_COLLECTION"))
         if (*pmc && std::string(pmc) != "0" && std::string(pmc) != "False" && std::string(pmc) != "false") {
-            t.mode = kBsTopoEvents;
-            t.why = "a rocprofv3 counter pass (ROCPROF_COUNTER_COLLECTION) serialises kernels across streams";
-            return t.mode;
+            r.topology = DeviceRuntime::kTopologyEvents;
+            r.topology_why = "a rocprofv3 counter pass (ROCPROF_COUNTER_COLLECTION) serialises kernels across streams";
+            return r.topology;
         }
-    unsigned *scratch = nullptr;
-    CU2REC_HIP(hipMalloc(reinterpret_cast<void **>(&scratch), 64 * sizeof(unsigned)));
-    bool forward = false, backward = false;
-    try {
-        forward = bs_probe_streams(stream, side, scratch);
-        backward = forward && bs_probe_streams(side, stream, scratch);
-    } catch (...) {
-        (void)hipFree(scratch);
-        throw;
-    }
-    (void)hipFree(scratch);
+    const bool forward = probe_streams(stream, side, r.probe);
+    const bool backward = forward && probe_streams(side, stream, r.probe);
     if (forward && backward) {
-        t.mode = kBsTopoDevice;
-        t.why = "two-stream handshake probe passed in both directions";
+        r.topology = DeviceRuntime::kTopologyDevice;
+        r.topology_why = "two-stream handshake probe passed in both directions";
     } else {
-        t.mode = kBsTopoEvents;
-        t.why = std::string("two-stream handshake probe: a wait kernel on the ") + (forward ? "side" : "main") +
-                " stream was not reached by the other stream's signal kernel within 10 ms (the streams do not run side by side here)";
+        r.topology = DeviceRuntime::kTopologyEvents;
+        r.topology_why = std::string("two-stream handshake probe: a wait kernel on the ") + (forward ? "side" : "main") +
+                         " stream was not reached by the other stream's signal kernel within 10 ms (the streams do not run side by side here)";
     }
-    return t.mode;
+    return r.topology;
 }
 
-int bs_topology_query(std::string *why) {
-    std::lock_guard<std::mutex> lock(g_topo_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1;
-    }
-    if (dev >= static_cast<int>(g_topo.size())) return -1;
-    if (why) *why = g_topo[dev].why;
-    return g_topo[dev].mode;
-}
-
-unsigned *bs_status_word() {
-    std::lock_guard<std::mutex> lock(g_fault_mutex);
-    return fault_for_current_device().dev_word;
-}
-
-void bs_report_status(hipStream_t stream) {
-    std::lock_guard<std::mutex> lock(g_fault_mutex);
-    BsFault &f = fault_for_current_device();
-    CU2REC_HIP(hipMemcpyAsync(f.host_word, f.dev_word, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-}
-
-void bs_check_fault() {
-    std::lock_guard<std::mutex> lock(g_fault_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    if (dev >= static_cast<int>(g_faults.size()) || !g_faults[dev].host_word) return;
-    BsFault &f = g_faults[dev];
-    if (*static_cast<volatile unsigned *>(f.host_word) != 0) {
-        (void)hipDeviceSynchronize();  // reported once: cleared so that the process can go on
-        (void)hipMemset(f.dev_word, 0, sizeof(unsigned));
-        *f.host_word = 0;
-        // self-healing: whatever kept the launches from running side by side will do so again -- every later block-solve call of
-        // this process on this device forks and joins with events (unless the environment forces the device form)
-        bool switched = false;
-        {
-            std::lock_guard<std::mutex> topo_lock(g_topo_mutex);
-            if (static_cast<int>(g_topo.size()) <= dev) g_topo.resize(dev + 1);
-            if (!g_topo[dev].forced && g_topo[dev].mode != kBsTopoEvents) {
-                g_topo[dev].mode = kBsTopoEvents;
-                g_topo[dev].why = "a device-side join gave up mid-run: switched to the event fork / join";
-                switched = true;
-            }
-        }
-        fail(CU2REC_EHIP,
-             std::string("cu2rec_amd: a block-solve iteration gave up waiting for one of its own launches (the three phases of an iteration "
-                         "run side by side and hand blocks over through flags: is another process or stream holding this GPU's compute "
-                         "units?); the model state is undefined.  ") +
-                 (switched ? "From here on this process forks and joins the iteration's streams with events instead of device-side waits "
-                             "(slower by a few microseconds per iteration, independent of concurrent execution): re-create the model and "
-                             "run again.  "
-                           : "(CU2REC_BS_GATE forces the device-side form: unset it to let the library fall back to events.)  ") +
-                 "CU2REC_SGD_ORDERED is the same result without concurrent launches");
-    }
-}
-
-unsigned long long bs_wait_ticks() {  // CU2REC_BS_WAIT_S (seconds, default 2): the bound of the device-side waits, in ticks of the 100 MHz clock
+unsigned long long wait_ticks() {  // CU2REC_BS_WAIT_S (seconds, default 2): the bound of the device-side waits, in ticks of the 100 MHz clock
     static const unsigned long long ticks = [] {
         double sec = 2.0;
         if (const char *env = std::getenv("CU2REC_BS_WAIT_S")) sec = std::max(0.001, std::atof(env));
@@ -1505,46 +1408,16 @@ unsigned long long bs_wait_ticks() {  // CU2REC_BS_WAIT_S (seconds, default 2): 
     return ticks;
 }
 
-bool bs_supported(int nslots) { return nslots >= 1 && nslots <= kBsMaxSlots; }
-bool bs_lookahead_supported(int nslots) { return la_supported(nslots); }
-
-int bs_compute_units() {
-    static std::mutex mutex;
-    static std::vector<int> cus;  // per device
-    int dev = 0;
-    CU2REC_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mutex);
-    if (static_cast<int>(cus.size()) <= dev) cus.resize(dev + 1, 0);
-    if (!cus[dev]) CU2REC_HIP(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    return cus[dev];
+#ifdef CU2REC_TEST_HOOKS  // fault-path tests only (build/test/libcu2rec_amd_hooks.so): 16 the signal is never sent, 32 the gate can never
+                          // open, 512 phase 3 launched with 3 workgroups (ordered.hip reads 256 itself)
+int dbg() {
+    static const int bits = std::getenv("CU2REC_BS_DBG") ? std::atoi(std::getenv("CU2REC_BS_DBG")) : 0;
+    return bits;
 }
+#else
+constexpr int dbg() { return 0; }
+#endif
 
-void bs_launch_tables(const SgdHyper &h, float *tables, hipStream_t stream) {
-    hipLaunchKernelGGL(bs_tables_kernel, dim3(1), dim3(192), 0, stream, h, tables);
-}
-
-void bs_launch_plan(const uint32_t *keys, int n_active, int n_batch, int n_hot, int item_bits, int max_blocks,
-                    const int *item_of_rank, int *chain_begin, BsChainDesc *chains, BsBlockDesc *blocks, int *walk_begin,
-                    hipStream_t stream, size_t stride) {
-    hipLaunchKernelGGL(bs_plan_kernel, dim3(n_batch), dim3(256), 0, stream, keys, n_active, n_hot, item_bits, max_blocks,
-                       item_of_rank, chain_begin, chains, blocks, walk_begin, stride);
-}
-
-void bs_launch_gram(const SgdArgs &a, const BsIteration &it, hipStream_t stream, hipEvent_t stop) {
-    if (it.n_hot <= 0 || it.max_blocks <= 0) return;
-    size_t gram_lds = std::max(static_cast<size_t>(kB) * (a.nslots | 1) * 16, static_cast<size_t>(5) * kH * kMS * 4) +
-                      static_cast<size_t>(kGramTabFloats + kB) * 4;
-    if (it.la_ranks > 0) gram_lds = std::max(gram_lds, static_cast<size_t>(2) * kB * (a.nslots | 1) * 16);  // (the cross blocks' workgroups: two blocks' rows)
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(bs_gram_kernel));
-    // `stop`: an event completed by the kernel's own completion signal (hipExtLaunchKernelGGL) -- a hipEventRecord behind the
-    // launch is a marker packet of its own and held the NEXT launch of the stream back by 6-7 us (kernel traces, round 3)
-    const int grid = it.max_blocks + (it.la_ranks > 0 ? it.la_grid : 0);
-    if (stop) hipExtLaunchKernelGGL(bs_gram_kernel, dim3(grid), dim3(256), static_cast<uint32_t>(gram_lds), stream, nullptr, stop, 0, a, it);
-    else hipLaunchKernelGGL(bs_gram_kernel, dim3(grid), dim3(256), gram_lds, stream, a, it);
-    CU2REC_HIP(hipGetLastError());
-}
-
-namespace {
 // A gate that gives up just ENDS (the side kernel then starts a little early: a matter of timing, no data hangs on it): it must not
 // set the status word -- that would declare the model state undefined for a delay that harms nothing.
 __global__ void bs_gate_kernel(const unsigned long long *count, unsigned long long target, const unsigned long long *started,
@@ -1564,43 +1437,268 @@ __global__ void bs_gate_kernel(const unsigned long long *count, unsigned long lo
         if ((++polls & 63u) == 0 && wall_clock64() - t0 > wait_ticks) break;
     }
 }
-}  // namespace
 
-namespace {
+// one thread that stores `value` to `word`: queued behind a kernel, it announces that kernel's completion
 __global__ void bs_signal_kernel(unsigned long long *word, unsigned long long value) {
     if (threadIdx.x == 0) __hip_atomic_store(word, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-}  // namespace
 
-void bs_launch_signal(unsigned long long *word, unsigned long long value, hipStream_t stream) {
-    hipLaunchKernelGGL(bs_signal_kernel, dim3(1), dim3(64), 0, stream, word, value);
+// Phase 1.  `stop`: an event completed by the kernel's own completion signal (hipExtLaunchKernelGGL) -- a hipEventRecord behind the
+// launch is a marker packet of its own and held the NEXT launch of the stream back by 6-7 us (kernel traces, round 3)
+void launch_gram(const SgdArgs &a, const BsIteration &it, hipStream_t stream, hipEvent_t stop) {
+    size_t gram_lds = std::max(static_cast<size_t>(kB) * (a.nslots | 1) * 16, static_cast<size_t>(5) * kH * kMS * 4) +
+                      static_cast<size_t>(kGramTabFloats + kB) * 4;
+    if (it.la_ranks > 0) gram_lds = std::max(gram_lds, static_cast<size_t>(2) * kB * (a.nslots | 1) * 16);  // (the cross blocks' workgroups: two blocks' rows)
+    ensure_max_dynamic_lds(reinterpret_cast<const void *>(bs_gram_kernel));
+    const int grid = it.max_blocks + (it.la_ranks > 0 ? it.la_grid : 0);
+    if (stop) hipExtLaunchKernelGGL(bs_gram_kernel, dim3(grid), dim3(256), static_cast<uint32_t>(gram_lds), stream, nullptr, stop, 0, a, it);
+    else hipLaunchKernelGGL(bs_gram_kernel, dim3(grid), dim3(256), gram_lds, stream, a, it);
     CU2REC_HIP(hipGetLastError());
 }
 
-void bs_launch_gate(const unsigned long long *count, unsigned long long target, const unsigned long long *started,
-                    unsigned long long started_target, hipStream_t stream) {
-    hipLaunchKernelGGL(bs_gate_kernel, dim3(1), dim3(64), 0, stream, count, target, started, started_target, bs_wait_ticks());
-    CU2REC_HIP(hipGetLastError());
-}
-
-void bs_launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
-    if (it.n_hot <= 0 || it.max_blocks <= 0) return;
+// Phase 2: one workgroup per hot chain
+void launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
     const int sw = (a.nslots + 3) / 4;
-    if (sw <= 1) launch_solve<1>(a, it, stream);
-    else if (sw <= 2) launch_solve<2>(a, it, stream);
-    else if (sw <= 4) launch_solve<4>(a, it, stream);
-    else if (sw <= 7) launch_solve<7>(a, it, stream);
-    else if (sw <= 8) launch_solve<8>(a, it, stream);
-    else if (sw <= 12) launch_solve<12>(a, it, stream);
-    else if (sw <= 16) launch_solve<16>(a, it, stream);
+    if (sw <= 1) launch_solve_sw<1>(a, it, stream);
+    else if (sw <= 2) launch_solve_sw<2>(a, it, stream);
+    else if (sw <= 4) launch_solve_sw<4>(a, it, stream);
+    else if (sw <= 7) launch_solve_sw<7>(a, it, stream);
+    else if (sw <= 8) launch_solve_sw<8>(a, it, stream);
+    else if (sw <= 12) launch_solve_sw<12>(a, it, stream);
+    else if (sw <= 16) launch_solve_sw<16>(a, it, stream);
     else fail(CU2REC_EUNSUPPORTED, "block-solve mode is compiled for n_factors <= 252");
 }
 
-void bs_launch_update(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
-    if (it.n_hot <= 0 || it.max_blocks <= 0) return;
+// Phase 3: launch_blocks workgroups, and one more that waits for the side kernel when side_seq is set
+void launch_update(const SgdArgs &a, const BsIteration &it, hipStream_t stream) {
     const int nwaves = (4 * a.nslots + 63) / 64;
     hipLaunchKernelGGL(bs_update_kernel, dim3(it.launch_blocks + (it.side_seq ? 1 : 0)), dim3(64 * nwaves), 0, stream, a, it);
     CU2REC_HIP(hipGetLastError());
+}
+
+std::atomic<int> g_lookahead{-1};  // -1: not yet initialised from the environment
+// explicit threshold (> 0), or <= 0: automatic (240 per 131,072 rating users, scaled with the set); -2 = not yet initialised
+// from the environment
+std::atomic<float> g_min_rate{-2.f};
+constexpr float kDefaultRate = 240.f;
+
+float min_rate_state() {
+    float cur = g_min_rate.load();
+    if (cur == -2.f) {  // first use: CU2REC_BLOCKSOLVE_RATE overrides the automatic threshold
+        float init = -1.f;
+        if (const char *env = std::getenv("CU2REC_BLOCKSOLVE_RATE")) init = std::max(0.01f, static_cast<float>(std::atof(env)));
+        g_min_rate.compare_exchange_strong(cur, init);
+        cur = g_min_rate.load();
+    }
+    return cur;
+}
+}  // namespace
+
+int blocksolve_lookahead_blocks(int blocks) {
+    int prev = g_lookahead.load();
+    if (prev < 0) {
+        const char *env = std::getenv("CU2REC_BLOCKSOLVE_LOOKAHEAD");
+        const int init = env ? std::max(0, std::atoi(env)) : 24;  // the top chains only: DESIGN.md section 4, "The look-ahead form"
+        g_lookahead.compare_exchange_strong(prev, init);
+        prev = g_lookahead.load();
+    }
+    if (blocks >= 0) g_lookahead.store(blocks);
+    return prev;
+}
+
+// rate > 0: explicit threshold; rate < 0: back to automatic; rate == 0: query.  Returns what was in force before the call:
+// the explicit value, or -1 for automatic -- so that f(f(x)) restores either state.
+float blocksolve_min_rate(float rate) {
+    const float prev = min_rate_state();
+    if (rate > 0.f) g_min_rate.store(rate);
+    else if (rate < 0.f) g_min_rate.store(-1.f);
+    return prev > 0.f ? prev : -1.f;
+}
+
+int blocksolve_hot_items(const std::vector<double> &rate, int n_active, int rank_limit) {
+    // the threshold: what the caller set, else scaled with the set -- down (a long chain costs the same whatever the set,
+    // the launch overhead it has to beat does not shrink with it; 1/1 .. 1/8 of the ML-20M shape,
+    // profiles/r02_shard_size_probe_blocksolve.log) and up (Netflix shape, 480,189 users: 290 us per iteration at 800
+    // against 353 at 240 -- the chains of several hundred hot items do not fit the CUs at once)
+    const float state = min_rate_state();
+    float min_rate = state > 0.f ? state : kDefaultRate;
+    const int n_cols = static_cast<int>(rate.size());
+    if (state <= 0.f) {
+        min_rate = std::max(30.f, min_rate * static_cast<float>(n_active) / 131072.f);
+        // a small set (one GPU's shard of a strong-scaling run): with the hottest item between 150 and 350 expected updates per
+        // iteration a threshold of 60 still pays a little (an eighth of the ML-20M shape, hottest item 247: 32.5 us per iteration
+        // against 35.3 walking everything; thresholds 40 / 60 / 90 / 130 / 180: 32.6 / 32.5 / 33.7 / 37.5 / 41.4, round 5); below
+        // that no chain is long enough to pay for three launches per iteration and the mode IS the ordered walk (ML-1M shape)
+        // Only for SMALL sets (at most a quarter of 131,072 users: where the rule was measured).  A large set with flat popularity --
+        // many users, hottest item under 350 -- keeps the scaled threshold: there "every item above 60" would be hundreds of
+        // 512-thread solve workgroups the side stream's gate has to see started (the regime that did not fit the CUs on the
+        // Netflix shape), and nothing was measured there.
+        if (n_cols > 0 && n_active <= 131072 / 4 && rate[0] < 350.0) min_rate = rate[0] >= 150.0 ? 60.f : std::numeric_limits<float>::infinity();
+    }
+    int n = 0;
+    while (n < n_cols && rate[n] >= min_rate) ++n;
+    return std::min(n, rank_limit);
+}
+
+BlockSolve::BlockSolve(int n_hot_, const std::vector<double> &rate, double hot_rate, int n_active_, int item_bits_, int max_batch_,
+                       const int *item_of_rank_)
+    : n_hot(n_hot_), n_active(n_active_), item_bits(item_bits_), max_batch(max_batch_), item_of_rank(item_of_rank_) {
+    max_blocks = n_active / kBsLinks + n_hot + 1;
+    // Blocks of 64 links an iteration's hot chains are expected to fill, as a bound that holds in all but astronomically rare iterations
+    // (the hot links' count: mean hot_rate, variance at most the mean; one partial block per chain): what phase 3 is launched with.  Its
+    // workgroups stride through the dense block table, so an iteration beyond the bound is still done completely.
+    const double bound = (hot_rate + 8.0 * std::sqrt(hot_rate) + 64.0) / kBsLinks + n_hot + 1;
+    launch_blocks = std::max(1, bound >= static_cast<double>(max_blocks) ? max_blocks : static_cast<int>(bound));
+    if (dbg() & 512) launch_blocks = std::min(3, max_blocks);  // (a launch far too small: every workgroup strides over many blocks)
+    // the look-ahead form of phase 2: the leading ranks whose chains are expected to be at least blocksolve_lookahead_blocks() blocks
+    // long -- the chains whose length is the iteration's critical path.  Their blocks are the first of every iteration's block table;
+    // la_cap bounds them with room to spare (a chain beyond it: the plain form).
+    const int la_min = blocksolve_lookahead_blocks(-1);
+    double la_blocks = 0.0;
+    while (la_min > 0 && la_ranks < n_hot && rate[la_ranks] >= static_cast<double>(la_min) * kBsLinks) {
+        la_blocks += std::ceil(rate[la_ranks] / kBsLinks) + 1.0;
+        ++la_ranks;
+    }
+    if (la_ranks > 0) la_cap = std::min(max_blocks, static_cast<int>(la_blocks * 1.25) + 4 * la_ranks + 8);
+    for (int slot = 0; slot < 2; ++slot) {
+        chain_begin[slot].allocate(static_cast<size_t>(max_batch) * (n_hot + 1));
+        walk_begin[slot].allocate(max_batch);
+        chains[slot].allocate(static_cast<size_t>(max_batch) * n_hot);
+        blocks[slot].allocate(static_cast<size_t>(max_batch) * max_blocks);
+    }
+    tables.allocate(kBsTableFloats);
+    Mbuf.allocate(static_cast<size_t>(max_blocks) * kBsRecFloats);
+    ebuf.allocate(static_cast<size_t>(max_blocks) * kBsLinks);
+    solve_started.allocate(16);
+    solve_started.zero();
+    gram_done.allocate(32 * 16);
+    gram_done.zero();
+    side_seq.allocate(16);
+    side_seq.zero();
+    if (la_cap > 0) Nbuf.allocate(static_cast<size_t>(la_cap) * kBsCrossFloats);
+}
+
+BlockSolve::~BlockSolve() {  // (the schedule has waited for its last call's end)
+    if (upd) (void)hipStreamDestroy(upd);
+    for (hipEvent_t e : {ev_call, ev_upd, ev_gram})
+        if (e) (void)hipEventDestroy(e);
+}
+
+void BlockSolve::plan(int slot, const uint32_t *sk, int nb, size_t stride, hipStream_t sched) {
+    hipLaunchKernelGGL(bs_plan_kernel, dim3(nb), dim3(256), 0, sched, sk, n_active, n_hot, item_bits, max_blocks, item_of_rank,
+                       chain_begin[slot].ptr, chains[slot].ptr, blocks[slot].ptr, walk_begin[slot].ptr, stride);
+}
+
+void BlockSolve::begin(const SgdArgs &a, hipStream_t stream) {
+    if (a.nslots < 1 || a.nslots > kBsMaxSlots) fail(CU2REC_EUNSUPPORTED, "block-solve mode is compiled for n_factors <= 252");
+    const bool same = tables_valid && tables_for.lr == a.h.lr && tables_for.q_reg == a.h.q_reg && tables_for.ib_reg == a.h.ib_reg;
+    if (!same) {  // stream ordered: kernels already queued keep the old tables
+        hipLaunchKernelGGL(bs_tables_kernel, dim3(1), dim3(192), 0, stream, a.h, tables.ptr);
+        tables_for = a.h;
+        tables_valid = true;
+    }
+    if (qstart_ld != a.ldq) {
+        CU2REC_HIP(hipStreamSynchronize(stream));
+        qstart.allocate(static_cast<size_t>(max_blocks) * a.ldq);
+        qstart_ld = a.ldq;
+    }
+    if (!upd) {
+        // default priority: a high-priority queue whose workgroups cannot all be placed (more hot chains than CUs) held back
+        // the queues below it (a 300-chain test set ran into the waits' timeout)
+        CU2REC_HIP(hipStreamCreateWithFlags(&upd, hipStreamNonBlocking));
+        for (hipEvent_t *e : {&ev_call, &ev_upd, &ev_gram}) CU2REC_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    }
+    unsigned *status = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(device_runtime_mutex());
+        DeviceRuntime &r = device_runtime();
+        device_join = topology(r, stream, upd) == DeviceRuntime::kTopologyDevice;
+        status = r.status + DeviceRuntime::kBlocksolveWord;
+        host_status = r.host_status + 1;
+    }
+    // the side stream starts behind everything the caller has queued so far
+    CU2REC_HIP(hipEventRecord(ev_call, stream));
+    CU2REC_HIP(hipStreamWaitEvent(upd, ev_call, 0));
+    const bool la_on = la_ranks > 0 && la_supported(a.nslots);  // (rows the rings have LDS for)
+    it = BsIteration{};
+    it.n_active = n_active;
+    it.n_hot = n_hot;
+    it.item_mask = (1u << item_bits) - 1u;
+    it.item_of_rank = item_of_rank;
+    it.tables = tables.ptr;
+    it.log2a = static_cast<float>(std::log2(1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.q_reg)));
+    it.log2c = static_cast<float>(std::log2(1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.ib_reg)));
+    it.Mbuf = Mbuf.ptr;
+    it.ebuf = ebuf.ptr;
+    it.qstart = qstart.ptr;
+    it.max_blocks = max_blocks;
+    it.launch_blocks = launch_blocks;
+    it.la_ranks = la_on ? la_ranks : 0;
+    it.la_cap = la_cap;
+    it.la_grid = la_on ? la_cap : 0;
+    it.Nbuf = Nbuf.ptr;
+    it.status = status;
+    it.solve_started = solve_started.ptr;
+    it.wait_ticks = wait_ticks();
+    if (device_join) {
+        it.gram_done = gram_done.ptr;
+        it.side_seq = side_seq.ptr;
+    }
+    upd_pending = false;
+}
+
+// One iteration = four launches: `stream`: phase 1 (bs_gram_kernel: every block's inverse factor) -> phase 2 (bs_solve_kernel: one
+// workgroup per chain) -> phase 3 (bs_update_kernel: the user side); side stream `upd`: the other items' chains (two-wave form / walk),
+// forked behind phase 1 -- beside it their thousands of workgroups take the CUs from phase 1's (measured: 71 instead of 19 us) -- and
+// joined in front of the next phase 1, which reads rows they write.  Host order gram, solve, [gate], side, [signal], update: every
+// launch behind what it waits for (streams sharing a hardware queue serialise, they cannot wait for each other).
+//  * device_join (kTopologyDevice), no event on the main stream: phase 1's workgroups count themselves through, phase 2's count
+//    themselves in, ONE wavefront queued in front of the side kernel (bs_gate_kernel) ends when both counts have reached what the host
+//    has launched so far; a signal kernel behind the side kernel stores the iteration's number and one extra workgroup of phase 3's
+//    launch waits for it.  (The host's counts move only behind a launch that succeeded: a launch that throws leaves gate and counters
+//    in step for the calls that follow.)
+//  * events (kTopologyEvents): fork on phase 1's completion signal, join by an event wait in front of the next phase 1 (5.4 + 2.5-3.3 us
+//    per iteration on the main stream: DESIGN.md section 4).
+void BlockSolve::iteration(const SgdArgs &a, int slot, int b, const uint32_t *keys, const uint64_t *vals, bool last, hipStream_t stream,
+                           const SideChains &side) {
+    it.keys = keys;
+    it.vals = vals;
+    it.chains = chains[slot].ptr + static_cast<size_t>(b) * n_hot;
+    it.blocks = blocks[slot].ptr + static_cast<size_t>(b) * max_blocks;
+    it.walk_begin = walk_begin[slot].ptr + b;
+    it.side_target = device_join ? side_seq_host + 1 : 0;
+    if (upd_pending) CU2REC_HIP(hipStreamWaitEvent(stream, ev_upd, 0));  // (events) join: rows the next phase 1 reads
+    launch_gram(a, it, stream, device_join ? nullptr : ev_gram);
+    if (device_join) gram_done_target += static_cast<unsigned long long>(max_blocks + it.la_grid);
+    else CU2REC_HIP(hipStreamWaitEvent(upd, ev_gram, 0));
+    launch_solve(a, it, stream);
+    if (device_join) {
+        started_total += static_cast<unsigned long long>(n_hot);
+        hipLaunchKernelGGL(bs_gate_kernel, dim3(1), dim3(64), 0, upd, gram_done.ptr, gram_done_target + ((dbg() & 32) ? (1ull << 40) : 0ull),
+                           solve_started.ptr, started_total, it.wait_ticks);
+        CU2REC_HIP(hipGetLastError());
+    }
+    // (device_join: only the batch's last side kernel carries the event the main stream waits for at the END of the batch -- an event on
+    // a kernel's completion signal holds the next packet of its queue back, here the signal kernel: 5.4 us)
+    side(upd, !device_join || last ? ev_upd : nullptr);
+    if (device_join) {
+        ++side_seq_host;
+        if (!(dbg() & 16)) {
+            hipLaunchKernelGGL(bs_signal_kernel, dim3(1), dim3(64), 0, upd, side_seq.ptr, side_seq_host);
+            CU2REC_HIP(hipGetLastError());
+        }
+    }
+    launch_update(a, it, stream);
+    upd_pending = !device_join;
+}
+
+void BlockSolve::join(hipStream_t stream) {
+    CU2REC_HIP(hipStreamWaitEvent(stream, ev_upd, 0));
+    upd_pending = false;
+}
+
+void BlockSolve::end(hipStream_t stream) {  // (every batch ended with `stream` behind the side stream)
+    CU2REC_HIP(hipMemcpyAsync(host_status, it.status, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
 }
 
 }  // namespace cu2rec

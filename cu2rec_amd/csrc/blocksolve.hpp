@@ -2,13 +2,15 @@
 // (mf_sequential.cu:102-143) with the long item chains solved block-wise; see blocksolve.hip.
 #pragma once
 
-#include <string>
+#include <functional>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 
+#include "hip_check.hpp"
 #include "kernels.hpp"
 
 namespace cu2rec {
@@ -52,7 +54,7 @@ struct BsIteration {
     float *qstart;            // [max_blocks][ldq]           item row at the start of each block
     int max_blocks;
     // workgroups phase 3 is LAUNCHED with (<= max_blocks; phase 1 keeps the full grid: blocksolve.hip): what an iteration is expected to have, mean + 8 sigma of the hot links
-    // (OrderedSchedule::blocks_bound); the block table is dense and the workgroups stride through it, so a busier iteration is still
+    // (BlockSolve's constructor); the block table is dense and the workgroups stride through it, so a busier iteration is still
     // done completely
     int launch_blocks;
     // Look-ahead chains (blocksolve.hip, "look-ahead form"): popularity ranks [0, la_ranks) -- the long chains, whose length IS the
@@ -63,8 +65,8 @@ struct BsIteration {
     int la_grid;              // workgroups of phase 1's launch that build the cross blocks
     float *Nbuf;              // [la_cap][kBsCrossFloats]
     unsigned *status;                 // [1] set by a wait that gave up (bounded spins); the host reports it
-    // Fork and join of the side stream without events (ordered.hip): phase 1's workgroups count themselves through and phase 2's
-    // count themselves in -- ONE wavefront queued in front of the side kernel (bs_launch_gate) ends when both counts have reached
+    // Fork and join of the side stream without events (BlockSolve::iteration): phase 1's workgroups count themselves through and phase 2's
+    // count themselves in -- ONE wavefront queued in front of the side kernel (bs_gate_kernel) ends when both counts have reached
     // what the host has launched so far (timing only, no data behind it); a signal kernel behind the side kernel stores the
     // iteration's number, and one extra workgroup of phase 3's launch waits for it (data: the next phase 1 reads rows the side kernel
     // writes).
@@ -72,36 +74,68 @@ struct BsIteration {
     const unsigned long long *side_seq;  // (or null) the word the signal kernel sets ...
     unsigned long long side_target;      // ... and the number the extra workgroup of phase 3's launch waits for
     unsigned long long *gram_done;       // [32 x 16]  phase-1 workgroups through (32 shards, 128 bytes apart), over all iterations so far (or null)
-    unsigned long long wait_ticks;    // bound of the device-side waits (bs_wait_ticks(): CU2REC_BS_WAIT_S, 2 s), 100 MHz ticks
+    unsigned long long wait_ticks;    // bound of the device-side waits (CU2REC_BS_WAIT_S, 2 s), 100 MHz ticks
 };
 
-unsigned long long bs_wait_ticks();
-bool bs_supported(int nslots);
-bool bs_lookahead_supported(int nslots);  // rows of at most 31 float4 slots: the look-ahead form's rings fit the LDS
-int bs_compute_units();       // of the current device
-// bounded device-side waits report through one status word per device: its address, an asynchronous refresh of the host copy
-// behind a call's launches, and the check (throws CU2REC_EHIP once if a wait gave up)
-unsigned *bs_status_word();
-void bs_report_status(hipStream_t stream);
-void bs_check_fault();
-// the fork / join topology of this device's iterations (blocksolve.hip, "the launch topology"): decided on first use -- environment,
-// counter pass, or a two-stream handshake probe on the iterations' own streams -- and switched to events by a join that gave up
-constexpr int kBsTopoEvents = 0, kBsTopoDevice = 2;
-int bs_topology(hipStream_t stream, hipStream_t side);
-int bs_topology_query(std::string *why);  // -1: not decided yet
-void bs_launch_tables(const SgdHyper &h, float *tables, hipStream_t stream);
-// one workgroup per iteration of the batch: chain and block descriptors
-void bs_launch_plan(const uint32_t *keys, int n_active, int n_batch, int n_hot, int item_bits, int max_blocks,
-                    const int *item_of_rank, int *chain_begin, BsChainDesc *chains, BsBlockDesc *blocks, int *walk_begin,
-                    hipStream_t stream, size_t stride);
-// the three phases of one iteration's hot chains: three launches queued one behind the other on one stream
-void bs_launch_gram(const SgdArgs &a, const BsIteration &it, hipStream_t stream, hipEvent_t stop = nullptr);
-void bs_launch_solve(const SgdArgs &a, const BsIteration &it, hipStream_t stream);
-// one wavefront that ends once `count` has reached `target` (bounded): queued in front of a kernel that should not start before then
-// one thread that stores `value` to `word` (write-through): queued behind a kernel, it announces that kernel's completion
-void bs_launch_signal(unsigned long long *word, unsigned long long value, hipStream_t stream);
-void bs_launch_gate(const unsigned long long *count, unsigned long long target, const unsigned long long *started,
-                    unsigned long long started_target, hipStream_t stream);
-void bs_launch_update(const SgdArgs &a, const BsIteration &it, hipStream_t stream);
+// minimum expected updates per iteration of an item for block-wise treatment (process-wide; schedules created later)
+// rate > 0 sets it, rate < 0 returns to automatic (scaled with the set), 0 queries; returns the explicit value in force before
+// the call or -1 for automatic
+float blocksolve_min_rate(float rate);
+// chains EXPECTED to be at least this many blocks of 64 links long run phase 2 in the look-ahead form (default 24: the top chains; 0: none;
+// schedules created later); blocks < 0 only queries
+int blocksolve_lookahead_blocks(int blocks);
+// popularity ranks [0, n) that are solved block-wise, n <= rank_limit (rate: expected updates per iteration of the items by rank)
+int blocksolve_hot_items(const std::vector<double> &rate, int n_active, int rank_limit);
+
+// The host side of the block-solve mode for one ordered schedule (ordered.hip), which samples and sorts the iterations: the buffers of the
+// three phases, the plan of every scheduled iteration, the side stream the other items' chains run on, and the launch sequence.
+class BlockSolve {
+public:
+    // ranks [0, n_hot) are solved block-wise; hot_rate = rate[0] + ... + rate[n_hot - 1]; keys carry the rank in item_bits bits
+    BlockSolve(int n_hot, const std::vector<double> &rate, double hot_rate, int n_active, int item_bits, int max_batch,
+               const int *item_of_rank);
+    ~BlockSolve();
+    BlockSolve(const BlockSolve &) = delete;
+    BlockSolve &operator=(const BlockSolve &) = delete;
+    // schedule slot `slot` now holds nb sorted iterations (their keys `sk`, `stride` apart): queues their chain and block tables on `sched`
+    void plan(int slot, const uint32_t *sk, int nb, size_t stride, hipStream_t sched);
+    // A call's start: decay tables, scratch, the side stream (behind everything queued on `stream` so far) and the fork / join topology.
+    void begin(const SgdArgs &a, hipStream_t stream);
+    // One iteration (a.iter0): the plan of iteration `b` of slot `slot`, its sorted keys and values.  `side` launches the other items'
+    // chains on the stream it is given, with `stop` (or null) riding on their completion.  last: the last iteration of the batch.
+    using SideChains = std::function<void(hipStream_t side, hipEvent_t stop)>;
+    void iteration(const SgdArgs &a, int slot, int b, const uint32_t *keys, const uint64_t *vals, bool last, hipStream_t stream,
+                   const SideChains &side);
+    void join(hipStream_t stream);  // the batch's end: `stream` waits for the side stream
+    void end(hipStream_t stream);   // the call's end: refreshes the host copy of the status word
+
+    const int n_hot;
+
+private:
+    int n_active, item_bits, max_batch;
+    const int *item_of_rank;
+    int max_blocks;     // blocks of 64 links (kBsLinks) per iteration, upper bound
+    int launch_blocks;  // workgroups phase 3 is launched with (BsIteration::launch_blocks)
+    int la_ranks = 0;   // ranks [0, la_ranks): phase 2 in the look-ahead form; their blocks lie below la_cap
+    int la_cap = 0;
+    // per schedule slot, per iteration: the plan (bs_plan_kernel)
+    DeviceBuffer<int> chain_begin[2], walk_begin[2];
+    DeviceBuffer<BsChainDesc> chains[2];
+    DeviceBuffer<BsBlockDesc> blocks[2];
+    DeviceBuffer<float> tables, Mbuf, ebuf, qstart, Nbuf;  // Nbuf: [la_cap][kBsCrossFloats] the cross blocks of the look-ahead chains
+    int qstart_ld = 0;
+    SgdHyper tables_for{};  // hyper-parameters the decay tables were computed from
+    bool tables_valid = false;
+    // Fork and join without events (blocksolve.hip, "the launch topology"): what phase 1's and phase 2's workgroups count, what the host
+    // has launched so far, and the number of the last iteration whose side kernel is complete (the signal kernel's word)
+    DeviceBuffer<unsigned long long> solve_started, gram_done, side_seq;
+    unsigned long long gram_done_target = 0, started_total = 0, side_seq_host = 0;
+    hipStream_t upd = nullptr;
+    hipEvent_t ev_call = nullptr, ev_upd = nullptr, ev_gram = nullptr;
+    BsIteration it{};       // the call's launch arguments; iteration() sets the fields of one iteration
+    bool device_join = false;
+    bool upd_pending = false;  // (event join) a side kernel of this batch has not been waited for yet
+    unsigned *host_status = nullptr;
+};
 
 }  // namespace cu2rec

@@ -5,6 +5,9 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <map>
+#include <mutex>
+#include <string>
 #include <vector>
 
 #include "device.hpp"
@@ -14,10 +17,91 @@
 
 namespace cu2rec {
 
-// what a persistent / concurrent launch could not finish is reported at the next entry point (resident.hip, blocksolve.hip)
+namespace {
+std::mutex g_runtime_mutex;
+std::map<int, DeviceRuntime> g_runtime;  // per device (a map: references stay valid while other devices are added)
+}  // namespace
+
+std::mutex &device_runtime_mutex() { return g_runtime_mutex; }
+
+DeviceRuntime &device_runtime() {
+    int dev = 0;
+    CU2REC_HIP(hipGetDevice(&dev));
+    DeviceRuntime &r = g_runtime[dev];
+    if (r.status) return r;
+    unsigned *words = nullptr, *host = nullptr;
+    try {
+        CU2REC_HIP(hipDeviceGetAttribute(&r.cus, hipDeviceAttributeMultiprocessorCount, dev));
+        CU2REC_HIP(hipMalloc(reinterpret_cast<void **>(&words), 128 * sizeof(unsigned)));
+        CU2REC_HIP(hipMemset(words, 0, 128 * sizeof(unsigned)));
+        CU2REC_HIP(hipHostMalloc(reinterpret_cast<void **>(&host), 2 * sizeof(unsigned), hipHostMallocDefault));
+    } catch (...) {  // (nothing kept: the next use tries again)
+        if (words) (void)hipFree(words);
+        throw;
+    }
+    host[0] = host[1] = 0;
+    r.host_status = host;
+    r.probe = words + 64;
+    r.status = words;
+    return r;
+}
+
+namespace {
+// the current device's record if it has one (the caller holds g_runtime_mutex); no allocation, no error
+DeviceRuntime *existing_device_runtime() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    const auto found = g_runtime.find(dev);
+    return found != g_runtime.end() && found->second.status ? &found->second : nullptr;
+}
+}  // namespace
+
+// What a persistent or concurrent launch could not finish is reported at the next entry point, once: the words are cleared so that
+// the process can go on.
 static void check_faults() {
-    resident_check_fault();
-    bs_check_fault();
+    std::lock_guard<std::mutex> lock(g_runtime_mutex);
+    DeviceRuntime *found = existing_device_runtime();
+    if (!found) return;
+    DeviceRuntime &r = *found;
+    volatile unsigned *host = r.host_status;
+    if (host[0] != 0) {
+        (void)hipDeviceSynchronize();
+        (void)hipMemset(r.status + DeviceRuntime::kResidentWord, 0, sizeof(unsigned));
+        host[0] = 0;
+        fail(CU2REC_EHIP,
+             "cu2rec_amd: a persistent SGD launch gave up at its grid barrier (the grid was not co-resident: is another "
+             "process or stream using this GPU?); the model state is undefined.  cu2rec_hogwild_resident(0) / "
+             "CU2REC_RESIDENT=0 selects the one-launch-per-iteration Hogwild kernel");
+    }
+    const unsigned bs = host[1];
+    if (bs == 0) return;
+    (void)hipDeviceSynchronize();
+    (void)hipMemset(r.status + DeviceRuntime::kBlocksolveWord, 0, sizeof(unsigned));
+    host[1] = 0;
+    const char *ordered = "CU2REC_SGD_ORDERED is the same result without concurrent launches";
+    if (bs == 2u)  // a look-ahead ring wait (blocksolve.hip, la_wait*): the fork / join had no part in it
+        fail(CU2REC_EHIP, std::string("cu2rec_amd: a block-solve iteration gave up at a wait inside a phase-2 workgroup (its wavefronts hand "
+                                      "blocks over through flags: is another process or stream holding this GPU's compute units?); the "
+                                      "model state is undefined.  ") + ordered);
+    // the join gave up.  Self-healing: whatever kept the launches from running side by side will do so again -- every later block-solve
+    // call of this process on this device forks and joins with events (unless the environment forces the device form)
+    std::string what;
+    if (r.topology_forced) {
+        what = "(CU2REC_BS_GATE forces the device-side form: unset it to let the library fall back to events.)  ";
+    } else if (r.topology == DeviceRuntime::kTopologyEvents) {
+        what = "This process already forks and joins the iteration's streams with events.  ";
+    } else {
+        r.topology = DeviceRuntime::kTopologyEvents;
+        r.topology_why = "a device-side join gave up mid-run: switched to the event fork / join";
+        what = "From here on this process forks and joins the iteration's streams with events instead of device-side waits (slower by a "
+               "few microseconds per iteration, independent of concurrent execution): re-create the model and run again.  ";
+    }
+    fail(CU2REC_EHIP, "cu2rec_amd: a block-solve iteration gave up waiting for one of its own launches (the three phases of an iteration "
+                      "run side by side and hand blocks over through flags: is another process or stream holding this GPU's compute "
+                      "units?); the model state is undefined.  " + what + ordered);
 }
 
 
@@ -610,7 +694,14 @@ int cu2rec_blocksolve_lookahead_blocks(int blocks) { return blocksolve_lookahead
 
 int cu2rec_blocksolve_topology(char *why, size_t cap) {
     std::string text;
-    const int mode = bs_topology_query(&text);
+    int mode = -1;
+    {
+        std::lock_guard<std::mutex> lock(g_runtime_mutex);
+        if (const DeviceRuntime *r = existing_device_runtime()) {
+            mode = r->topology;
+            text = r->topology_why;
+        }
+    }
     if (why && cap) {
         const size_t n = std::min(text.size(), cap - 1);
         std::memcpy(why, text.data(), n);
@@ -628,7 +719,7 @@ int cu2rec_csr_blocksolve_items(const cu2rec_csr *train) {
             m.schedule.reset(new OrderedSchedule(m.indptr.ptr, m.indices.ptr, m.rows, m.cols, m.nnz));
             m.schedule->speculate = true;
         }
-        n = m.schedule->n_hot_bs;
+        n = m.schedule->blocksolve_items();
     });
     return rc == CU2REC_OK ? n : -1;
 }

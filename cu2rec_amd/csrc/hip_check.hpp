@@ -6,6 +6,7 @@
 #include <mutex>
 #include <set>
 #include <sstream>
+#include <string>
 #include <utility>
 
 #include "common.hpp"
@@ -44,6 +45,26 @@ inline void ensure_max_dynamic_lds(const void *kernel, int bytes = 160 * 1024) {
     CU2REC_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     done.insert({dev, kernel});
 }
+
+// What the launch paths keep per device (device.cpp), created on first use and never freed.  Bounded device-side waits that give
+// up set a status word; the host copy is refreshed behind the launches (resident.hip: every resident launch; blocksolve.hip: the
+// end of every block-solve call) and check_faults() reports and clears it at the next entry point.
+struct DeviceRuntime {
+    static constexpr int kResidentWord = 0, kBlocksolveWord = 32;  // indices into `status` (each word on a 128-byte line of its own)
+    int cus = 0;                      // compute units
+    unsigned *status = nullptr;       // device: the status words, then 64 words of scratch for the topology probe (`probe`)
+    unsigned *probe = nullptr;
+    unsigned *host_status = nullptr;  // pinned: [0] the resident word, [1] the block-solve word
+    // the block-solve fork / join topology (blocksolve.hip, "the launch topology"; the values are cu2rec_blocksolve_topology's): -1 until
+    // the first block-solve call decides it
+    static constexpr int kTopologyEvents = 0, kTopologyDevice = 2;
+    int topology = -1;
+    bool topology_forced = false;  // by CU2REC_BS_GATE: never revised
+    std::string topology_why = "not decided yet";
+};
+// The current device's record; the caller holds device_runtime_mutex(), which guards every record.
+std::mutex &device_runtime_mutex();
+DeviceRuntime &device_runtime();
 
 template <class T>
 struct DeviceBuffer {  // RAII hipMalloc, the role of CudaDenseMatrix / CudaCSRMatrix members (matrix.cu:12-46)

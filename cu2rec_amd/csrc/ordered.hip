@@ -625,7 +625,7 @@ void launch_chain(const SgdArgs &a, const uint32_t *keys, const uint64_t *vals, 
     const int walk_blocks = (n_active - walk_lo + kGroupsPerBlock - 1) / kGroupsPerBlock;
     const int blocks = hot_blocks + walk_blocks + (walk_lo > 0 ? 1 : 0);
     if (blocks == 0) return;
-    if (stop)  // the event rides on the kernel's completion signal (see bs_launch_gram)
+    if (stop)  // the event rides on the kernel's completion signal (see launch_gram, blocksolve.hip)
         hipExtLaunchKernelGGL(sgd_ordered_kernel<J>, dim3(blocks), dim3(kBlock), 0, stream, nullptr, stop, 0, a, keys, vals, n_active,
                               item_of_rank, item_mask, n_hot, hot_blocks, rank_lo, ranges, walk_lo, walk_blocks);
     else
@@ -687,8 +687,10 @@ OrderedSchedule::OrderedSchedule(const int *d_indptr, const int *d_indices, int 
     item_rank.upload(rank.data(), n_cols);
     item_of_rank.allocate(n_cols);
     item_of_rank.upload(order.data(), n_cols);
+    std::vector<double> rank_rate(n_cols);  // expected updates per iteration by popularity rank
+    for (int r = 0; r < n_cols; ++r) rank_rate[r] = rate[order[r]];
     rank_rate_prefix.assign(static_cast<size_t>(n_cols) + 1, 0.0);
-    for (int r = 0; r < n_cols; ++r) rank_rate_prefix[r + 1] = rank_rate_prefix[r] + rate[order[r]];
+    for (int r = 0; r < n_cols; ++r) rank_rate_prefix[r + 1] = rank_rate_prefix[r] + rank_rate[r];
     item_bits = bits_for(n_cols);
     // batch size: keep key = b << item_bits | rank (+ the sentinel bit) inside 32 bits and the buffers modest
     int b_bits = std::min(6, 31 - item_bits - 1);
@@ -713,56 +715,17 @@ OrderedSchedule::OrderedSchedule(const int *d_indptr, const int *d_indices, int 
                                                                        seg_offsets.ptr, seg_offsets.ptr + 1, 0u, 32u, nullptr));
     }
     temp.allocate(temp_bytes + 16);
-    // block-solve workspace
-    // the threshold: what the caller set, else scaled with the set -- down (a long chain costs the same whatever the set,
-    // the launch overhead it has to beat does not shrink with it; 1/1 .. 1/8 of the ML-20M shape,
-    // profiles/r02_shard_size_probe_blocksolve.log) and up (Netflix shape, 480,189 users: 290 us per iteration at 800
-    // against 353 at 240 -- the chains of several hundred hot items do not fit the CUs at once)
-    float min_rate = blocksolve_min_rate_base();
-    if (!blocksolve_min_rate_is_set()) {
-        min_rate = std::max(30.f, min_rate * static_cast<float>(n_active) / 131072.f);
-        // a small set (one GPU's shard of a strong-scaling run): with the hottest item between 150 and 350 expected updates per
-        // iteration a threshold of 60 still pays a little (an eighth of the ML-20M shape, hottest item 247: 32.5 us per iteration
-        // against 35.3 walking everything; thresholds 40 / 60 / 90 / 130 / 180: 32.6 / 32.5 / 33.7 / 37.5 / 41.4, round 5); below
-        // that no chain is long enough to pay for three launches per iteration and the mode IS the ordered walk (ML-1M shape)
-        // Only for SMALL sets (at most a quarter of 131,072 users: where the rule was measured).  A large set with flat popularity --
-        // many users, hottest item under 350 -- keeps the scaled threshold: there "every item above 60" would be hundreds of
-        // 512-thread solve workgroups the side stream's gate has to see started (the regime that did not fit the CUs on the
-        // Netflix shape), and nothing was measured there.
-        if (n_cols > 0 && n_active <= 131072 / 4 && rate[order[0]] < 350.0)
-            min_rate = rate[order[0]] >= 150.0 ? 60.f : std::numeric_limits<float>::infinity();
-    }
-    n_hot_bs = 0;
-    while (n_hot_bs < n_cols && rate[order[n_hot_bs]] >= min_rate) ++n_hot_bs;
-    n_hot_bs = std::min(n_hot_bs, (1 << item_bits) - 1);
+    const int n_hot_bs = blocksolve_hot_items(rank_rate, n_active, (1 << item_bits) - 1);
+    if (n_hot_bs > 0)
+        bs.reset(new BlockSolve(n_hot_bs, rank_rate, rank_rate_prefix[static_cast<size_t>(n_hot_bs)], n_active, item_bits, max_batch,
+                                item_of_rank.ptr));
     // beside the block solves: chains expected to be at least 12 links long run in the ordered mode's two-wave form
     n_duo_bs = n_hot_bs;
-    while (n_duo_bs < n_cols && n_duo_bs < 4096 && rate[order[n_duo_bs]] >= 12.0) ++n_duo_bs;
+    while (n_duo_bs < n_cols && n_duo_bs < 4096 && rank_rate[n_duo_bs] >= 12.0) ++n_duo_bs;
     n_duo_bs = std::min(n_duo_bs, (1 << item_bits) - 1);
-    max_blocks = n_active / kBsLinks + n_hot_bs + 1;
-    // the look-ahead form of phase 2 (blocksolve.hip): the leading ranks whose chains are expected to be at least
-    // blocksolve_lookahead_blocks() blocks long -- the chains whose length is the iteration's critical path.  Their blocks are
-    // the first of every iteration's block table; la_cap bounds them with room to spare (a chain beyond it: the plain form).
-    la_ranks = 0;
-    la_cap = 0;
-    {
-        const int la_min = blocksolve_lookahead_blocks(-1);
-        double blocks = 0.0;
-        while (la_min > 0 && la_ranks < n_hot_bs && rate[order[la_ranks]] >= static_cast<double>(la_min) * kBsLinks) {
-            blocks += std::ceil(rate[order[la_ranks]] / kBsLinks) + 1.0;
-            ++la_ranks;
-        }
-        if (la_ranks > 0) la_cap = std::min(max_blocks, static_cast<int>(blocks * 1.25) + 4 * la_ranks + 8);
-    }
     n_range_ranks = std::max(std::max(std::min(n_cols, kHotChains), n_duo_bs), n_hot_bs);
     n_range_ranks = std::min(n_range_ranks, (1 << item_bits) - 1);
-    for (int slot = 0; slot < 2; ++slot) {
-        chain_ranges[slot].allocate(static_cast<size_t>(max_batch) * (n_range_ranks + 1));
-        chain_begin[slot].allocate(static_cast<size_t>(max_batch) * (n_hot_bs + 1));
-        walk_begin[slot].allocate(max_batch);
-        bs_chains[slot].allocate(static_cast<size_t>(max_batch) * std::max(n_hot_bs, 1));
-        bs_blocks[slot].allocate(static_cast<size_t>(max_batch) * max_blocks);
-    }
+    for (int slot = 0; slot < 2; ++slot) chain_ranges[slot].allocate(static_cast<size_t>(max_batch) * (n_range_ranks + 1));
     {
         // The next batch's schedule is built beside the iterations that consume this batch's, on a stream of the lowest priority
         // (measured: no different from the default priority -- what its kernels cost the iterations is DESIGN.md section 4)
@@ -774,19 +737,7 @@ OrderedSchedule::OrderedSchedule(const int *d_indptr, const int *d_indices, int 
         CU2REC_HIP(hipEventCreateWithFlags(&ev_ready[slot], hipEventDisableTiming));
         CU2REC_HIP(hipEventCreateWithFlags(&ev_consumed[slot], hipEventDisableTiming));
     }
-    tables.allocate(kBsTableFloats);
     CU2REC_HIP(hipEventCreateWithFlags(&ev_last, hipEventDisableTiming));
-    if (n_hot_bs > 0) {
-        Mbuf.allocate(static_cast<size_t>(max_blocks) * kBsRecFloats);
-        ebuf.allocate(static_cast<size_t>(max_blocks) * kBsLinks);
-        solve_started.allocate(16);
-        solve_started.zero();
-        gram_done.allocate(32 * 16);
-        gram_done.zero();
-        side_seq.allocate(16);
-        side_seq.zero();
-        if (la_cap > 0) Nbuf.allocate(static_cast<size_t>(la_cap) * kBsCrossFloats);
-    }
 }
 
 OrderedSchedule::~OrderedSchedule() {
@@ -798,59 +749,7 @@ OrderedSchedule::~OrderedSchedule() {
         if (ev_ready[slot]) (void)hipEventDestroy(ev_ready[slot]);
         if (ev_consumed[slot]) (void)hipEventDestroy(ev_consumed[slot]);
     }
-    if (upd) (void)hipStreamDestroy(upd);
-    for (hipEvent_t e : {ev_call, ev_upd, ev_gram, ev_last})
-        if (e) (void)hipEventDestroy(e);
-}
-
-namespace {
-std::atomic<int> g_bs_lookahead{-1};  // -1: not yet initialised from the environment
-}
-
-int blocksolve_lookahead_blocks(int blocks) {
-    int prev = g_bs_lookahead.load();
-    if (prev < 0) {
-        const char *env = std::getenv("CU2REC_BLOCKSOLVE_LOOKAHEAD");
-        const int init = env ? std::max(0, std::atoi(env)) : 24;  // the top chains only: DESIGN.md section 4, "The look-ahead form"
-        g_bs_lookahead.compare_exchange_strong(prev, init);
-        prev = g_bs_lookahead.load();
-    }
-    if (blocks >= 0) g_bs_lookahead.store(blocks);
-    return prev;
-}
-
-namespace {
-// explicit threshold (> 0), or <= 0: automatic (240 per 131,072 rating users, scaled with the set); -2 = not yet initialised
-// from the environment
-std::atomic<float> g_bs_min_rate{-2.f};
-constexpr float kBsDefaultRate = 240.f;
-
-float bs_min_rate_state() {
-    float cur = g_bs_min_rate.load();
-    if (cur == -2.f) {  // first use: CU2REC_BLOCKSOLVE_RATE overrides the automatic threshold
-        float init = -1.f;
-        if (const char *env = std::getenv("CU2REC_BLOCKSOLVE_RATE")) init = std::max(0.01f, static_cast<float>(std::atof(env)));
-        g_bs_min_rate.compare_exchange_strong(cur, init);
-        cur = g_bs_min_rate.load();
-    }
-    return cur;
-}
-}  // namespace
-
-bool blocksolve_min_rate_is_set() { return bs_min_rate_state() > 0.f; }
-
-float blocksolve_min_rate_base() {
-    const float cur = bs_min_rate_state();
-    return cur > 0.f ? cur : kBsDefaultRate;
-}
-
-// rate > 0: explicit threshold; rate < 0: back to automatic; rate == 0: query.  Returns what was in force before the call:
-// the explicit value, or -1 for automatic -- so that f(f(x)) restores either state.
-float blocksolve_min_rate(float rate) {
-    const float prev = bs_min_rate_state();
-    if (rate > 0.f) g_bs_min_rate.store(rate);
-    else if (rate < 0.f) g_bs_min_rate.store(-1.f);
-    return prev > 0.f ? prev : -1.f;
+    if (ev_last) (void)hipEventDestroy(ev_last);
 }
 
 // How many sorted positions the walk behind popularity rank n_hot has to cover in one iteration, as an upper bound that holds in all but
@@ -869,22 +768,9 @@ int OrderedSchedule::walk_bound(int n_hot) const {
     return bound >= static_cast<double>(n_active) ? n_active : static_cast<int>(bound);
 }
 
-// Blocks of 64 links an iteration's hot chains are expected to fill, as a bound that holds in all but astronomically rare iterations
-// (the hot links' count: mean rank_rate_prefix[n_hot_bs], variance at most the mean; one partial block per chain): what phase 3 is
-// launched with.  Its workgroups stride through the dense block table, so an iteration beyond the bound is still done completely.
-int OrderedSchedule::blocks_bound() const {
-#ifdef CU2REC_TEST_HOOKS  // (fault-path tests: a launch far too small, so that every workgroup strides over many blocks)
-    if (const char *env = std::getenv("CU2REC_BS_DBG"))
-        if (std::atoi(env) & 512) return std::min(3, max_blocks);
-#endif
-    const double mean = rank_rate_prefix[static_cast<size_t>(std::min(std::max(n_hot_bs, 0), n_cols))];
-    const double bound = (mean + 8.0 * std::sqrt(mean) + 64.0) / kBsLinks + n_hot_bs + 1;
-    return std::max(1, bound >= static_cast<double>(max_blocks) ? max_blocks : static_cast<int>(bound));
-}
-
 void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t stream, bool blocksolve) {
     if (n_active == 0) return;
-    if (blocksolve && n_hot_bs == 0) blocksolve = false;  // nothing to solve block-wise: the ordered walk, bit for bit
+    if (blocksolve && !bs) blocksolve = false;  // nothing to solve block-wise: the ordered walk, bit for bit
     // A decay factor a = 1 - lr Q_reg or c = 1 - lr item_bias_reg at or below zero has no logarithm: the cross-tile terms
     // exp2(d * log2 a) would be NaN (0 * -inf at d = 0).  The sequential update is still defined there: the ordered walk, bit for bit.
     // (In double, as the decay tables are.)
@@ -894,32 +780,13 @@ void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t st
     // The workspace (key / value buffers, block records, events) exists once: a call on another stream than the last one
     // starts behind that call's end.
     if (have_last && last_stream != stream) CU2REC_HIP(hipStreamWaitEvent(stream, ev_last, 0));
-    if (blocksolve) {
-        if (!bs_supported(a.nslots)) fail(CU2REC_EUNSUPPORTED, "block-solve mode is compiled for n_factors <= 252");
-        const bool same = tables_valid && tables_for.lr == a.h.lr && tables_for.q_reg == a.h.q_reg && tables_for.ib_reg == a.h.ib_reg;
-        if (!same) {  // stream ordered: kernels already queued keep the old tables
-            bs_launch_tables(a.h, tables.ptr, stream);
-            tables_for = a.h;
-            tables_valid = true;
-        }
-        if (qstart_ld != a.ldq) {
-            CU2REC_HIP(hipStreamSynchronize(stream));
-            qstart.allocate(static_cast<size_t>(max_blocks) * a.ldq);
-            qstart_ld = a.ldq;
-        }
-        if (!upd) {
-            // default priority: a high-priority queue whose workgroups cannot all be placed (more hot chains than CUs) held back
-            // the queues below it (a 300-chain test set ran into the waits' timeout)
-            CU2REC_HIP(hipStreamCreateWithFlags(&upd, hipStreamNonBlocking));
-            for (hipEvent_t *e : {&ev_call, &ev_upd, &ev_gram}) CU2REC_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        }
-    }
+    if (blocksolve) bs->begin(a, stream);
     const uint32_t item_mask = (1u << item_bits) - 1u;
     // ranks [0, n_hot) get a dedicated group each with deep prefetch; keep r + 1 representable in item_bits
     const int n_hot = std::min(std::min(n_cols, kHotChains), static_cast<int>(item_mask));
     // positions the walk covers per iteration (its tail of the sorted order): behind the two-wave chains of either mode
-    const int walk_bound_plain = walk_bound(n_hot), walk_bound_bs = walk_bound(std::max(n_duo_bs, n_hot_bs));
-    const int launch_blocks = blocksolve ? blocks_bound() : 0;
+    const int n_hot_bs = blocksolve_items(), n_side = std::max(n_duo_bs, n_hot_bs);
+    const int walk_bound_plain = walk_bound(n_hot), walk_bound_bs = walk_bound(n_side);
     // Sample + sort (+ plan) of one window into a slot, on the schedule stream: nothing in it depends on the model.  The keys carry
     // the item's popularity rank only, and every iteration of the window is sorted as a segment of its own (stable, so users stay
     // ascending inside a chain); iteration b of the window occupies [b * n_rows, b * n_rows + n_active) of the sorted arrays.
@@ -941,9 +808,7 @@ void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t st
         Window w{true, a.seed, first_iter, nb, a.user_offset, a.indptr, blocksolve, keys[slot][1].ptr, vals[slot][1].ptr};
         hipLaunchKernelGGL(chain_ranges_kernel, dim3(nb), dim3(kBlock), 0, sched, w.sk, n_active, n_range_ranks, chain_ranges[slot].ptr, seg);
         CU2REC_HIP(hipGetLastError());
-        if (blocksolve)
-            bs_launch_plan(w.sk, n_active, nb, n_hot_bs, item_bits, max_blocks, item_of_rank.ptr, chain_begin[slot].ptr,
-                           bs_chains[slot].ptr, bs_blocks[slot].ptr, walk_begin[slot].ptr, sched, seg);
+        if (blocksolve) bs->plan(slot, w.sk, nb, seg, sched);
         CU2REC_HIP(hipEventRecord(ev_ready[slot], sched));
         slot_used[slot] = true;
         win[slot] = w;
@@ -966,10 +831,13 @@ void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t st
         return w.valid && w.seed == a.seed && w.user_offset == a.user_offset && w.indptr == a.indptr && w.blocksolve == blocksolve &&
                it >= w.iter_begin && it < w.iter_begin + static_cast<uint64_t>(w.nb);
     };
-    if (blocksolve) {  // the side stream starts behind everything the caller has queued so far
-        CU2REC_HIP(hipEventRecord(ev_call, stream));
-        CU2REC_HIP(hipStreamWaitEvent(upd, ev_call, 0));
-    }
+    // the iteration being launched, and (block-solve mode) the launch of its other chains beside the hot ones
+    const uint32_t *kb = nullptr;
+    const uint64_t *vb = nullptr;
+    const int *ranges = nullptr;
+    const BlockSolve::SideChains side_chains = [&](hipStream_t side, hipEvent_t stop) {
+        launch_chains(a, kb, vb, n_active, item_of_rank.ptr, item_mask, n_side, side, n_hot_bs, ranges, stop, walk_bound_bs);
+    };
     int done = 0;
     while (done < n_iters) {
         const uint64_t it_first = iter0 + static_cast<uint64_t>(done);
@@ -1002,108 +870,24 @@ void OrderedSchedule::run(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t st
         const uint32_t *sk = win[slot].sk + static_cast<size_t>(off) * seg;   // (the batch's first iteration inside the window)
         const uint64_t *sv = win[slot].sv + static_cast<size_t>(off) * seg;
         a.iters = 1;
-        if (blocksolve) {
-            // One iteration = four launches: `stream`: phase 1 (bs_gram_kernel: every block's inverse factor) -> phase 2
-            // (bs_solve_kernel: one workgroup per chain) -> phase 3 (bs_update_kernel: the user side); side stream `upd`: the other
-            // items' chains (two-wave form / walk), forked behind phase 1 -- beside it their thousands of workgroups take the CUs
-            // from phase 1's (measured: 71 instead of 19 us) -- and joined in front of the next phase 1, which reads rows they write.
-            //  * default (bs_topology() == kBsTopoDevice: blocksolve.hip, "the launch topology"), no event on the main stream: phase 1's workgroups count themselves through, phase 2's
-            //    count themselves in, ONE wavefront queued in front of the side kernel (bs_gate_kernel) ends when both counts have
-            //    reached what the host has launched so far; a signal kernel behind the side kernel stores the iteration's number and
-            //    one extra workgroup of phase 3's launch waits for it.  Host order gram, solve, gate, side, signal, update: every
-            //    launch behind what it waits for (streams sharing a hardware queue serialise, they cannot wait for each other).
-            //  * events (kBsTopoEvents: a counter pass, streams that do not run side by side, after a join that gave up): fork on phase 1's completion signal, join by an event wait in
-            //    front of the next phase 1 (5.4 + 2.5-3.3 us per iteration on the main stream: DESIGN.md section 4).
-            const double la = std::log2(1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.q_reg));
-            const double lc = std::log2(1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.ib_reg));
-            unsigned *status = bs_status_word();
-            const bool device_join = max_blocks > 0 && bs_topology(stream, upd) == kBsTopoDevice;
-            bool upd_pending = false;  // (event join) the side kernel of an earlier iteration of this batch has not been waited for yet
-#ifdef CU2REC_TEST_HOOKS  // fault-path tests only (build/test/libcu2rec_amd_hooks.so): 16 the signal is never sent, 32 the gate can never open
-            static const int dbg = std::getenv("CU2REC_BS_DBG") ? std::atoi(std::getenv("CU2REC_BS_DBG")) : 0;
-#else
-            constexpr int dbg = 0;
-#endif
-            for (int b = 0; b < nb; ++b) {
-                if (b == std::min(2, nb - 1) && b > 0) schedule_next();  // (two iterations are queued: the device has work)
-                a.iter0 = iter0 + done + b;
-                BsIteration it{};
-                it.keys = sk + static_cast<size_t>(b) * seg;
-                it.vals = sv + static_cast<size_t>(b) * seg;
-                it.n_active = n_active;
-                it.n_hot = n_hot_bs;
-                it.item_mask = item_mask;
-                it.chains = bs_chains[slot].ptr + static_cast<size_t>(off + b) * std::max(n_hot_bs, 1);
-                it.blocks = bs_blocks[slot].ptr + static_cast<size_t>(off + b) * max_blocks;
-                it.walk_begin = walk_begin[slot].ptr + off + b;
-                it.item_of_rank = item_of_rank.ptr;
-                it.tables = tables.ptr;
-                it.log2a = static_cast<float>(la);
-                it.log2c = static_cast<float>(lc);
-                it.Mbuf = Mbuf.ptr;
-                it.ebuf = ebuf.ptr;
-                it.qstart = qstart.ptr;
-                it.max_blocks = max_blocks;
-                it.launch_blocks = launch_blocks;
-                const bool la_on = la_ranks > 0 && bs_lookahead_supported(a.nslots);  // (rows the rings have LDS for)
-                it.la_ranks = la_on ? la_ranks : 0;
-                it.la_cap = la_cap;
-                it.la_grid = la_on ? la_cap : 0;
-                it.Nbuf = Nbuf.ptr;
-                it.status = status;
-                it.solve_started = solve_started.ptr;
-                it.wait_ticks = bs_wait_ticks();
-                const int *ranges = chain_ranges[slot].ptr + static_cast<size_t>(off + b) * (n_range_ranks + 1);
-                if (device_join) {
-                    // (the host's counts move only behind a launch that succeeded: a launch that throws leaves gate and counters in
-                    // step for the calls that follow)
-                    it.gram_done = gram_done.ptr;
-                    it.side_seq = side_seq.ptr;
-                    it.side_target = side_seq_host + 1;
-                    bs_launch_gram(a, it, stream);
-                    gram_done_target += static_cast<unsigned long long>(max_blocks + it.la_grid);
-                    bs_launch_solve(a, it, stream);
-                    started_total += static_cast<unsigned long long>(n_hot_bs);
-                    bs_launch_gate(gram_done.ptr, gram_done_target + ((dbg & 32) ? (1ull << 40) : 0ull), solve_started.ptr, started_total, upd);
-                    // (only the batch's last side kernel carries the event the main stream waits for at the END of the batch: an event
-                    // on a kernel's completion signal holds the next packet of its queue back, here the signal kernel: 5.4 us)
-                    launch_chains(a, it.keys, it.vals, n_active, item_of_rank.ptr, item_mask, std::max(n_duo_bs, n_hot_bs), upd, n_hot_bs, ranges,
-                                  b == nb - 1 ? ev_upd : nullptr, walk_bound_bs);
-                    ++side_seq_host;
-                    if (!(dbg & 16)) bs_launch_signal(side_seq.ptr, side_seq_host, upd);
-                    bs_launch_update(a, it, stream);
-                } else {
-                    if (upd_pending) CU2REC_HIP(hipStreamWaitEvent(stream, ev_upd, 0));  // join: rows the next phase 1 reads
-                    bs_launch_gram(a, it, stream, ev_gram);
-                    CU2REC_HIP(hipStreamWaitEvent(upd, ev_gram, 0));
-                    bs_launch_solve(a, it, stream);
-                    launch_chains(a, it.keys, it.vals, n_active, item_of_rank.ptr, item_mask, std::max(n_duo_bs, n_hot_bs), upd, n_hot_bs, ranges, ev_upd,
-                                  walk_bound_bs);
-                    bs_launch_update(a, it, stream);
-                    upd_pending = true;
-                }
-            }
-            schedule_next();  // (a batch of one or two iterations)
-            CU2REC_HIP(hipGetLastError());
-            // the batch's slot is free once both streams are through with it
-            CU2REC_HIP(hipStreamWaitEvent(stream, ev_upd, 0));
-            CU2REC_HIP(hipEventRecord(ev_consumed[slot], stream));
-            done += nb;
-            continue;
-        }
         for (int b = 0; b < nb; ++b) {
-            if (b == std::min(2, nb - 1) && b > 0) schedule_next();
+            if (b == std::min(2, nb - 1) && b > 0) schedule_next();  // (two iterations are queued: the device has work)
             a.iter0 = iter0 + done + b;
-            launch_chains(a, sk + static_cast<size_t>(b) * seg, sv + static_cast<size_t>(b) * seg, n_active, item_of_rank.ptr, item_mask, n_hot, stream, 0,
-                          n_hot <= n_range_ranks ? chain_ranges[slot].ptr + static_cast<size_t>(off + b) * (n_range_ranks + 1) : nullptr, nullptr,
-                          walk_bound_plain);
+            kb = sk + static_cast<size_t>(b) * seg;
+            vb = sv + static_cast<size_t>(b) * seg;
+            ranges = chain_ranges[slot].ptr + static_cast<size_t>(off + b) * (n_range_ranks + 1);
+            if (blocksolve) bs->iteration(a, slot, off + b, kb, vb, b == nb - 1, stream, side_chains);
+            else
+                launch_chains(a, kb, vb, n_active, item_of_rank.ptr, item_mask, n_hot, stream, 0, n_hot <= n_range_ranks ? ranges : nullptr,
+                              nullptr, walk_bound_plain);
         }
-        schedule_next();
+        schedule_next();  // (a batch of one or two iterations)
         CU2REC_HIP(hipGetLastError());
+        if (blocksolve) bs->join(stream);  // the batch's slot is free once both streams are through with it
         CU2REC_HIP(hipEventRecord(ev_consumed[slot], stream));
         done += nb;
     }
-    if (blocksolve) bs_report_status(stream);  // (every batch ended with `stream` behind the side stream)
+    if (blocksolve) bs->end(stream);
     CU2REC_HIP(hipEventRecord(ev_last, stream));
     last_stream = stream;
     have_last = true;

@@ -1,6 +1,7 @@
 // Workspace + driver of the ordered (sequential-semantics, deterministic) SGD mode; see ordered.hip.
 #pragma once
 
+#include <memory>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -55,18 +56,11 @@ struct OrderedSchedule {
     DeviceBuffer<unsigned char> temp;
     DeviceBuffer<int> seg_offsets;  // [max_batch + 1] b * n_rows: the iterations of a batch as segments of the sort
     size_t temp_bytes = 0;
-    // block-solve mode: items are ranked by their expected updates per iteration (sum over raters of 1 / degree);
-    // ranks [0, n_hot_bs) -- at least blocksolve_min_rate() expected updates -- get the block-wise treatment
-    int n_hot_bs = 0;
-    int n_duo_bs = 0;        // ranks [n_hot_bs, n_duo_bs): the ordered mode's two-wave chains, beside the block solves
-    int max_blocks = 0;      // blocks of 64 links (kBsLinks) per iteration, upper bound
-    int la_ranks = 0;        // ranks [0, la_ranks): phase 2 in the look-ahead form (blocksolve.hip); their blocks lie below la_cap
-    int la_cap = 0;
-    DeviceBuffer<float> Nbuf;  // [la_cap][kBsCrossFloats] the cross blocks of the look-ahead chains
-    int qstart_ld = 0;
-    SgdHyper tables_for{};   // hyper-parameters the decay tables were computed from
-    bool tables_valid = false;
-    DeviceBuffer<int> chain_begin[2], walk_begin[2];
+    // block-solve mode (blocksolve.hip): items are ranked by their expected updates per iteration (sum over raters of 1 / degree); the
+    // block-wise solved ones are ranks [0, bs->n_hot); no BlockSolve when no item qualifies (the mode is then the ordered walk)
+    std::unique_ptr<BlockSolve> bs;
+    int blocksolve_items() const { return bs ? bs->n_hot : 0; }
+    int n_duo_bs = 0;  // block-solve mode: ranks [bs->n_hot, n_duo_bs) run in the two-wave form beside the block solves
     // per schedule slot: [iteration of the batch][rank 0 .. n_range_ranks] first sorted position of the chains of the most
     // popular items (chain_ranges_kernel, behind the sort): the two-wave blocks read their chain's range instead of searching
     DeviceBuffer<int> chain_ranges[2];
@@ -75,36 +69,11 @@ struct OrderedSchedule {
     // behind rank r has to cover is n_active minus that, give or take its square root (walk_bound)
     std::vector<double> rank_rate_prefix;
     int walk_bound(int n_hot) const;
-    int blocks_bound() const;  // workgroups phase 3 of a block-solve iteration is launched with (BsIteration::launch_blocks)
-    DeviceBuffer<BsChainDesc> bs_chains[2];
-    DeviceBuffer<BsBlockDesc> bs_blocks[2];
-    DeviceBuffer<float> tables, Mbuf, ebuf, qstart;
-    // Block-solve mode: an iteration is four launches on two streams -- `stream` (the caller's): phases 1, 2, 3; `upd`: the other
-    // items' chains (two-wave form + walk) beside phases 2 and 3, forked behind phase 1 and joined in front of the next phase 1
-    // without events on the main stream (OrderedSchedule::run, blocksolve.hpp)
-    DeviceBuffer<unsigned long long> solve_started, gram_done;
-    unsigned long long gram_done_target = 0;  // phase-1 workgroups launched so far (what gram_done will reach)
-    DeviceBuffer<unsigned long long> side_seq;  // [1] number of the last iteration whose side kernel is complete (bs_launch_signal)
-    unsigned long long side_seq_host = 0;
-    unsigned long long started_total = 0;  // phase-2 workgroups launched so far (what solve_started will reach)
-    hipStream_t upd = nullptr;
-    hipEvent_t ev_call = nullptr, ev_upd = nullptr, ev_gram = nullptr;
     // one stream at a time per schedule: a call on another stream than the last one first waits for that call's end
     hipEvent_t ev_last = nullptr;
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     ~OrderedSchedule();
 };
-
-// minimum expected updates per iteration of an item for block-wise treatment (process-wide; schedules created later)
-// rate > 0 sets it, rate < 0 returns to automatic (scaled with the set), 0 queries; returns the explicit value in force before
-// the call or -1 for automatic
-float blocksolve_min_rate(float rate);
-float blocksolve_min_rate_base();   // the explicit value, or the default the automatic scaling starts from
-bool blocksolve_min_rate_is_set();  // by the caller or the environment; otherwise a schedule scales the default with its set
-
-// chains EXPECTED to be at least this many blocks of 64 links long run phase 2 in the look-ahead form (default 24: the top chains; 0: none;
-// schedules created later); blocks < 0 only queries
-int blocksolve_lookahead_blocks(int blocks);
 
 }  // namespace cu2rec

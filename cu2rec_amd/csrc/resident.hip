@@ -35,7 +35,7 @@
 // write-backs per XCD queue behind each other.)  The barrier is split in two halves; the next iteration's sample
 // gathers and the acquire's L1 invalidate sit between them.  Every spin is bounded (wall clock): a grid that is
 // not co-resident ends with the status word set instead of hanging, and the host reports it
-// (resident_check_fault).  Residency comes from the grid size alone: at most one workgroup per CU.
+// (check_faults, device.cpp).  Residency comes from the grid size alone: at most one workgroup per CU.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -442,10 +442,9 @@ bool resident_partial_allowed() { return true; }
 struct DeviceState {
     bool ready = false;
     bool usable[kNumVariants] = {};   // the occupancy query admits one workgroup per CU
-    int cus = 0;
-    unsigned *words = nullptr;        // device: the barrier block (kBarrierWords), then the status word
+    DeviceRuntime *runtime = nullptr; // CU count, status word and its pinned host copy (refreshed after every launch)
+    unsigned *words = nullptr;        // device: the barrier block (kBarrierWords)
     float *sink = nullptr;            // device: kSinkFloats floats
-    unsigned *host_status = nullptr;  // pinned host copy of the status word, refreshed after every launch
     hipEvent_t done = nullptr;        // end of the latest resident launch
     hipStream_t last_stream = nullptr;
     bool have_last = false;
@@ -463,18 +462,17 @@ DeviceState &state_for_current_device() {
     if (static_cast<int>(g_states.size()) <= dev) g_states.resize(dev + 1);
     DeviceState &s = g_states[dev];
     if (!s.ready) {
-        hipDeviceProp_t prop;
-        CU2REC_HIP(hipGetDeviceProperties(&prop, dev));
-        s.cus = prop.multiProcessorCount;
+        {
+            std::lock_guard<std::mutex> lock(device_runtime_mutex());
+            s.runtime = &device_runtime();
+        }
         int coop = 0;
         if (hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) != hipSuccess) (void)hipGetLastError();
         s.cooperative = coop != 0;
-        CU2REC_HIP(hipMalloc(reinterpret_cast<void **>(&s.words), (kBarrierWords + kLine) * sizeof(unsigned)));
-        CU2REC_HIP(hipMemset(s.words, 0, (kBarrierWords + kLine) * sizeof(unsigned)));
+        CU2REC_HIP(hipMalloc(reinterpret_cast<void **>(&s.words), kBarrierWords * sizeof(unsigned)));
+        CU2REC_HIP(hipMemset(s.words, 0, kBarrierWords * sizeof(unsigned)));
         CU2REC_HIP(hipMalloc(reinterpret_cast<void **>(&s.sink), kSinkFloats * sizeof(float)));
         CU2REC_HIP(hipMemset(s.sink, 0, kSinkFloats * sizeof(float)));
-        CU2REC_HIP(hipHostMalloc(reinterpret_cast<void **>(&s.host_status), sizeof(unsigned), hipHostMallocDefault));
-        *s.host_status = 0;
         CU2REC_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
         for (int i = 0; i < kNumVariants; ++i) {
             int per_cu = 0;
@@ -502,27 +500,6 @@ int resident_policy(int set_to) {
     const int prev = g_policy.load();
     if (set_to >= kResidentOff && set_to <= kResidentForce) g_policy.store(set_to);
     return prev;
-}
-
-void resident_check_fault() {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) {
-        (void)hipGetLastError();
-        return;
-    }
-    if (dev < static_cast<int>(g_states.size()) && g_states[dev].ready &&
-        *static_cast<volatile unsigned *>(g_states[dev].host_status) != 0) {
-        // reported once: the words are cleared so that the process can go on (e.g. with cu2rec_hogwild_resident(0))
-        DeviceState &s = g_states[dev];
-        (void)hipDeviceSynchronize();
-        (void)hipMemset(s.words + kBarrierWords, 0, sizeof(unsigned));
-        *s.host_status = 0;
-        fail(CU2REC_EHIP,
-             "cu2rec_amd: a persistent SGD launch gave up at its grid barrier (the grid was not co-resident: is another "
-             "process or stream using this GPU?); the model state is undefined.  cu2rec_hogwild_resident(0) / "
-             "CU2REC_RESIDENT=0 selects the one-launch-per-iteration Hogwild kernel");
-    }
 }
 
 // Pure arithmetic of the plan (no device needed): which compiled variant holds n_rows users of this width on n_cus
@@ -579,7 +556,7 @@ bool plan_locked(int n_rows, int nslots, int n_iters, int update_items, DeviceSt
     DeviceState &s = state_for_current_device();
     state = &s;
     int need = 0;
-    variant = geometry(n_rows, nslots, s.cus, need, blocks, streamed);
+    variant = geometry(n_rows, nslots, s.runtime->cus, need, blocks, streamed);
     if (variant < 0 || !s.usable[variant]) return false;  // the rows do not fit: stream them
     // Auto: the barrier costs a few microseconds where a kernel boundary costs one or two, so residency pays once
     // an iteration moves enough rows per group and the launch is long enough to amortise loading them.
@@ -623,7 +600,8 @@ bool resident_launch(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t stream)
     if (s.have_last && s.last_stream != stream) CU2REC_HIP(hipStreamWaitEvent(stream, s.done, 0));  // never two at once
     a.iter0 = iter0;
     a.iters = n_iters;
-    ResidentArgs ra{s.words, s.words + kBarrierWords, s.sink, streamed};
+    unsigned *status = s.runtime->status + DeviceRuntime::kResidentWord;
+    ResidentArgs ra{s.words, status, s.sink, streamed};
     void *args[] = {&a, &ra};
     CU2REC_HIP(hipMemsetAsync(s.words, 0, kBarrierWords * sizeof(unsigned), stream));  // counters start from zero
     // A cooperative launch: the runtime checks the grid against what can be co-resident and REFUSES a larger one up
@@ -641,7 +619,7 @@ bool resident_launch(SgdArgs a, uint64_t iter0, int n_iters, hipStream_t stream)
         return false;
     }
     CU2REC_HIP(launched);  // anything else (lost device, a sticky error of an earlier kernel, bad configuration) is an error
-    CU2REC_HIP(hipMemcpyAsync(s.host_status, s.words + kBarrierWords, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+    CU2REC_HIP(hipMemcpyAsync(s.runtime->host_status, status, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
     CU2REC_HIP(hipEventRecord(s.done, stream));
     s.last_stream = stream;
     s.have_last = true;

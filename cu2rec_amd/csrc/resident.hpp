@@ -33,7 +33,4 @@ int resident_streamed_rows(int n_rows, int n_factors, int n_cus);
 // Launches the runtime refused on the current device because the grid could not be co-resident (those calls streamed).
 int resident_refusals();
 
-// Throws if an earlier resident launch on the current device gave up at a grid barrier (bounded spin).
-void resident_check_fault();
-
 }  // namespace cu2rec

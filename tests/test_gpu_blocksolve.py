@@ -508,6 +508,7 @@ def test_blocksolve_random_shapes_long_chains(min_rate, case):
 
 
 _FAULT_SCRIPT = r"""
+import os
 import sys
 import numpy as np
 sys.path.insert(0, %(root)r)
@@ -525,7 +526,10 @@ try:
     model.sgd(d_tr, hyper, 42, 0, iters, mode="blocksolve")
     check(lib().cu2rec_check_faults())
 except Cu2recError as e:
-    print("STATUS", e.status, "gave up" in str(e), "with events instead" in str(e))
+    print("STATUS", e.status, "gave up" in str(e), "with events instead" in str(e), "CU2REC_BS_GATE" in str(e))
+    if os.environ.get("CU2REC_BS_GATE"):  # forced: no healing, the device form stays
+        print("TOPOLOGY", api.blocksolve_topology()[0])
+        sys.exit(0)
     # self-healing: the process has switched to the event fork / join -- a fresh model, the same call, the oracle's result
     assert api.blocksolve_topology()[0] == "events", api.blocksolve_topology()
     model = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
@@ -544,13 +548,15 @@ print("OK %%.3e" %% max(float(np.abs(g.astype(np.float64) - w).max()) for g, w i
 """
 
 
-def _run_fault_script(dbg):
+def _run_fault_script(dbg, **extra_env):
     import subprocess
     import sys
     # (the fault injection is compiled only into the test build of the library: make test-hooks -> build/test/libcu2rec_amd_hooks.so)
     hooks = os.path.join(ROOT, "build", "test", "libcu2rec_amd_hooks.so")
     assert os.path.exists(hooks), "build/test/libcu2rec_amd_hooks.so is missing: run __graft_entry__.build()"
     env = dict(os.environ, CU2REC_BS_DBG=str(dbg), CU2REC_BS_WAIT_S="0.02", CU2REC_AMD_LIB=hooks)
+    env.pop("CU2REC_BS_GATE", None)
+    env.update(extra_env)
     res = subprocess.run([sys.executable, "-c", _FAULT_SCRIPT % {"root": ROOT}], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                          text=True, timeout=300)
     assert res.returncode == 0, res.stdout[-3000:]
@@ -565,8 +571,16 @@ def test_blocksolve_join_wait_that_is_never_satisfied_ends_in_ehip_and_the_proce
     sent: the event form does not need it) gives the oracle's result, and cu2rec_blocksolve_topology says "events".  In a process of
     its own: the settings are read once."""
     lines = _run_fault_script(16)
-    assert lines[-2] == "STATUS -3 True True", lines[-3:]
+    assert lines[-2] == "STATUS -3 True True False", lines[-3:]
     assert lines[-1].startswith("HEALED ") and float(lines[-1].split()[1]) <= 2e-6, lines[-1]
+
+
+def test_blocksolve_join_that_gives_up_under_a_forced_device_topology_names_the_force():
+    """The same join give-up (CU2REC_BS_DBG=16) with the device form forced by CU2REC_BS_GATE=1: the call still reports CU2REC_EHIP,
+    but nothing switches -- the error names CU2REC_BS_GATE as what keeps the device form instead of announcing events, and
+    cu2rec_blocksolve_topology still says "device"."""
+    lines = _run_fault_script(16, CU2REC_BS_GATE="1")
+    assert lines[-2:] == ["STATUS -3 True False True", "TOPOLOGY device"], lines[-3:]
 
 
 _SWEEP_SCRIPT = r"""
@@ -605,9 +619,9 @@ def test_launch_bounds_too_small_are_swept_and_change_nothing():
     mean + 8 sigma of the positions behind the two-wave chains); what an iteration has in front of that is swept by one extra workgroup.
     The bound is about speed, never about results: in the test build CU2REC_BS_DBG=256 cuts it to 16 positions, so the sweeper does
     nearly the whole walk -- thousands of short chains -- and the ordered mode still equals the oracle bit for bit, the block-solve mode
-    within its rounding, on sets with hundreds to thousands of walked items.  Likewise phases 1 and 3 of a block-solve iteration are
-    launched with the EXPECTED number of blocks (OrderedSchedule::blocks_bound) and stride through the dense block table: with the
-    launch cut to 3 workgroups (bit 512) every one of them does many blocks in turn, LDS tiles reused -- same results."""
+    within its rounding, on sets with hundreds to thousands of walked items.  Likewise phase 3 of a block-solve iteration is launched
+    with the EXPECTED number of blocks (BlockSolve's constructor, blocksolve.hip) and strides through the dense block table (phase 1
+    keeps the full grid): with the launch cut to 3 workgroups (bit 512) every one of them does many blocks in turn -- same results."""
     import subprocess
     import sys
     hooks = os.path.join(ROOT, "build", "test", "libcu2rec_amd_hooks.so")
