@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "als.hpp"
+#include "kernels.hpp"
 #include "score_tile.hpp"
 
 namespace cu2rec {
@@ -405,17 +406,8 @@ void als_plan_side(AlsSide &side, hipStream_t stream) {
 
 int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
     const int nt = (p.n_factors + 2 + 31) / 32;  // columns f + 2: factors, the 1, t
-    switch (nt) {
-        case 1: return run_half_step<1>(c, side, p, max_rows, stream);
-        case 2: return run_half_step<2>(c, side, p, max_rows, stream);
-        case 3: return run_half_step<3>(c, side, p, max_rows, stream);
-        case 4: return run_half_step<4>(c, side, p, max_rows, stream);
-        case 5: return run_half_step<5>(c, side, p, max_rows, stream);
-        case 6: return run_half_step<6>(c, side, p, max_rows, stream);
-        case 7: return run_half_step<7>(c, side, p, max_rows, stream);
-        case 8: return run_half_step<8>(c, side, p, max_rows, stream);
-        default: fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als: n_factors above 252 is not supported");
-    }
+    return dispatch_1_to_8(nt, "cu2rec_model_als: n_factors above 252 is not supported",
+                           [&](auto tiles) { return run_half_step<tiles()>(c, side, p, max_rows, stream); });
 }
 
 }  // namespace cu2rec

@@ -120,6 +120,15 @@ void check_aligned(const void *p, const char *what) {
         fail(CU2REC_EINVAL, std::string(what) + ": factor matrix must be 16-byte aligned");
 }
 
+// The one validation of a factor view: row strides, then alignment.  n_factors > 0 stays in each caller's own "bad shape" check,
+// which names the caller and holds for a loss over no ratings too; so do the null checks: such a loss reads no pointer.
+void check_factors(const FactorsRef &m) {
+    check_ld(m.ldp, m.n_factors, "P");
+    check_ld(m.ldq, m.n_factors, "Q");
+    check_aligned(m.P, "P");
+    check_aligned(m.Q, "Q");
+}
+
 // Per-block partial sums come back to the host and are added there in block order, so the result
 // does not depend on scheduling (the reference also sums its 256 block partials on the host,
 // loss.cu:183-189).
@@ -153,29 +162,25 @@ PartialSums collect_partials(double *device_partials, int blocks, hipStream_t st
 
 }  // namespace
 
-SgdArgs make_sgd_args(const int *indptr, const int *indices, const float *data, int n_rows, int n_cols, float *P,
-                      int ldp, float *Q, int ldq, float *user_bias, float *item_bias, float global_bias, int n_factors,
-                      const cu2rec_hyper &hyper, uint64_t seed, int update_items, int user_offset) {
-    require(indptr && P && Q && user_bias && item_bias, "cu2rec_sgd_update: null device pointer");
-    require(n_rows >= 0 && n_cols >= 0 && n_factors > 0, "cu2rec_sgd_update: bad shape");
-    require(n_rows == 0 || (indices && data), "cu2rec_sgd_update: null device pointer");
-    check_ld(ldp, n_factors, "P");
-    check_ld(ldq, n_factors, "Q");
-    check_aligned(P, "P");
-    check_aligned(Q, "Q");
+SgdArgs make_sgd_args(const RatingsRef &r, const FactorsRef &m, int n_cols, const cu2rec_hyper &hyper, uint64_t seed,
+                      int update_items, int user_offset) {
+    require(r.indptr && m.P && m.Q && m.user_bias && m.item_bias, "cu2rec_sgd_update: null device pointer");
+    require(r.n_rows >= 0 && n_cols >= 0 && m.n_factors > 0, "cu2rec_sgd_update: bad shape");
+    require(r.n_rows == 0 || (r.indices && r.data), "cu2rec_sgd_update: null device pointer");
+    check_factors(m);
     SgdArgs a{};
-    a.indptr = indptr;
-    a.indices = indices;
-    a.data = data;
-    a.P = P;
-    a.Q = Q;
-    a.user_bias = user_bias;
-    a.item_bias = item_bias;
-    a.n_rows = n_rows;
-    a.ldp = ldp;
-    a.ldq = ldq;
-    a.nslots = (n_factors + 3) / 4;
-    a.global_bias = global_bias;
+    a.indptr = r.indptr;
+    a.indices = r.indices;
+    a.data = r.data;
+    a.P = m.P;
+    a.Q = m.Q;
+    a.user_bias = m.user_bias;
+    a.item_bias = m.item_bias;
+    a.n_rows = r.n_rows;
+    a.ldp = m.ldp;
+    a.ldq = m.ldq;
+    a.nslots = (m.n_factors + 3) / 4;
+    a.global_bias = m.global_bias;
     a.h = SgdHyper{hyper.learning_rate, hyper.P_reg, hyper.Q_reg, hyper.user_bias_reg, hyper.item_bias_reg};
     a.seed = seed;
     a.update_items = update_items ? 1 : 0;
@@ -183,16 +188,40 @@ SgdArgs make_sgd_args(const int *indptr, const int *indices, const float *data, 
     return a;
 }
 
-void sgd_update(const int *indptr, const int *indices, const float *data, int n_rows, int n_cols, float *P, int ldp,
-                float *Q, int ldq, float *user_bias, float *item_bias, float global_bias, int n_factors,
-                const cu2rec_hyper &hyper, uint64_t seed, uint64_t iter0, int n_iters, int mode, int update_items,
-                int user_offset, hipStream_t stream, const void *sample_pairs) {
+namespace {
+// the loss pass's argument block, validated like make_sgd_args's (nnz > 0: every array is read)
+LossArgs make_loss_args(const RatingsRef &r, int nnz, const FactorsRef &m, float *errors_out, void *workspace) {
+    require(r.indptr && r.indices && r.data && m.P && m.Q && m.user_bias && m.item_bias && workspace,
+            "cu2rec_loss: null device pointer");
+    check_factors(m);
+    LossArgs a{};
+    a.indptr = r.indptr;
+    a.indices = r.indices;
+    a.data = r.data;
+    a.P = m.P;
+    a.Q = m.Q;
+    a.user_bias = m.user_bias;
+    a.item_bias = m.item_bias;
+    a.n_rows = r.n_rows;
+    a.nnz = nnz;
+    a.ldp = m.ldp;
+    a.ldq = m.ldq;
+    a.nslots = (m.n_factors + 3) / 4;
+    a.global_bias = m.global_bias;
+    a.errors_out = errors_out;
+    a.partials = static_cast<double *>(workspace);
+    return a;
+}
+}  // namespace
+
+void sgd_update(const RatingsRef &r, const FactorsRef &m, int n_cols, const cu2rec_hyper &hyper, uint64_t seed,
+                uint64_t iter0, int n_iters, int mode, int update_items, int user_offset, hipStream_t stream,
+                const void *sample_pairs) {
     require(mode == CU2REC_SGD_HOGWILD || mode == CU2REC_SGD_SERIAL,
             "cu2rec_sgd_update: unknown mode (CU2REC_SGD_ORDERED needs cu2rec_sgd_update_ordered and a schedule)");
     require(n_iters >= 0, "cu2rec_sgd_update: bad iteration count");
-    SgdArgs a = make_sgd_args(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias, global_bias,
-                              n_factors, hyper, seed, update_items, user_offset);
-    if (n_rows == 0 || n_iters == 0) return;
+    SgdArgs a = make_sgd_args(r, m, n_cols, hyper, seed, update_items, user_offset);
+    if (r.n_rows == 0 || n_iters == 0) return;
     require_device();
     check_faults();
     require((reinterpret_cast<uintptr_t>(sample_pairs) & 7u) == 0, "cu2rec_sgd_update: sample pairs must be 8-byte aligned");
@@ -221,22 +250,19 @@ void sgd_update(const int *indptr, const int *indices, const float *data, int n_
     CU2REC_HIP(hipGetLastError());
 }
 
-bool sgd_update_pingpong(const int *indptr, const int *indices, const float *data, int n_rows, int n_cols, float *P,
-                         int ldp, float *Q, float *Q_target, int ldq, float *user_bias, float *item_bias,
-                         float *item_bias_target, unsigned long long *claim, float global_bias, int n_factors,
+bool sgd_update_pingpong(const RatingsRef &r, const FactorsRef &m, int n_cols, const PingPongArgs &other,
                          const cu2rec_hyper &hyper, uint64_t seed, uint64_t iter0, int n_iters, int update_items,
                          int user_offset, bool swap_last, hipStream_t stream) {
     require(n_iters >= 0, "cu2rec_sgd_update_pingpong: bad iteration count");
-    require(Q_target && item_bias_target && claim, "cu2rec_sgd_update_pingpong: null device pointer");
-    check_aligned(Q_target, "Q_target");
-    SgdArgs a = make_sgd_args(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias, global_bias,
-                              n_factors, hyper, seed, update_items, user_offset);
-    if (n_rows == 0 || n_iters == 0) return false;
+    require(other.Q_target && other.item_bias_target && other.claim, "cu2rec_sgd_update_pingpong: null device pointer");
+    check_aligned(other.Q_target, "Q_target");
+    SgdArgs a = make_sgd_args(r, m, n_cols, hyper, seed, update_items, user_offset);
+    if (r.n_rows == 0 || n_iters == 0) return false;
     require_device();
     check_faults();
     // claims carry the iteration number; a call may restart from an earlier one, so they start from "nobody"
-    CU2REC_HIP(hipMemsetAsync(claim, 0xFF, static_cast<size_t>(std::max(n_cols, 1)) * sizeof(unsigned long long), stream));
-    PingPongArgs pp{Q_target, item_bias_target, claim};
+    CU2REC_HIP(hipMemsetAsync(other.claim, 0xFF, static_cast<size_t>(std::max(n_cols, 1)) * sizeof(unsigned long long), stream));
+    PingPongArgs pp = other;
     a.iters = 1;
     bool swapped = false;
     for (int i = 0; i < n_iters; ++i) {  // one claim + one update launch per iteration (training.cu:107-113)
@@ -262,59 +288,32 @@ void sample_pairs_build(const int *indices, const float *data, int nnz, void *pa
     CU2REC_HIP(hipGetLastError());
 }
 
-void sgd_update_ordered(OrderedSchedule &schedule, const int *indptr, const int *indices, const float *data,
-                        int n_rows, int n_cols, float *P, int ldp, float *Q, int ldq, float *user_bias,
-                        float *item_bias, float global_bias, int n_factors, const cu2rec_hyper &hyper, uint64_t seed,
-                        uint64_t iter0, int n_iters, int update_items, int user_offset, hipStream_t stream,
-                        bool blocksolve) {
+void sgd_update_ordered(OrderedSchedule &schedule, const RatingsRef &r, const FactorsRef &m, int n_cols,
+                        const cu2rec_hyper &hyper, uint64_t seed, uint64_t iter0, int n_iters, int update_items,
+                        int user_offset, hipStream_t stream, bool blocksolve) {
     if (!update_items) {
         // frozen items: no two updates of an iteration share a written row, so the parallel schedule IS the
         // sequential result; no chains needed
-        sgd_update(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors,
-                   hyper, seed, iter0, n_iters, CU2REC_SGD_HOGWILD, 0, user_offset, stream);
+        sgd_update(r, m, n_cols, hyper, seed, iter0, n_iters, CU2REC_SGD_HOGWILD, 0, user_offset, stream);
         return;
     }
     require(n_iters >= 0, "cu2rec_sgd_update_ordered: bad iteration count");
-    require(schedule.n_rows == n_rows && schedule.n_cols == n_cols, "cu2rec_sgd_update_ordered: schedule built for another CSR");
-    SgdArgs a = make_sgd_args(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias, global_bias,
-                              n_factors, hyper, seed, update_items, user_offset);
-    if (n_rows == 0 || n_iters == 0) return;
+    require(schedule.n_rows == r.n_rows && schedule.n_cols == n_cols, "cu2rec_sgd_update_ordered: schedule built for another CSR");
+    SgdArgs a = make_sgd_args(r, m, n_cols, hyper, seed, update_items, user_offset);
+    if (r.n_rows == 0 || n_iters == 0) return;
     require_device();
     check_faults();
     schedule.run(a, iter0, n_iters, stream, blocksolve);
 }
 
-void loss(const int *indptr, const int *indices, const float *data, int n_rows, int nnz, const float *P, int ldp,
-          const float *Q, int ldq, const float *user_bias, const float *item_bias, float global_bias, int n_factors,
-          float *errors_out, void *workspace, double *sum_abs, double *sum_sq, float *mae, float *rmse,
-          hipStream_t stream) {
-    require(n_rows >= 0 && nnz >= 0 && n_factors > 0, "cu2rec_loss: bad shape");
+void loss(const RatingsRef &r, int nnz, const FactorsRef &m, float *errors_out, void *workspace, double *sum_abs,
+          double *sum_sq, float *mae, float *rmse, hipStream_t stream) {
+    require(r.n_rows >= 0 && nnz >= 0 && m.n_factors > 0, "cu2rec_loss: bad shape");
     PartialSums s;
     if (nnz > 0) {
-        require(indptr && indices && data && P && Q && user_bias && item_bias && workspace,
-                "cu2rec_loss: null device pointer");
-        check_ld(ldp, n_factors, "P");
-        check_ld(ldq, n_factors, "Q");
-        check_aligned(P, "P");
-        check_aligned(Q, "Q");
+        const LossArgs a = make_loss_args(r, nnz, m, errors_out, workspace);
         require_device();
         check_faults();
-        LossArgs a{};
-        a.indptr = indptr;
-        a.indices = indices;
-        a.data = data;
-        a.P = P;
-        a.Q = Q;
-        a.user_bias = user_bias;
-        a.item_bias = item_bias;
-        a.n_rows = n_rows;
-        a.nnz = nnz;
-        a.ldp = ldp;
-        a.ldq = ldq;
-        a.nslots = (n_factors + 3) / 4;
-        a.global_bias = global_bias;
-        a.errors_out = errors_out;
-        a.partials = static_cast<double *>(workspace);
         const int blocks = loss_blocks(nnz);
         launch_loss(a, blocks, stream);
         CU2REC_HIP(hipGetLastError());
@@ -433,6 +432,8 @@ void DeviceModel::sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t se
                       int update_items, hipStream_t stream, bool defer_last_swap, int user_offset) {
     require(train.rows <= rows && train.max_item < cols, "cu2rec_model_sgd: ratings exceed the model's shape");
     finish_swap();
+    const RatingsRef ratings = train.ref();
+    const FactorsRef factors = ref();  // after finish_swap: Q / item_bias name the current item side
     if (mode == CU2REC_SGD_PINGPONG) {
         if (!Q_other.ptr) {
             Q_other.allocate(Q.count);
@@ -445,10 +446,8 @@ void DeviceModel::sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t se
                                       hipMemcpyDeviceToDevice, stream));
             other_in_sync = true;
         }
-        const bool swapped = sgd_update_pingpong(train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, cols, P.ptr,
-                                                 ld, Q.ptr, Q_other.ptr, ldq, user_bias.ptr, item_bias.ptr,
-                                                 item_bias_other.ptr, claim.ptr, global_bias, n_factors, h, seed, iter0,
-                                                 n_iters, update_items, user_offset, !defer_last_swap, stream);
+        const bool swapped = sgd_update_pingpong(ratings, factors, cols, {Q_other.ptr, item_bias_other.ptr, claim.ptr}, h, seed,
+                                                 iter0, n_iters, update_items, user_offset, !defer_last_swap, stream);
         if (swapped) {  // Q / item_bias always name the current item side
             Q.swap(Q_other);
             item_bias.swap(item_bias_other);
@@ -462,9 +461,8 @@ void DeviceModel::sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t se
             train.schedule.reset(new OrderedSchedule(train.indptr.ptr, train.indices.ptr, train.rows, cols, train.nnz));
             train.schedule->speculate = true;  // the schedule is destroyed with the arrays it reads
         }
-        sgd_update_ordered(*train.schedule, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, cols, P.ptr,
-                           ld, Q.ptr, ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors, h, seed, iter0, n_iters,
-                           update_items, user_offset, stream, mode == CU2REC_SGD_BLOCKSOLVE);
+        sgd_update_ordered(*train.schedule, ratings, factors, cols, h, seed, iter0, n_iters, update_items, user_offset, stream,
+                           mode == CU2REC_SGD_BLOCKSOLVE);
         return;
     }
     const void *pairs = nullptr;
@@ -476,9 +474,7 @@ void DeviceModel::sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t se
         }
         pairs = train.pairs.ptr;
     }
-    sgd_update(train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, cols, P.ptr, ld, Q.ptr, ldq,
-               user_bias.ptr, item_bias.ptr, global_bias, n_factors, h, seed, iter0, n_iters, mode, update_items, user_offset,
-               stream, pairs);
+    sgd_update(ratings, factors, cols, h, seed, iter0, n_iters, mode, update_items, user_offset, stream, pairs);
 }
 
 // Argument checks first: nothing on the device or in the model is touched by a call that fails them.
@@ -530,9 +526,7 @@ void DeviceModel::loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq
                        hipStream_t stream) const {
     // Appendix quirk 6: a test file may have fewer users than train, never more
     require(ratings.rows <= rows && ratings.max_item < cols, "cu2rec_model_loss: ratings exceed the model's shape");
-    cu2rec::loss(ratings.indptr.ptr, ratings.indices.ptr, ratings.data.ptr, ratings.rows, ratings.nnz, P.ptr, ld, Q.ptr,
-                 ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors, nullptr, workspace.ptr, sum_abs, sum_sq, mae,
-                 rmse, stream);
+    cu2rec::loss(ratings.ref(), ratings.nnz, ref(), nullptr, workspace.ptr, sum_abs, sum_sq, mae, rmse, stream);
 }
 
 }  // namespace cu2rec
@@ -586,8 +580,8 @@ int cu2rec_sgd_update(const int *indptr, const int *indices, const float *data, 
                       int user_offset, void *stream) {
     return guarded([&] {
         require(hyper, "cu2rec_sgd_update: hyper is null");
-        sgd_update(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors,
-                   *hyper, seed, iter0, n_iters, mode, update_items, user_offset, as_stream(stream));
+        sgd_update({indptr, indices, data, n_rows}, {P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors}, n_cols, *hyper, seed,
+                   iter0, n_iters, mode, update_items, user_offset, as_stream(stream));
     });
 }
 
@@ -597,8 +591,8 @@ int cu2rec_sgd_update_ex(const int *indptr, const int *indices, const float *dat
                          int user_offset, const void *sample_pairs, void *stream) {
     return guarded([&] {
         require(hyper, "cu2rec_sgd_update_ex: hyper is null");
-        sgd_update(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors,
-                   *hyper, seed, iter0, n_iters, mode, update_items, user_offset, as_stream(stream), sample_pairs);
+        sgd_update({indptr, indices, data, n_rows}, {P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors}, n_cols, *hyper, seed,
+                   iter0, n_iters, mode, update_items, user_offset, as_stream(stream), sample_pairs);
     });
 }
 
@@ -616,9 +610,9 @@ int cu2rec_sgd_update_pingpong(const int *indptr, const int *indices, const floa
                                int *swapped, void *stream) {
     return guarded([&] {
         require(hyper, "cu2rec_sgd_update_pingpong: hyper is null");
-        const bool s = sgd_update_pingpong(indptr, indices, data, n_rows, n_cols, P, ldp, Q, Q_target, ldq, user_bias,
-                                           item_bias, item_bias_target, claim, global_bias, n_factors, *hyper, seed, iter0,
-                                           n_iters, update_items, user_offset, swap_last != 0, as_stream(stream));
+        const bool s = sgd_update_pingpong({indptr, indices, data, n_rows}, {P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors},
+                                           n_cols, {Q_target, item_bias_target, claim}, *hyper, seed, iter0, n_iters, update_items,
+                                           user_offset, swap_last != 0, as_stream(stream));
         if (swapped) *swapped = s ? 1 : 0;
     });
 }
@@ -670,9 +664,8 @@ int cu2rec_sgd_update_ordered(cu2rec_schedule *schedule, const int *indptr, cons
                               void *stream) {
     return guarded([&] {
         require(schedule && hyper, "cu2rec_sgd_update_ordered: null argument");
-        sgd_update_ordered(schedule->impl, indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias,
-                           global_bias, n_factors, *hyper, seed, iter0, n_iters, update_items, user_offset,
-                           as_stream(stream));
+        sgd_update_ordered(schedule->impl, {indptr, indices, data, n_rows}, {P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors},
+                           n_cols, *hyper, seed, iter0, n_iters, update_items, user_offset, as_stream(stream));
     });
 }
 
@@ -683,9 +676,8 @@ int cu2rec_sgd_update_blocksolve(cu2rec_schedule *schedule, const int *indptr, c
                                  void *stream) {
     return guarded([&] {
         require(schedule && hyper, "cu2rec_sgd_update_blocksolve: null argument");
-        sgd_update_ordered(schedule->impl, indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias,
-                           global_bias, n_factors, *hyper, seed, iter0, n_iters, update_items, user_offset,
-                           as_stream(stream), true);
+        sgd_update_ordered(schedule->impl, {indptr, indices, data, n_rows}, {P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors},
+                           n_cols, *hyper, seed, iter0, n_iters, update_items, user_offset, as_stream(stream), true);
     });
 }
 
@@ -731,8 +723,10 @@ int cu2rec_loss(const int *indptr, const int *indices, const float *data, int n_
                 int n_factors, float *errors_out, void *workspace, double *sum_abs, double *sum_sq, float *mae,
                 float *rmse, void *stream) {
     return guarded([&] {
-        loss(indptr, indices, data, n_rows, nnz, P, ldp, Q, ldq, user_bias, item_bias, global_bias, n_factors,
-             errors_out, workspace, sum_abs, sum_sq, mae, rmse, as_stream(stream));
+        // (the view's pointers are not const: one type serves the trainers too; loss() only reads through them)
+        const FactorsRef m{const_cast<float *>(P), ldp, const_cast<float *>(Q), ldq, const_cast<float *>(user_bias),
+                           const_cast<float *>(item_bias), global_bias, n_factors};
+        loss({indptr, indices, data, n_rows}, nnz, m, errors_out, workspace, sum_abs, sum_sq, mae, rmse, as_stream(stream));
     });
 }
 

@@ -16,37 +16,48 @@ struct cu2rec_model;
 
 namespace cu2rec {
 
-// fills the launch argument block after validating shapes / alignment (shared by all SGD modes)
-SgdArgs make_sgd_args(const int *indptr, const int *indices, const float *data, int n_rows, int n_cols, float *P,
-                      int ldp, float *Q, int ldq, float *user_bias, float *item_bias, float global_bias, int n_factors,
-                      const cu2rec_hyper &hyper, uint64_t seed, int update_items, int user_offset);
+// The ratings and the model as the hot path passes them on: plain views, nothing owned.  The extern "C" wrappers (device.cpp) pack
+// their loose parameters into these; an owned object hands out its own (DeviceCsr::ref, DeviceModel::ref).
+struct RatingsRef {
+    const int *indptr, *indices;
+    const float *data;
+    int n_rows;
+};
 
-void sgd_update(const int *indptr, const int *indices, const float *data, int n_rows, int n_cols, float *P, int ldp,
-                float *Q, int ldq, float *user_bias, float *item_bias, float global_bias, int n_factors,
-                const cu2rec_hyper &hyper, uint64_t seed, uint64_t iter0, int n_iters, int mode, int update_items,
-                int user_offset, hipStream_t stream, const void *sample_pairs = nullptr);
+struct FactorsRef {
+    float *P;
+    int ldp;
+    float *Q;
+    int ldq;
+    float *user_bias, *item_bias;
+    float global_bias;
+    int n_factors;
+};
+
+// fills the launch argument block after validating shapes / alignment (shared by all SGD modes)
+SgdArgs make_sgd_args(const RatingsRef &r, const FactorsRef &m, int n_cols, const cu2rec_hyper &hyper, uint64_t seed,
+                      int update_items, int user_offset);
+
+void sgd_update(const RatingsRef &r, const FactorsRef &m, int n_cols, const cu2rec_hyper &hyper, uint64_t seed,
+                uint64_t iter0, int n_iters, int mode, int update_items, int user_offset, hipStream_t stream,
+                const void *sample_pairs = nullptr);
 
 // CU2REC_SGD_PINGPONG on raw pointers (include/cu2rec_amd.h: cu2rec_sgd_update_pingpong); returns true if the item
-// side's current values ended up in Q_target / item_bias_target (odd number of swaps)
-bool sgd_update_pingpong(const int *indptr, const int *indices, const float *data, int n_rows, int n_cols, float *P,
-                         int ldp, float *Q, float *Q_target, int ldq, float *user_bias, float *item_bias,
-                         float *item_bias_target, unsigned long long *claim, float global_bias, int n_factors,
+// side's current values ended up in other.Q_target / other.item_bias_target (odd number of swaps)
+bool sgd_update_pingpong(const RatingsRef &r, const FactorsRef &m, int n_cols, const PingPongArgs &other,
                          const cu2rec_hyper &hyper, uint64_t seed, uint64_t iter0, int n_iters, int update_items,
                          int user_offset, bool swap_last, hipStream_t stream);
 
 // [nnz] x {item, rating} side by side for SgdArgs::pairs (8 bytes per rating, device memory)
 void sample_pairs_build(const int *indices, const float *data, int nnz, void *pairs, hipStream_t stream);
 
-void sgd_update_ordered(OrderedSchedule &schedule, const int *indptr, const int *indices, const float *data,
-                        int n_rows, int n_cols, float *P, int ldp, float *Q, int ldq, float *user_bias,
-                        float *item_bias, float global_bias, int n_factors, const cu2rec_hyper &hyper, uint64_t seed,
-                        uint64_t iter0, int n_iters, int update_items, int user_offset, hipStream_t stream,
-                        bool blocksolve = false);
+void sgd_update_ordered(OrderedSchedule &schedule, const RatingsRef &r, const FactorsRef &m, int n_cols,
+                        const cu2rec_hyper &hyper, uint64_t seed, uint64_t iter0, int n_iters, int update_items,
+                        int user_offset, hipStream_t stream, bool blocksolve = false);
 
-void loss(const int *indptr, const int *indices, const float *data, int n_rows, int nnz, const float *P, int ldp,
-          const float *Q, int ldq, const float *user_bias, const float *item_bias, float global_bias, int n_factors,
-          float *errors_out, void *workspace, double *sum_abs, double *sum_sq, float *mae, float *rmse,
-          hipStream_t stream);
+// reads the model only
+void loss(const RatingsRef &r, int nnz, const FactorsRef &m, float *errors_out, void *workspace, double *sum_abs,
+          double *sum_sq, float *mae, float *rmse, hipStream_t stream);
 
 void error_metrics(const float *errors, int n, void *workspace, float *mae, float *rmse, hipStream_t stream);
 
@@ -55,6 +66,7 @@ struct DeviceCsr {
     DeviceCsr(int rows, int cols, int nnz, const int *h_indptr, const int *h_indices, const float *h_data);
     DeviceBuffer<int> indptr, indices;
     DeviceBuffer<float> data;
+    RatingsRef ref() const { return {indptr.ptr, indices.ptr, data.ptr, rows}; }
     int rows, cols, nnz;
     int max_item;
     int users_with_ratings;
@@ -77,6 +89,7 @@ struct DeviceModel {
     int als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream);
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
               hipStream_t stream) const;
+    FactorsRef ref() const { return {P.ptr, ld, Q.ptr, ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors}; }
     DeviceBuffer<float> P, Q, user_bias, item_bias;
     DeviceBuffer<float> Q_other, item_bias_other;  // CU2REC_SGD_PINGPONG: the second buffer pair, created on first use
     DeviceBuffer<unsigned long long> claim;

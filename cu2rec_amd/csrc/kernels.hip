@@ -313,33 +313,13 @@ void launch_loss_j(const LossArgs &a, int blocks, hipStream_t stream) {
 int slots_per_lane(int nslots) { return (nslots + kGroup - 1) / kGroup; }
 
 void launch_sgd(const SgdArgs &a, int mode, hipStream_t stream) {
-    switch (slots_per_lane(a.nslots)) {
-        case 1: launch_sgd_j<1>(a, mode, stream); break;
-        case 2: launch_sgd_j<2>(a, mode, stream); break;
-        case 3: launch_sgd_j<3>(a, mode, stream); break;
-        case 4: launch_sgd_j<4>(a, mode, stream); break;
-        case 5: launch_sgd_j<5>(a, mode, stream); break;
-        case 6: launch_sgd_j<6>(a, mode, stream); break;
-        case 7: launch_sgd_j<7>(a, mode, stream); break;
-        case 8: launch_sgd_j<8>(a, mode, stream); break;
-        default: fail(CU2REC_EUNSUPPORTED, "n_factors above 512 is not compiled in");
-    }
+    dispatch_row_width(a.nslots, [&](auto j) { launch_sgd_j<j()>(a, mode, stream); });
 }
 
 void launch_sgd_pingpong(const SgdArgs &a, const PingPongArgs &pp, hipStream_t stream) {
     hipLaunchKernelGGL(pingpong_claim_kernel, dim3(blocks_for(static_cast<size_t>(a.n_rows), kBlock, 4096)), dim3(kBlock), 0,
                        stream, a, pp);
-    switch (slots_per_lane(a.nslots)) {
-        case 1: launch_pingpong_j<1>(a, pp, stream); break;
-        case 2: launch_pingpong_j<2>(a, pp, stream); break;
-        case 3: launch_pingpong_j<3>(a, pp, stream); break;
-        case 4: launch_pingpong_j<4>(a, pp, stream); break;
-        case 5: launch_pingpong_j<5>(a, pp, stream); break;
-        case 6: launch_pingpong_j<6>(a, pp, stream); break;
-        case 7: launch_pingpong_j<7>(a, pp, stream); break;
-        case 8: launch_pingpong_j<8>(a, pp, stream); break;
-        default: fail(CU2REC_EUNSUPPORTED, "n_factors above 512 is not compiled in");
-    }
+    dispatch_row_width(a.nslots, [&](auto j) { launch_pingpong_j<j()>(a, pp, stream); });
 }
 
 int loss_blocks(int nnz) {
@@ -348,17 +328,7 @@ int loss_blocks(int nnz) {
 }
 
 void launch_loss(const LossArgs &a, int blocks, hipStream_t stream) {
-    switch (slots_per_lane(a.nslots)) {
-        case 1: launch_loss_j<1>(a, blocks, stream); break;
-        case 2: launch_loss_j<2>(a, blocks, stream); break;
-        case 3: launch_loss_j<3>(a, blocks, stream); break;
-        case 4: launch_loss_j<4>(a, blocks, stream); break;
-        case 5: launch_loss_j<5>(a, blocks, stream); break;
-        case 6: launch_loss_j<6>(a, blocks, stream); break;
-        case 7: launch_loss_j<7>(a, blocks, stream); break;
-        case 8: launch_loss_j<8>(a, blocks, stream); break;
-        default: fail(CU2REC_EUNSUPPORTED, "n_factors above 512 is not compiled in");
-    }
+    dispatch_row_width(a.nslots, [&](auto j) { launch_loss_j<j()>(a, blocks, stream); });
 }
 
 namespace {

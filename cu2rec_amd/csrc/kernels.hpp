@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -66,6 +67,30 @@ struct PingPongArgs {
 constexpr int kMaxPartialBlocks = 4096;
 
 int slots_per_lane(int nslots);
+
+// f(std::integral_constant<int, J>{}) for the J in 1 .. 8 that equals j: the one place a run-time width picks among the compiled
+// kernel templates; any other j fails with `unsupported`
+template <class F>
+auto dispatch_1_to_8(int j, const char *unsupported, F &&f) -> decltype(f(std::integral_constant<int, 1>{})) {
+    switch (j) {
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        default: fail(CU2REC_EUNSUPPORTED, unsupported);
+    }
+}
+
+// the row-width dispatch of every SGD and loss launch: J = float4 slots per lane of a row of nslots slots
+template <class F>
+void dispatch_row_width(int nslots, F &&f) {
+    dispatch_1_to_8(slots_per_lane(nslots), "n_factors above 512 is not compiled in", f);
+}
+
 void launch_sgd(const SgdArgs &args, int mode, hipStream_t stream);
 // one iteration (args.iter0) of CU2REC_SGD_PINGPONG: claim kernel + update kernel; args.Q / item_bias are only read
 void launch_sgd_pingpong(const SgdArgs &args, const PingPongArgs &pp, hipStream_t stream);

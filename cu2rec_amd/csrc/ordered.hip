@@ -46,6 +46,7 @@
 #include <vector>
 
 #include "hip_check.hpp"
+#include "item_rates.hpp"
 #include "kernels.hpp"
 #include "ordered.hpp"
 #include "sampler.hpp"
@@ -635,17 +636,9 @@ void launch_chain(const SgdArgs &a, const uint32_t *keys, const uint64_t *vals, 
 
 void launch_chains(const SgdArgs &a, const uint32_t *kb, const uint64_t *vb, int n_active, const int *item_of_rank,
                    uint32_t item_mask, int n_hot, hipStream_t stream, int rank_lo, const int *ranges, hipEvent_t stop, int walk_bound) {
-    switch (slots_per_lane(a.nslots)) {
-        case 1: launch_chain<1>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 2: launch_chain<2>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 3: launch_chain<3>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 4: launch_chain<4>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 5: launch_chain<5>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 6: launch_chain<6>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 7: launch_chain<7>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        case 8: launch_chain<8>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound); break;
-        default: fail(CU2REC_EUNSUPPORTED, "n_factors above 512 is not compiled in");
-    }
+    dispatch_row_width(a.nslots, [&](auto j) {
+        launch_chain<j()>(a, kb, vb, n_active, item_of_rank, item_mask, n_hot, stream, rank_lo, ranges, stop, walk_bound);
+    });
 }
 
 int bits_for(int n) {  // bits needed to represent values in [0, n)
@@ -669,17 +662,10 @@ OrderedSchedule::OrderedSchedule(const int *d_indptr, const int *d_indices, int 
     // popularity = expected updates per iteration: every user draws one of its ratings uniformly (sgd.cu:36-37), so an
     // item collects sum over its raters of 1 / degree; descending, ties by item id.  Ranks only order the chains
     // (longest first) and pick the hot ones; results do not depend on them.
-    std::vector<double> rate(n_cols, 0.0);
+    std::vector<double> rate(n_cols);
     std::vector<int> order(n_cols), rank(n_cols);
-    for (int u = 0; u < n_rows; ++u) {
-        const int low = indptr[u], high = indptr[u + 1];
-        require(low <= high && high <= nnz, "ordered schedule: bad indptr");
-        const double w = high > low ? 1.0 / (high - low) : 0.0;
-        for (int k = low; k < high; ++k) {
-            require(indices[k] >= 0 && indices[k] < n_cols, "ordered schedule: item id out of range");
-            rate[indices[k]] += w;
-        }
-    }
+    for (int u = 0; u < n_rows; ++u) require(indptr[u] <= indptr[u + 1] && indptr[u + 1] <= nnz, "ordered schedule: bad indptr");
+    item_update_rates(indptr.data(), indices.data(), n_rows, n_cols, rate.data());
     std::iota(order.begin(), order.end(), 0);
     std::stable_sort(order.begin(), order.end(), [&](int l, int r) { return rate[l] > rate[r]; });
     for (int r = 0; r < n_cols; ++r) rank[order[r]] = r;
