@@ -1,6 +1,8 @@
 """CPU checks of alternating least squares: the float64 reference (tests/als_reference64.py) against hand-solved cases and its own
 normal equations, and the host side of the new interface -- the C entry point's argument check, the constants the header and the
-Python package share, the usage lines of bin/mf and bin/predict."""
+Python package share, the usage lines of bin/mf and bin/predict.  Also the judge of the GPU edge tests itself: the rounding bound of
+als_reference64.row_residual holds for a float32 restatement of the row solve on every conditioning set of tests/als_checks.py,
+and three deliberate mistakes in that restatement break it."""
 import os
 import re
 import subprocess
@@ -11,6 +13,7 @@ import cu2rec_amd as cu
 from cu2rec_amd import api, synth
 from conftest import ROOT
 
+import als_checks as chk
 import als_reference64 as ref
 
 
@@ -120,3 +123,73 @@ def test_predict_usage_lists_A():
     res = subprocess.run([os.path.join(ROOT, "bin", "predict"), "-c", "x"], stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                          text=True)
     assert res.returncode != 0 and "[-A]" in res.stderr, res.stderr
+
+
+def _f32_ratios(case, rows=None, mutation=None, forward=None):
+    """{row: max |A x - b| / bound, or None where the float32 restatement meets a bad pivot} over the rows of a Case; with
+    `forward` (a dict) also {row: max |x - x*| / (1e-3 max(1, |x*|_inf))} into it."""
+    c = case.csr
+    out = {}
+    with np.errstate(all="ignore"):
+        for r in (range(c.rows) if rows is None else rows):
+            x = ref.solve_row_f32(c.indptr, c.indices, c.data, case.X, case.xb, c.global_bias, case.reg, case.reg_b, r, mutation)
+            if x is None:
+                out[r] = None
+                continue
+            A, b, res, bound = ref.row_residual(c.indptr, c.indices, c.data, case.X, case.xb, c.global_bias, case.reg, case.reg_b, r, x)
+            out[r] = ref.residual_ratio(res, bound)
+            if forward is not None:
+                xs = np.linalg.solve(A, b)
+                forward[r] = float(np.abs(x - xs).max() / (1e-3 * max(1.0, np.abs(xs).max())))
+    return out
+
+
+def test_float32_restatement_meets_the_residual_bound_on_every_conditioning_set():
+    """The inputs of test_gpu_als_edges.py's conditioning classes are fair: plain float32 arithmetic solves every row outside the
+    class `singular` and stays within row_residual's bound everywhere; a singular row either meets a bad pivot or is within it.
+    It also meets the forward bar on every row on which Case.well_conditioned() puts that bar in force for the GPU."""
+    for f in (8, 100):
+        for case in chk.conditioning_cases(f):
+            fwd = {}
+            ratios = _f32_ratios(case, forward=fwd)
+            failed = [r for r, v in ratios.items() if v is None]
+            worst = max((v for v in ratios.values() if v is not None), default=0.0)
+            barred = np.flatnonzero(case.well_conditioned())
+            worst_fwd = max((fwd[r] for r in barred), default=0.0)
+            print("f=%d %-9s rows=%d worst residual/bound=%.3g unsolved=%d; forward bar on %d rows, worst error/bar=%.3g"
+                  % (f, case.name, case.csr.rows, worst, len(failed), len(barred), worst_fwd))
+            if not case.singular:
+                assert not failed, (f, case.name, [(r, case.class_of[r]) for r in failed])
+                assert len(barred) >= 5
+            assert worst <= 1.0, (f, case.name, worst)
+            assert worst_fwd <= 1.0, (f, case.name, [(r, case.class_of[r], fwd[r]) for r in barred if fwd[r] > 1.0])
+
+
+def test_residual_bound_has_teeth():
+    """Three mistakes a kernel could make each leave the bound, on both well-conditioned sets (base and bias0): the two
+    regularisers swapped and the regulariser scaled by n - 1 (judged on the rows of at most 64 ratings, where an error of
+    ~reg |x| stands above n^2 u), and one rating dropped at the chunk boundary of a 1,025-rating row.  A mutated solve that meets
+    a bad pivot counts as noticed (the GPU tests require every such row to be solved): swapping in a factor regulariser of 0
+    (bias0) leaves rows of fewer ratings than factors singular.  n - 1 is not judged on the one-rating row: there it removes the
+    regulariser altogether and leaves z z^T, which has no solution to hold against a bound."""
+    for f in (8, 100):
+        for base in chk.conditioning_cases(f)[:2]:
+            assert base.name in ("base", "bias0")
+            short = base.classes["short"]
+            assert base.csr.indptr[short[0] + 1] - base.csr.indptr[short[0]] == 1
+            clean = _f32_ratios(base, short)
+            assert max(clean.values()) <= 1.0
+            for mutation in ("swap_reg", "n_minus_1"):
+                judged = short[1:] if mutation == "n_minus_1" else short
+                got = _f32_ratios(base, judged, mutation)
+                missed = [r for r in judged if got[r] is not None and got[r] <= 1.0]
+                print("f=%d %s %s: smallest residual/bound %.3g, bad pivot on %d rows"
+                      % (f, base.name, mutation, min((v for v in got.values() if v is not None), default=np.inf),
+                         sum(v is None for v in got.values())))
+                assert not missed, (f, base.name, mutation, [(r, got[r]) for r in missed])
+            row = base.classes["long"][0]
+            assert base.csr.indptr[row + 1] - base.csr.indptr[row] == 1025
+            assert _f32_ratios(base, [row])[row] <= 1.0
+            dropped = _f32_ratios(base, [row], "drop_1024")[row]
+            print("f=%d %s drop_1024: residual/bound %.3g" % (f, base.name, dropped))
+            assert dropped > 1.0, (f, base.name, dropped)

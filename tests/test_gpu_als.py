@@ -3,7 +3,9 @@ the float64 reference of tests/als_reference64.py.
 
 The bar for a solved row x (factors and bias) against the float64 optimum x* of the same system, built from the same float32
 inputs: max |x - x*| <= 1e-3 max(1, |x*|_inf), and the float64 objective after the GPU half-step at most the optimum's (1 + 1e-6).
-Rows the half-step does not own or cannot solve stay bit for bit."""
+Rows the half-step does not own or cannot solve stay bit for bit.  That forward bar says little where a system is badly conditioned
+and is loose where it is not: tests/test_gpu_als_edges.py also judges a row by its residual against the rounding bound derived in
+als_reference64.row_residual.  The judge itself (_check_half_step) lives in tests/als_checks.py, shared with that file."""
 import ctypes as C
 import os
 import subprocess
@@ -17,77 +19,13 @@ from cu2rec_amd._lib import lib
 from conftest import ROOT, ml_small
 
 import als_reference64 as ref
+from als_checks import HYPER, als as _als, bigger_model as _bigger_model, check_half_step as _check_half_step
+from als_checks import rows_with_ratings as _rows_with_ratings
 
 pytestmark = pytest.mark.gpu
 
-HYPER = (0.01, 0.05, 0.04, 0.02, 0.03)  # (learning rate: ignored, P_reg, Q_reg, user_bias_reg, item_bias_reg)
 EINVAL, EUNSUPPORTED = -1, -6
 _CACHE = {}
-
-
-def _hip():
-    if "hip" not in _CACHE:
-        lib()
-        h = C.CDLL("libamdhip64.so.7")
-        h.hipMemcpy.restype = C.c_int
-        h.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-        _CACHE["hip"] = h
-    return _CACHE["hip"]
-
-
-def _q_padding(model, f):
-    _, Q, _, _ = model.device_ptrs()
-    ldq = lib().cu2rec_model_item_stride(model._h)
-    out = np.empty((model.cols, ldq), np.float32)
-    assert _hip().hipMemcpy(out.ctypes.data, Q, out.nbytes, 2) == 0
-    return out[:, f:]
-
-
-def _als(model, d_csr, hyper, side):
-    n = C.c_int(-1)
-    h = cu.Hyper(*[float(x) for x in hyper])
-    rc = lib().cu2rec_model_als(model._h, d_csr._h, C.byref(h), api.SIDES[side], C.byref(n))
-    return rc, n.value
-
-
-def _rows_with_ratings(csr, side):
-    counts = np.diff(csr.indptr) if side == "users" else np.bincount(csr.indices, minlength=csr.cols)
-    return np.flatnonzero(counts > 0)
-
-
-def _check_half_step(model, d_csr, csr, side, hyper=HYPER):
-    """One GPU half-step against the float64 reference from the same float32 state; returns the state after it."""
-    f = model.n_factors
-    before = model.download()
-    pad_before = _q_padding(model, f)
-    rc, unsolved = _als(model, d_csr, hyper, side)
-    assert rc == 0 and unsolved == 0, (rc, unsolved, lib().cu2rec_last_error())
-    got = model.download()
-    want = ref.half_step(csr, *before, csr.global_bias, hyper, side)
-    own = (0, 2) if side == "users" else (1, 3)
-    other = (1, 3) if side == "users" else (0, 2)
-    for k in other:
-        assert np.array_equal(got[k], before[k]), "the other side moved (%s half-step, f=%d)" % (side, f)
-    solved = _rows_with_ratings(csr, side)
-    untouched = np.setdiff1d(np.arange(len(before[own[1]])), solved)
-    for k in own:  # rows without ratings, and model rows past the CSR, keep their values bit for bit
-        assert np.array_equal(got[k][untouched], before[k][untouched]), (side, f)
-    x = np.concatenate([got[own[0]][solved].astype(np.float64), got[own[1]][solved, None]], axis=1)
-    xs = np.concatenate([want[own[0]][solved], want[own[1]][solved, None]], axis=1)
-    err = np.abs(x - xs).max(axis=1)
-    bar = 1e-3 * np.maximum(1.0, np.abs(xs).max(axis=1))
-    worst = int(np.argmax(err / bar))
-    assert (err <= bar).all(), (side, f, int(solved[worst]), float(err[worst]), float(bar[worst]))
-    L_got = ref.objective(csr, *got, csr.global_bias, hyper)
-    L_opt = ref.objective(csr, *want, csr.global_bias, hyper)
-    assert L_got <= L_opt * (1 + 1e-6), (side, f, L_got, L_opt)
-    assert np.array_equal(_q_padding(model, f), pad_before) and not pad_before.any()
-    return got
-
-
-def _bigger_model(csr, f, extra_rows=3, extra_cols=5):
-    """A model with rows / items past the CSR (they must stay as they are)."""
-    return cu.Model(csr.rows + extra_rows, csr.cols + extra_cols, f, csr.global_bias)
 
 
 @pytest.mark.parametrize("f", [1, 3, 4, 31, 32, 33, 64, 100, 127, 128, 129, 200, 252])
