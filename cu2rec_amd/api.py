@@ -296,6 +296,28 @@ class Model:
                 total += n.value
         return total
 
+    def ials(self, train, hyper, alpha=40.0, side="both", sweeps=1):
+        """Implicit-feedback half-steps (cu2rec_model_als_implicit): every user x item pair of train's shape counts, a stored entry
+        (u, i, r) with confidence weight alpha * r; no biases.  side and sweeps as in als(); of hyper only P_reg and Q_reg are read.
+        Rows without entries become zero rows.  Returns the number of rows left unchanged by a failed pivot."""
+        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        if side not in ALS_SIDES:
+            raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        total = 0
+        for _ in range(int(sweeps)):
+            for s in ALS_SIDES[side]:
+                n = C.c_int()
+                check(lib().cu2rec_model_als_implicit(self._h, train._h, C.byref(h), float(alpha), s, C.byref(n)))
+                total += n.value
+        return total
+
+    def implicit_objective(self, train, hyper, alpha):
+        """The objective ials() minimises, at the model's current values (cu2rec_model_implicit_objective) -> float."""
+        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        L = C.c_double()
+        check(lib().cu2rec_model_implicit_objective(self._h, train._h, C.byref(h), float(alpha), C.byref(L)))
+        return L.value
+
     def loss(self, ratings):
         """calculate_loss_gpu + get_error_metrics_gpu (loss.cu:40-49,195-200) -> dict(mae, rmse, sum_abs, sum_sq)."""
         sa, ss, mae, rmse = C.c_double(), C.c_double(), C.c_float(), C.c_float()
@@ -406,22 +428,29 @@ def default_mode(n_factors):
 
 
 def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=None, mode=None, verbose=True,
-          P=None, user_bias=None, return_stats=False):
+          P=None, user_bias=None, return_stats=False, alpha=40.0):
     """train() (training.h:12-15).  mode None = default_mode(cfg.n_factors); "hogwild" opts into sgd.cu's racy semantics; "als"
-    trains by alternating least squares (one iteration = one sweep; no learning rate, so no decay).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
+    trains by alternating least squares (one iteration = one sweep; no learning rate, so no decay); "ials" by its implicit-feedback
+    form with confidence weight alpha * r (cu2rec_train_implicit: test_matrix is not read and may be None, and the third element
+    returned is the objective at the checked sweeps, float64, NaN elsewhere).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
     otherwise everything starts from the seed-42 normal init.  Returns (P, Q, losses, user_bias,
     item_bias) like the reference's out-pointers; cfg.learning_rate / cfg.cur_iterations are
     updated in place."""
     tr = train_matrix if isinstance(train_matrix, DeviceCSR) else DeviceCSR(train_matrix)
-    te = test_matrix if isinstance(test_matrix, DeviceCSR) else DeviceCSR(test_matrix)
     gb = tr.host.global_bias if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
-    losses = np.empty(max(cfg.total_iterations, 1), np.float32)
     stats = TrainStats()
-    mode = default_mode(cfg.n_factors) if mode is None else mode
-    check(lib().cu2rec_train(tr._h, te._h, C.byref(cfg), model._h, _mode(mode), 1 if verbose else 0, _ptr(losses),
-                             C.byref(stats)))
+    if mode == "ials":
+        losses = np.empty(max(cfg.total_iterations, 1), np.float64)
+        check(lib().cu2rec_train_implicit(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses),
+                                          C.byref(stats)))
+    else:
+        te = test_matrix if isinstance(test_matrix, DeviceCSR) else DeviceCSR(test_matrix)
+        losses = np.empty(max(cfg.total_iterations, 1), np.float32)
+        mode = default_mode(cfg.n_factors) if mode is None else mode
+        check(lib().cu2rec_train(tr._h, te._h, C.byref(cfg), model._h, _mode(mode), 1 if verbose else 0, _ptr(losses),
+                                 C.byref(stats)))
     Pn, Qn, ub, ib = model.download()
     model.close()
     out = (Pn, Qn, losses[:cfg.total_iterations], ub, ib)

@@ -13,12 +13,22 @@
 // counts it (integer atomic).  Everything a row's result depends on -- staging, accumulation order, the chunk cut of a long row
 // and the order its partial Grams are summed in, the factorisation -- is a function of the row's own length: no float atomics,
 // nothing that depends on the batch or the other rows.
+//
+// The implicit-feedback half-step (cu2rec_model_als_implicit) is the same machinery with three differences, each a case of AlsKind
+// in the templates below.  (1) Every partner row counts, so a half-step first forms G0 = X^T X over partner rows [0, n): the rows
+// are tiled kAlsChunk at a time, one workgroup per tile gathers BY ROW NUMBER and accumulates exactly as above (AlsKind::Gram),
+// the tiles' partial Grams go to the workspace and a second kernel adds them in tile order into a buffer kept in the accumulator
+// layout [pair][16][64].  (2) A row's own entries are staged as two operands, A = [w q | 1 + w] and B = [q | 0] (w = alpha r), so
+// that the product's first f rows are sum w q q^T and its row f is the right-hand side sum (1 + w) q; the accumulators start from
+// G0 (AlsKind::Implicit).  (3) The system has order f (no bias), plain reg on the diagonal, and a row without entries is written
+// as zeros.
 #include <hip/hip_runtime.h>
 
 #include <cstring>  // (rocPRIM's headers call memset without including it)
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
+#include <string>
 
 #include "als.hpp"
 #include "kernels.hpp"
@@ -31,13 +41,18 @@ namespace {
 constexpr int kAlsThreads = 512;
 constexpr int kAlsWaves = kAlsThreads / 64;
 
+// What a kernel template is compiled for: the explicit half-step ([x | 1 | t] staged once, order f + 1), the implicit one (two
+// operands, seeded from G0, order f), or a tile of the global Gram G0 itself ([x | 0] gathered by row number).
+enum class AlsKind { Explicit, Implicit, Gram };
+
 struct AlsArgs {
     const int *indptr, *indices;
     const float *data;
     AlsProblem p;
     const int *long_rows, *long_first_chunk, *chunk_lo, *chunk_hi;
-    int chunk0, row0;  // first chunk / first long row of the batch
+    int chunk0, row0;  // first chunk / first long row of the batch (AlsKind::Gram: chunk = tile of kAlsChunk partner rows)
     float *ws;         // the batch's partial Grams: [chunk][pair][16][64]
+    const float *g0;   // AlsKind::Implicit: X^T X over partner rows [0, p.x_rows), [pair][16][64]
     int *unsolved;
 };
 
@@ -60,10 +75,12 @@ __host__ __device__ inline size_t solve_lds_floats(int f) {  // packed augmented
     return static_cast<size_t>(tri(f + 2)) + 3 * static_cast<size_t>(f + 4) + 4;
 }
 
-// acc += the augmented Gram of ratings [lo, hi) of the current row, kAlsStep ratings per LDS stage
-template <int NT>
+// acc += the augmented Gram of ratings [lo, hi) of the current row, kAlsStep ratings per LDS stage.  AlsKind::Gram: [lo, hi) are
+// partner row numbers.  AlsKind::Implicit: the A operand is staged at zs, the B operand kAlsStep x C floats behind it.
+template <int NT, AlsKind K>
 __device__ void als_accumulate(const AlsArgs &a, int lo, int hi, f32x16 (&acc)[AlsShape<NT>::per_wave], float *zs) {
     constexpr int C = AlsShape<NT>::C, S4 = C / 4, pairs = AlsShape<NT>::pairs;
+    constexpr int b_off = K == AlsKind::Implicit ? kAlsStep * C : 0;  // the B operand's stage (the A operand's own otherwise)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
     const int F = a.p.n_factors;
     float4 *zs4 = reinterpret_cast<float4 *>(zs);
@@ -72,22 +89,45 @@ __device__ void als_accumulate(const AlsArgs &a, int lo, int hi, f32x16 (&acc)[A
         for (int e = tid; e < kAlsStep * S4; e += kAlsThreads) {
             const int row = e / S4, s = e - row * S4, k = k0 + row, c0 = 4 * s;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            [[maybe_unused]] float4 va = v;  // AlsKind::Implicit: [w x | 1 + w | 0]
             if (k < hi) {
-                const int idx = a.indices[k];
+                const int idx = K == AlsKind::Gram ? k : a.indices[k];
                 if (c0 < F) v = *reinterpret_cast<const float4 *>(a.p.X + static_cast<size_t>(idx) * a.p.ldx + c0);
-                if (c0 + 3 >= F) {  // columns F (the constant 1), F + 1 (t) and zero fill
-                    float t = 0.f;
-                    if (c0 <= F + 1 && F + 1 <= c0 + 3) t = (a.data[k] - a.p.global_bias) - a.p.xb[idx];
-                    auto fix = [&](float &x, int c) {
-                        if (c >= F) x = c == F ? 1.f : (c == F + 1 ? t : 0.f);
-                    };
-                    fix(v.x, c0);
-                    fix(v.y, c0 + 1);
-                    fix(v.z, c0 + 2);
-                    fix(v.w, c0 + 3);
+                if constexpr (K == AlsKind::Explicit) {
+                    if (c0 + 3 >= F) {  // columns F (the constant 1), F + 1 (t) and zero fill
+                        float t = 0.f;
+                        if (c0 <= F + 1 && F + 1 <= c0 + 3) t = (a.data[k] - a.p.global_bias) - a.p.xb[idx];
+                        auto fix = [&](float &x, int c) {
+                            if (c >= F) x = c == F ? 1.f : (c == F + 1 ? t : 0.f);
+                        };
+                        fix(v.x, c0);
+                        fix(v.y, c0 + 1);
+                        fix(v.z, c0 + 2);
+                        fix(v.w, c0 + 3);
+                    }
+                } else {
+                    if (c0 + 3 >= F) {  // zero fill from column F on
+                        if (c0 >= F) v.x = 0.f;
+                        if (c0 + 1 >= F) v.y = 0.f;
+                        if (c0 + 2 >= F) v.z = 0.f;
+                        if (c0 + 3 >= F) v.w = 0.f;
+                    }
+                    if constexpr (K == AlsKind::Implicit) {
+                        const float w = a.p.alpha * a.data[k];
+                        va = make_float4(w * v.x, w * v.y, w * v.z, w * v.w);
+                        if (c0 == F) va.x = 1.f + w;  // column F of the A operand: the right-hand side's weight
+                        if (c0 + 1 == F) va.y = 1.f + w;
+                        if (c0 + 2 == F) va.z = 1.f + w;
+                        if (c0 + 3 == F) va.w = 1.f + w;
+                    }
                 }
             }
-            zs4[row * S4 + s] = v;
+            if constexpr (K == AlsKind::Implicit) {
+                zs4[row * S4 + s] = va;
+                zs4[b_off / 4 + row * S4 + s] = v;
+            } else {
+                zs4[row * S4 + s] = v;
+            }
         }
         __syncthreads();
         // A[i][k] = Z[k][32 ti + i], B[k][j] = Z[k][32 tj + j]: lane (r, h) feeds row 2 kk + h of the stage
@@ -97,7 +137,7 @@ __device__ void als_accumulate(const AlsArgs &a, int lo, int hi, f32x16 (&acc)[A
             if (p < pairs) {
                 int ti, tj;
                 pair_tiles(p, ti, tj);
-                const float *za = zs + h * C + 32 * ti + r, *zb = zs + h * C + 32 * tj + r;
+                const float *za = zs + h * C + 32 * ti + r, *zb = zs + b_off + h * C + 32 * tj + r;
 #pragma unroll
                 for (int kk = 0; kk < kAlsStep / 2; ++kk)
                     acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(za[2 * kk * C], zb[2 * kk * C], acc[s], 0, 0, 0);
@@ -106,12 +146,14 @@ __device__ void als_accumulate(const AlsArgs &a, int lo, int hi, f32x16 (&acc)[A
     }
 }
 
-// the accumulated augmented Gram of `row` (n ratings) -> Cholesky in LDS -> the row's factors and bias, or counted as unsolved
-template <int NT>
+// the accumulated augmented Gram of `row` (n ratings) -> Cholesky in LDS -> the row's factors and bias, or counted as unsolved.
+// AlsKind::Implicit: order f, plain reg on the diagonal, the bias written as 0.
+template <int NT, AlsKind K>
 __device__ void als_solve(const AlsArgs &a, int row, int n, f32x16 (&acc)[AlsShape<NT>::per_wave], float *lds) {
     constexpr int pairs = AlsShape<NT>::pairs;
+    constexpr bool with_bias = K == AlsKind::Explicit;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, r = lane & 31, h = lane >> 5;
-    const int F = a.p.n_factors, D = F + 1;  // system order D; row D of the augmented triangle is the right-hand side
+    const int F = a.p.n_factors, D = F + (with_bias ? 1 : 0);  // system order D; row D of the augmented triangle is the right-hand side
     float *G = lds, *col = G + tri(D + 1), *x = col + (D + 3), *xo = x + (D + 3);
     int *bad = reinterpret_cast<int *>(xo + (D + 3));  // (no __syncthreads_or: its static LDS would cap the dynamic LDS below 160 KiB)
     __syncthreads();  // G overlays the staging area
@@ -128,7 +170,7 @@ __device__ void als_solve(const AlsArgs &a, int row, int n, f32x16 (&acc)[AlsSha
                 const int i = 32 * ti + acc_row(reg, h);
                 if (j <= i && i <= D) {
                     float v = acc[s][reg];
-                    if (i == j && i < D) v = v + nf * (i < F ? a.p.reg : a.p.reg_bias);
+                    if (i == j && i < D) v = v + (with_bias ? nf * (i < F ? a.p.reg : a.p.reg_bias) : a.p.reg);
                     G[tri(i) + j] = v;
                 }
             }
@@ -181,7 +223,7 @@ __device__ void als_solve(const AlsArgs &a, int row, int n, f32x16 (&acc)[AlsSha
     }
     float *y = a.p.Y + static_cast<size_t>(row) * a.p.ldy;
     for (int c = tid; c < a.p.ldy; c += kAlsThreads) y[c] = c < F ? xo[c] : 0.f;
-    if (tid == 0) a.p.yb[row] = xo[F];
+    if (tid == 0) a.p.yb[row] = with_bias ? xo[F] : 0.f;
 }
 
 template <int NT>
@@ -192,30 +234,64 @@ __device__ inline void zero_acc(f32x16 (&acc)[AlsShape<NT>::per_wave]) {
         for (int i = 0; i < 16; ++i) acc[s][i] = 0.f;
 }
 
-// rows of 1 .. kAlsChunk ratings: one workgroup each, gather, Gram and solve
+// acc += one Gram in the accumulator layout [pair][16][64] (a chunk's partial Gram, or G0)
 template <int NT>
+__device__ inline void add_gram(f32x16 (&acc)[AlsShape<NT>::per_wave], const float *gram) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int s = 0; s < AlsShape<NT>::per_wave; ++s) {
+        const int p = wave + kAlsWaves * s;
+        if (p < AlsShape<NT>::pairs) {
+            const float *src = gram + static_cast<size_t>(p) * 16 * 64 + lane;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) acc[s][reg] = acc[s][reg] + src[reg * 64];
+        }
+    }
+}
+
+// the accumulators a row starts from: zero, or G0 for the implicit half-step
+template <int NT, AlsKind K>
+__device__ inline void seed_acc(const AlsArgs &a, f32x16 (&acc)[AlsShape<NT>::per_wave]) {
+    zero_acc<NT>(acc);
+    if constexpr (K == AlsKind::Implicit) add_gram<NT>(acc, a.g0);
+}
+
+// rows of 1 .. kAlsChunk ratings: one workgroup each, gather, Gram and solve.  AlsKind::Implicit: a row without entries has right-hand
+// side 0, so its minimiser is the zero row: written, not factorised, not counted.
+template <int NT, AlsKind K>
 __global__ __launch_bounds__(kAlsThreads) void als_short_kernel(AlsArgs a) {
     extern __shared__ float4 als_smem[];
     float *lds = reinterpret_cast<float *>(als_smem);
     const int row = blockIdx.x;
     const int lo = a.indptr[row], hi = a.indptr[row + 1];
-    if (hi <= lo || hi - lo > kAlsChunk) return;
+    if (hi <= lo) {
+        if constexpr (K == AlsKind::Implicit) {
+            float *y = a.p.Y + static_cast<size_t>(row) * a.p.ldy;
+            for (int c = threadIdx.x; c < a.p.ldy; c += kAlsThreads) y[c] = 0.f;
+            if (threadIdx.x == 0) a.p.yb[row] = 0.f;
+        }
+        return;
+    }
+    if (hi - lo > kAlsChunk) return;
     f32x16 acc[AlsShape<NT>::per_wave];
-    zero_acc<NT>(acc);
-    als_accumulate<NT>(a, lo, hi, acc, lds);
-    als_solve<NT>(a, row, hi - lo, acc, lds);
+    seed_acc<NT, K>(a, acc);
+    als_accumulate<NT, K>(a, lo, hi, acc, lds);
+    als_solve<NT, K>(a, row, hi - lo, acc, lds);
 }
 
-// one chunk of a long row: its partial Gram to the batch workspace, lane-major (coalesced)
-template <int NT>
+// one chunk of a long row (AlsKind::Gram: one tile of kAlsChunk partner rows): its partial Gram to the batch workspace, lane-major
+// (coalesced)
+template <int NT, AlsKind K>
 __global__ __launch_bounds__(kAlsThreads) void als_chunk_kernel(AlsArgs a) {
     extern __shared__ float4 als_smem[];
     float *lds = reinterpret_cast<float *>(als_smem);
     constexpr int pairs = AlsShape<NT>::pairs;
     const int c = a.chunk0 + blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int lo = K == AlsKind::Gram ? c * kAlsChunk : a.chunk_lo[c];
+    const int hi = K == AlsKind::Gram ? min(lo + kAlsChunk, a.p.x_rows) : a.chunk_hi[c];
     f32x16 acc[AlsShape<NT>::per_wave];
     zero_acc<NT>(acc);
-    als_accumulate<NT>(a, a.chunk_lo[c], a.chunk_hi[c], acc, lds);
+    als_accumulate<NT, K>(a, lo, hi, acc, lds);
 #pragma unroll
     for (int s = 0; s < AlsShape<NT>::per_wave; ++s) {
         const int p = wave + kAlsWaves * s;
@@ -227,40 +303,78 @@ __global__ __launch_bounds__(kAlsThreads) void als_chunk_kernel(AlsArgs a) {
     }
 }
 
-// a long row: its chunks' partial Grams summed in chunk order, then the solve
-template <int NT>
+// a long row: its chunks' partial Grams summed in chunk order (AlsKind::Implicit: onto G0), then the solve
+template <int NT, AlsKind K>
 __global__ __launch_bounds__(kAlsThreads) void als_long_kernel(AlsArgs a) {
     extern __shared__ float4 als_smem[];
     float *lds = reinterpret_cast<float *>(als_smem);
-    constexpr int pairs = AlsShape<NT>::pairs;
-    const int lr = a.row0 + blockIdx.x, row = a.long_rows[lr], wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    constexpr size_t gram_floats = static_cast<size_t>(AlsShape<NT>::pairs) * 16 * 64;
+    const int lr = a.row0 + blockIdx.x, row = a.long_rows[lr];
     const int c_begin = a.long_first_chunk[lr] - a.chunk0, c_end = a.long_first_chunk[lr + 1] - a.chunk0;
     f32x16 acc[AlsShape<NT>::per_wave];
-    zero_acc<NT>(acc);
-    for (int c = c_begin; c < c_end; ++c) {
-#pragma unroll
-        for (int s = 0; s < AlsShape<NT>::per_wave; ++s) {
-            const int p = wave + kAlsWaves * s;
-            if (p < pairs) {
-                const float *src = a.ws + (static_cast<size_t>(c) * pairs + p) * 16 * 64 + lane;
-#pragma unroll
-                for (int reg = 0; reg < 16; ++reg) acc[s][reg] = acc[s][reg] + src[reg * 64];
-            }
-        }
-    }
-    als_solve<NT>(a, row, a.indptr[row + 1] - a.indptr[row], acc, lds);
+    seed_acc<NT, K>(a, acc);
+    for (int c = c_begin; c < c_end; ++c) add_gram<NT>(acc, a.ws + c * gram_floats);
+    als_solve<NT, K>(a, row, a.indptr[row + 1] - a.indptr[row], acc, lds);
 }
 
+// G0: the tiles' partial Grams added in tile order, element by element; `first`: the first batch of tiles starts from zero
+__global__ void als_gram_sum_kernel(const float *__restrict__ ws, int tiles, size_t gram_floats, float *__restrict__ g0, int first) {
+    const size_t e = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (e >= gram_floats) return;
+    float s = first ? 0.f : g0[e];
+    for (int t = 0; t < tiles; ++t) s = s + ws[t * gram_floats + e];
+    g0[e] = s;
+}
+
+void ensure_workspace(AlsCache &c, size_t floats) {
+    if (c.workspace.count < floats) c.workspace.allocate(floats);
+}
+
+// out = X^T X over rows [0, n) of X in the accumulator layout of NT tiles, through the workspace in batches of whole tiles
 template <int NT>
+void run_global_gram(AlsCache &c, const float *X, int ldx, int n, int n_factors, DeviceBuffer<float> &out, hipStream_t stream) {
+    constexpr size_t gram_floats = static_cast<size_t>(AlsShape<NT>::pairs) * 16 * 64;
+    const size_t stage_bytes = static_cast<size_t>(kAlsStep) * AlsShape<NT>::C * sizeof(float);
+    if (out.count < gram_floats) out.allocate(gram_floats);
+    const int tiles = (n + kAlsChunk - 1) / kAlsChunk;
+    if (tiles == 0) {
+        CU2REC_HIP(hipMemsetAsync(out.ptr, 0, gram_floats * sizeof(float), stream));
+        return;
+    }
+    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_chunk_kernel<NT, AlsKind::Gram>), kMaxLds);
+    const int batch_tiles = static_cast<int>(kAlsWorkspaceBytes / (gram_floats * sizeof(float)));
+    ensure_workspace(c, std::min(batch_tiles, tiles) * gram_floats);
+    AlsArgs a{};
+    a.p.X = X;
+    a.p.ldx = ldx;
+    a.p.n_factors = n_factors;
+    a.p.x_rows = n;
+    a.ws = c.workspace.ptr;
+    const int sum_threads = 256, sum_blocks = static_cast<int>((gram_floats + sum_threads - 1) / sum_threads);
+    for (int t0 = 0; t0 < tiles; t0 += batch_tiles) {
+        const int nt = std::min(batch_tiles, tiles - t0);
+        a.chunk0 = t0;
+        hipLaunchKernelGGL((als_chunk_kernel<NT, AlsKind::Gram>), dim3(nt), dim3(kAlsThreads), stage_bytes, stream, a);
+        CU2REC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(als_gram_sum_kernel, dim3(sum_blocks), dim3(sum_threads), 0, stream, c.workspace.ptr, nt, gram_floats, out.ptr,
+                           t0 == 0 ? 1 : 0);
+        CU2REC_HIP(hipGetLastError());
+    }
+}
+
+template <int NT, AlsKind K>
 int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
     constexpr int pairs = AlsShape<NT>::pairs;
-    const size_t stage_bytes = static_cast<size_t>(kAlsStep) * AlsShape<NT>::C * sizeof(float);
+    constexpr int operands = K == AlsKind::Implicit ? 2 : 1;
+    const size_t stage_bytes = static_cast<size_t>(operands) * kAlsStep * AlsShape<NT>::C * sizeof(float);
     const size_t solve_bytes = (solve_lds_floats(p.n_factors) * sizeof(float) + 15) & ~static_cast<size_t>(15);
     const size_t short_bytes = std::max(stage_bytes, solve_bytes);
-    if (short_bytes > kMaxLds) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als: n_factors too large for the LDS of one workgroup");
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_short_kernel<NT>), kMaxLds);
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_chunk_kernel<NT>), kMaxLds);
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_long_kernel<NT>), kMaxLds);
+    if (short_bytes > kMaxLds)
+        fail(CU2REC_EUNSUPPORTED, std::string(K == AlsKind::Implicit ? "cu2rec_model_als_implicit" : "cu2rec_model_als") +
+                                      ": n_factors too large for the LDS of one workgroup");
+    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_short_kernel<NT, K>), kMaxLds);
+    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_chunk_kernel<NT, K>), kMaxLds);
+    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_long_kernel<NT, K>), kMaxLds);
     if (!c.unsolved.ptr) c.unsolved.allocate(1);
     CU2REC_HIP(hipMemsetAsync(c.unsolved.ptr, 0, sizeof(int), stream));
     AlsArgs a{};
@@ -273,9 +387,13 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
     a.chunk_lo = side.d_chunk_lo.ptr;
     a.chunk_hi = side.d_chunk_hi.ptr;
     a.unsolved = c.unsolved.ptr;
+    if constexpr (K == AlsKind::Implicit) {  // once per half-step, before the workspace holds the long rows' chunks
+        run_global_gram<NT>(c, p.X, p.ldx, p.x_rows, p.n_factors, c.g0, stream);
+        a.g0 = c.g0.ptr;
+    }
     const int grid = std::min(side.rows, max_rows);
     if (grid > 0)
-        hipLaunchKernelGGL(als_short_kernel<NT>, dim3(grid), dim3(kAlsThreads), short_bytes, stream, a);
+        hipLaunchKernelGGL((als_short_kernel<NT, K>), dim3(grid), dim3(kAlsThreads), short_bytes, stream, a);
     CU2REC_HIP(hipGetLastError());
     const int L = static_cast<int>(side.long_rows.size());
     if (L > 0) {
@@ -284,7 +402,7 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
         const int batch_chunks = static_cast<int>(kAlsWorkspaceBytes / (gram_floats * sizeof(float)));
         static_assert(kAlsWorkspaceBytes / (36 * 16 * 64 * sizeof(float)) >= kAlsMaxChunks, "workspace below one row's chunks");
         const int needed = std::min(batch_chunks, side.long_first_chunk[L]);
-        if (c.workspace.count < needed * gram_floats) c.workspace.allocate(needed * gram_floats);
+        ensure_workspace(c, needed * gram_floats);
         a.ws = c.workspace.ptr;
         for (int r = 0; r < L;) {
             const int c0 = side.long_first_chunk[r];
@@ -292,9 +410,9 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
             while (r1 < L && side.long_first_chunk[r1 + 1] - c0 <= batch_chunks) ++r1;
             a.chunk0 = c0;
             a.row0 = r;
-            hipLaunchKernelGGL(als_chunk_kernel<NT>, dim3(side.long_first_chunk[r1] - c0), dim3(kAlsThreads), stage_bytes, stream, a);
+            hipLaunchKernelGGL((als_chunk_kernel<NT, K>), dim3(side.long_first_chunk[r1] - c0), dim3(kAlsThreads), stage_bytes, stream, a);
             CU2REC_HIP(hipGetLastError());
-            hipLaunchKernelGGL(als_long_kernel<NT>, dim3(r1 - r), dim3(kAlsThreads), solve_bytes, stream, a);
+            hipLaunchKernelGGL((als_long_kernel<NT, K>), dim3(r1 - r), dim3(kAlsThreads), solve_bytes, stream, a);
             CU2REC_HIP(hipGetLastError());
             r = r1;
         }
@@ -303,6 +421,96 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
     CU2REC_HIP(hipMemcpyAsync(&unsolved, c.unsolved.ptr, sizeof(int), hipMemcpyDeviceToHost, stream));
     CU2REC_HIP(hipStreamSynchronize(stream));
     return unsolved;
+}
+
+// ---- the implicit objective ----------------------------------------------------------------------------------------------
+constexpr int kObjThreads = 256, kObjGroup = 16, kObjMaxBlocks = 4096;
+
+struct IalsObjectiveArgs {
+    const int *indptr, *indices;
+    const float *data;
+    const float *P, *Q;
+    int ldp, ldq, rows, cols, nnz, n_factors;
+    float alpha;
+    double *partials;  // [blocks][3]: entries term, sum |p_u|^2, sum |q_i|^2
+};
+
+// x . y over the first f floats of two rows, in double, by one 16-lane group; every lane returns the sum
+__device__ inline double group_dot(const float *x, const float *y, int f, int lane16) {
+    double d = 0.0;
+    for (int c0 = 4 * lane16; c0 < f; c0 += 4 * kObjGroup) {
+        const float4 a = *reinterpret_cast<const float4 *>(x + c0), b = *reinterpret_cast<const float4 *>(y + c0);
+        d += static_cast<double>(a.x) * static_cast<double>(b.x);
+        if (c0 + 1 < f) d += static_cast<double>(a.y) * static_cast<double>(b.y);
+        if (c0 + 2 < f) d += static_cast<double>(a.z) * static_cast<double>(b.z);
+        if (c0 + 3 < f) d += static_cast<double>(a.w) * static_cast<double>(b.w);
+    }
+    for (int m = kObjGroup / 2; m > 0; m >>= 1) d += __shfl_xor(d, m, kObjGroup);
+    return d;
+}
+
+// one pass over the entries and the rows of both sides, a 16-lane group per entry / row, sums in double; per-block partials
+__global__ __launch_bounds__(kObjThreads) void ials_objective_kernel(IalsObjectiveArgs a) {
+    __shared__ double red[3][kObjThreads];
+    const int tid = threadIdx.x, lane16 = tid & (kObjGroup - 1);
+    const int group = (blockIdx.x * kObjThreads + tid) / kObjGroup, groups = gridDim.x * (kObjThreads / kObjGroup);
+    double s_e = 0.0, s_p = 0.0, s_q = 0.0;
+    for (int k = group; k < a.nnz; k += groups) {
+        int lo = 0, hi = a.rows;  // the last u with indptr[u] <= k
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (a.indptr[mid] <= k) lo = mid;
+            else hi = mid - 1;
+        }
+        const double s = group_dot(a.P + static_cast<size_t>(lo) * a.ldp, a.Q + static_cast<size_t>(a.indices[k]) * a.ldq, a.n_factors, lane16);
+        const double w = static_cast<double>(a.alpha * a.data[k]);
+        if (lane16 == 0) s_e += w * (1.0 - s) * (1.0 - s) + 1.0 - 2.0 * s;
+    }
+    for (int u = group; u < a.rows; u += groups) {
+        const float *x = a.P + static_cast<size_t>(u) * a.ldp;
+        const double n2 = group_dot(x, x, a.n_factors, lane16);
+        if (lane16 == 0) s_p += n2;
+    }
+    for (int i = group; i < a.cols; i += groups) {
+        const float *x = a.Q + static_cast<size_t>(i) * a.ldq;
+        const double n2 = group_dot(x, x, a.n_factors, lane16);
+        if (lane16 == 0) s_q += n2;
+    }
+    red[0][tid] = s_e;
+    red[1][tid] = s_p;
+    red[2][tid] = s_q;
+    for (int stride = kObjThreads / 2; stride > 0; stride >>= 1) {
+        __syncthreads();
+        if (tid < stride)
+            for (int j = 0; j < 3; ++j) red[j][tid] += red[j][tid + stride];
+    }
+    if (tid == 0)
+        for (int j = 0; j < 3; ++j) a.partials[3 * blockIdx.x + j] = red[j][0];
+}
+
+// out[0..2] = the block partials added in block order; out[3] = <G_P, G_Q> over the full symmetric matrices: the Grams hold the
+// tile pairs ti >= tj as whole 32 x 32 tiles, so an off-diagonal pair counts twice.  One workgroup, fixed order.
+__global__ __launch_bounds__(kObjThreads) void ials_objective_reduce_kernel(const double *__restrict__ partials, int blocks,
+                                                                            const float *__restrict__ gp, const float *__restrict__ gq,
+                                                                            int pairs, double *__restrict__ out) {
+    __shared__ double red[4][kObjThreads];
+    const int tid = threadIdx.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = tid; b < blocks; b += kObjThreads)
+        for (int j = 0; j < 3; ++j) s[j] += partials[3 * b + j];
+    for (int e = tid; e < pairs * 16 * 64; e += kObjThreads) {
+        int ti, tj;
+        pair_tiles(e / (16 * 64), ti, tj);
+        s[3] += (ti == tj ? 1.0 : 2.0) * (static_cast<double>(gp[e]) * static_cast<double>(gq[e]));
+    }
+    for (int j = 0; j < 4; ++j) red[j][tid] = s[j];
+    for (int stride = kObjThreads / 2; stride > 0; stride >>= 1) {
+        __syncthreads();
+        if (tid < stride)
+            for (int j = 0; j < 4; ++j) red[j][tid] += red[j][tid + stride];
+    }
+    if (tid == 0)
+        for (int j = 0; j < 4; ++j) out[j] = red[j][0];
 }
 
 // ---- the item-major view -------------------------------------------------------------------------------------------------
@@ -407,7 +615,35 @@ void als_plan_side(AlsSide &side, hipStream_t stream) {
 int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
     const int nt = (p.n_factors + 2 + 31) / 32;  // columns f + 2: factors, the 1, t
     return dispatch_1_to_8(nt, "cu2rec_model_als: n_factors above 252 is not supported",
-                           [&](auto tiles) { return run_half_step<tiles()>(c, side, p, max_rows, stream); });
+                           [&](auto tiles) { return run_half_step<tiles(), AlsKind::Explicit>(c, side, p, max_rows, stream); });
+}
+
+int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
+    return dispatch_1_to_8(ials_tiles(p.n_factors), "cu2rec_model_als_implicit: n_factors above 252 is not supported",
+                           [&](auto tiles) { return run_half_step<tiles(), AlsKind::Implicit>(c, side, p, max_rows, stream); });
+}
+
+double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t stream) {
+    const int nt = ials_tiles(o.n_factors);
+    dispatch_1_to_8(nt, "cu2rec_model_implicit_objective: n_factors above 252 is not supported", [&](auto tiles) {
+        run_global_gram<tiles()>(c, o.P, o.ldp, o.rows, o.n_factors, c.g0, stream);
+        run_global_gram<tiles()>(c, o.Q, o.ldq, o.cols, o.n_factors, c.g0_other, stream);
+    });
+    const size_t work = static_cast<size_t>(std::max(o.nnz, std::max(o.rows, o.cols)));
+    const int per_block = (kObjThreads / kObjGroup) * 8;  // eight entries per group
+    const int blocks = static_cast<int>(std::min<size_t>(std::max<size_t>((work + per_block - 1) / per_block, 1), kObjMaxBlocks));
+    if (c.objective.count < 3 * static_cast<size_t>(kObjMaxBlocks) + 4) c.objective.allocate(3 * static_cast<size_t>(kObjMaxBlocks) + 4);
+    IalsObjectiveArgs a{o.indptr, o.indices, o.data, o.P, o.Q, o.ldp, o.ldq, o.rows, o.cols, o.nnz, o.n_factors, o.alpha, c.objective.ptr};
+    hipLaunchKernelGGL(ials_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, a);
+    CU2REC_HIP(hipGetLastError());
+    double *out = c.objective.ptr + 3 * static_cast<size_t>(kObjMaxBlocks);
+    hipLaunchKernelGGL(ials_objective_reduce_kernel, dim3(1), dim3(kObjThreads), 0, stream, c.objective.ptr, blocks, c.g0.ptr, c.g0_other.ptr,
+                       tri(nt), out);
+    CU2REC_HIP(hipGetLastError());
+    double sums[4];
+    CU2REC_HIP(hipMemcpyAsync(sums, out, sizeof(sums), hipMemcpyDeviceToHost, stream));
+    CU2REC_HIP(hipStreamSynchronize(stream));
+    return 0.5 * (sums[3] + sums[0] + static_cast<double>(o.P_reg) * sums[1] + static_cast<double>(o.Q_reg) * sums[2]);
 }
 
 }  // namespace cu2rec

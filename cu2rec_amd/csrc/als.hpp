@@ -1,7 +1,8 @@
 // Alternating least squares (include/cu2rec_amd.h: cu2rec_model_als): one exact half-step solves every row of one side of
 // the model against the other side, frozen.  For a row with n ratings, Z is the n x (f + 2) matrix of its gathered partner
 // rows [x_i, 1, t_i] (t_i = r - gb - partner bias); the augmented Gram Z^T Z is formed on the matrix cores and the row's
-// (f + 1)-order system is solved by Cholesky in LDS (als.hip).
+// (f + 1)-order system is solved by Cholesky in LDS (als.hip).  The implicit-feedback half-step (cu2rec_model_als_implicit) runs on the
+// same kernels: every partner row enters through G0 = X^T X, a row's entries add sum w x x^T, and the system has order f.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -53,6 +54,10 @@ struct AlsCache {
     DeviceBuffer<float> t_data;
     DeviceBuffer<float> workspace;  // the partial Grams of one batch of long rows, kAlsWorkspaceBytes at most
     DeviceBuffer<int> unsolved;
+    // implicit feedback: X^T X of the partner side (and of the other side, for the objective) in the accumulator layout
+    // [tile pair][16][64] of als.hip, rebuilt by every call that reads it; the objective pass's per-block partial sums
+    DeviceBuffer<float> g0, g0_other;
+    DeviceBuffer<double> objective;
 };
 
 struct AlsProblem {
@@ -64,7 +69,26 @@ struct AlsProblem {
     float *yb;
     int n_factors;
     float global_bias, reg, reg_bias;
+    float alpha = 0.f;  // implicit half-step only: an entry's weight is alpha * r; the partner rows are [0, x_rows)
+    int x_rows = 0;
 };
+
+// the implicit objective (include/cu2rec_amd.h: cu2rec_model_implicit_objective) over the user-major CSR and rows [0, rows) of P,
+// [0, cols) of Q
+struct AlsObjectiveProblem {
+    const int *indptr, *indices;
+    const float *data;
+    int rows, cols, nnz;
+    const float *P;
+    int ldp;
+    const float *Q;
+    int ldq;
+    int n_factors;
+    float alpha, P_reg, Q_reg;
+};
+
+// 32-column tiles of the implicit half-step's staged operands: f factor columns and the right-hand side's weight
+inline int ials_tiles(int n_factors) { return (n_factors + 1 + 31) / 32; }
 
 // builds the transpose of (indptr, indices, data) [rows x cols] into the cache's t_* buffers
 void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, const float *data, int rows, int cols, int nnz,
@@ -73,5 +97,10 @@ void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, con
 void als_plan_side(AlsSide &side, hipStream_t stream);
 // one half-step over every row of `side` (rows < max_rows); returns the number of rows left unchanged by a failed pivot
 int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream);
+// the implicit-feedback half-step: G0 = X^T X over partner rows [0, p.x_rows), then every row of `side` -- rows without entries become
+// zero rows; p.global_bias, p.reg_bias and p.xb are not read, the solved biases are written as 0.  Returns als_half_step's count
+int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream);
+// the implicit objective L (two global Grams, one pass over the entries and both sides' rows in double); synchronises the stream
+double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t stream);
 
 }  // namespace cu2rec

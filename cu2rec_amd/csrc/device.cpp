@@ -477,6 +477,38 @@ void DeviceModel::sgd(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t se
     sgd_update(ratings, factors, cols, h, seed, iter0, n_iters, mode, update_items, user_offset, stream, pairs);
 }
 
+namespace {
+// The rows one ALS half-step solves, as it reads them: the CSR itself for the users, its item-major view for the items -- built on
+// the device, and either side planned, the first time it is asked for.
+AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream) {
+    if (!train.als) train.als.reset(new AlsCache);
+    AlsCache &c = *train.als;
+    if (users) {
+        if (!c.users_ready) {
+            c.users.indptr = train.indptr.ptr;
+            c.users.indices = train.indices.ptr;
+            c.users.data = train.data.ptr;
+            c.users.rows = train.rows;
+            c.users.nnz = train.nnz;
+            als_plan_side(c.users, stream);
+            c.users_ready = true;
+        }
+        return c.users;
+    }
+    if (!c.items_ready) {  // the item-major view, built on the device once per rating matrix
+        als_build_transpose(c, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz, stream);
+        c.items.indptr = c.t_indptr.ptr;
+        c.items.indices = c.t_indices.ptr;
+        c.items.data = c.t_data.ptr;
+        c.items.rows = train.cols;
+        c.items.nnz = train.nnz;
+        als_plan_side(c.items, stream);
+        c.items_ready = true;
+    }
+    return c.items;
+}
+}  // namespace
+
 // Argument checks first: nothing on the device or in the model is touched by a call that fails them.
 int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream) {
     require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, "cu2rec_model_als: side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
@@ -489,37 +521,50 @@ int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hi
     require_device();
     check_faults();
     finish_swap();
-    if (!train.als) train.als.reset(new AlsCache);
+    AlsSide &rows_of_side = als_side(train, users, stream);
     AlsCache &c = *train.als;
-    int unsolved = 0;
-    if (users) {
-        if (!c.users_ready) {
-            c.users.indptr = train.indptr.ptr;
-            c.users.indices = train.indices.ptr;
-            c.users.data = train.data.ptr;
-            c.users.rows = train.rows;
-            c.users.nnz = train.nnz;
-            als_plan_side(c.users, stream);
-            c.users_ready = true;
-        }
-        const AlsProblem p{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, global_bias, reg, reg_bias};
-        unsolved = als_half_step(c, c.users, p, rows, stream);
-    } else {
-        if (!c.items_ready) {  // the item-major view, built on the device once per rating matrix
-            als_build_transpose(c, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz, stream);
-            c.items.indptr = c.t_indptr.ptr;
-            c.items.indices = c.t_indices.ptr;
-            c.items.data = c.t_data.ptr;
-            c.items.rows = train.cols;
-            c.items.nnz = train.nnz;
-            als_plan_side(c.items, stream);
-            c.items_ready = true;
-        }
-        const AlsProblem p{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, global_bias, reg, reg_bias};
-        unsolved = als_half_step(c, c.items, p, cols, stream);
-    }
+    const AlsProblem p = users ? AlsProblem{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, global_bias, reg, reg_bias}
+                               : AlsProblem{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, global_bias, reg, reg_bias};
+    const int unsolved = als_half_step(c, rows_of_side, p, users ? rows : cols, stream);
     other_in_sync = false;  // Q moved on without the ping-pong pair
     return unsolved;
+}
+
+// Implicit feedback (include/cu2rec_amd.h: cu2rec_model_als_implicit).  The same order as als(): argument checks, then the device.
+int DeviceModel::ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream) {
+    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, "cu2rec_model_als_implicit: side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    const bool users = side == CU2REC_SIDE_USERS;
+    const float reg = users ? h.P_reg : h.Q_reg;
+    require(std::isfinite(reg) && reg > 0.f, "cu2rec_model_als_implicit: the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
+    require(std::isfinite(alpha) && alpha >= 0.f, "cu2rec_model_als_implicit: alpha must be finite and >= 0");
+    require(train.rows <= rows && train.max_item < cols && train.cols <= cols, "cu2rec_model_als_implicit: ratings exceed the model's shape");
+    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als_implicit: n_factors above 252 is not supported");
+    require_device();
+    check_faults();
+    finish_swap();
+    AlsSide &rows_of_side = als_side(train, users, stream);
+    AlsProblem p = users ? AlsProblem{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, 0.f, reg, 0.f}
+                         : AlsProblem{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, 0.f, reg, 0.f};
+    p.alpha = alpha;
+    p.x_rows = users ? train.cols : train.rows;  // every partner row inside the CSR counts
+    const int unsolved = ials_half_step(*train.als, rows_of_side, p, users ? rows : cols, stream);
+    other_in_sync = false;
+    return unsolved;
+}
+
+double DeviceModel::implicit_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream) {
+    require(std::isfinite(h.P_reg) && h.P_reg >= 0.f && std::isfinite(h.Q_reg) && h.Q_reg >= 0.f,
+            "cu2rec_model_implicit_objective: the factor regularisers must be finite and >= 0");
+    require(std::isfinite(alpha) && alpha >= 0.f, "cu2rec_model_implicit_objective: alpha must be finite and >= 0");
+    require(train.rows <= rows && train.max_item < cols && train.cols <= cols, "cu2rec_model_implicit_objective: ratings exceed the model's shape");
+    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_implicit_objective: n_factors above 252 is not supported");
+    require_device();
+    check_faults();
+    finish_swap();
+    if (!train.als) train.als.reset(new AlsCache);
+    const AlsObjectiveProblem o{train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz,
+                                P.ptr, ld, Q.ptr, ldq, n_factors, alpha, h.P_reg, h.Q_reg};
+    return ials_objective(*train.als, o, stream);
 }
 
 void DeviceModel::loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
@@ -817,6 +862,22 @@ int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hype
         require(m && train && hyper, "cu2rec_model_als: null argument");
         const int n = m->impl.als(train->impl, *hyper, side, nullptr);
         if (unsolved) *unsolved = n;
+    });
+}
+
+int cu2rec_model_als_implicit(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
+                              int *unsolved) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_als_implicit: null argument");
+        const int n = m->impl.ials(train->impl, *hyper, alpha, side, nullptr);
+        if (unsolved) *unsolved = n;
+    });
+}
+
+int cu2rec_model_implicit_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, double *L) {
+    return guarded([&] {
+        require(m && train && hyper && L, "cu2rec_model_implicit_objective: null argument");
+        *L = m->impl.implicit_objective(train->impl, *hyper, alpha, nullptr);
     });
 }
 

@@ -72,7 +72,7 @@ struct DeviceCsr {
     int users_with_ratings;
     mutable std::unique_ptr<OrderedSchedule> schedule;  // created on first CU2REC_SGD_ORDERED use
     mutable DeviceBuffer<uint2> pairs;                   // sample array, created on first Hogwild use (SgdArgs::pairs)
-    mutable std::unique_ptr<AlsCache> als;               // item-major view and row plans, created on first cu2rec_model_als use
+    mutable std::unique_ptr<AlsCache> als;               // item-major view and row plans, created on first ALS use
 };
 
 // P, Q, biases on the device with padded rows (see include/cu2rec_amd.h "Device data layout").
@@ -87,6 +87,10 @@ struct DeviceModel {
     void finish_swap();
     // one exact ALS half-step (side: CU2REC_SIDE_USERS / CU2REC_SIDE_ITEMS); returns the rows a failed pivot left unchanged
     int als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream);
+    // one implicit-feedback half-step (confidence weight alpha * r per entry, every user x item pair counted); same return
+    int ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream);
+    // the implicit objective at the current model (synchronises)
+    double implicit_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream);
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
               hipStream_t stream) const;
     FactorsRef ref() const { return {P.ptr, ld, Q.ptr, ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors}; }

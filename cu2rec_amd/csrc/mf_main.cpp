@@ -2,7 +2,7 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als] [-g gpus] [-s sync_every]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|ials] [-a alpha] [-g gpus] [-s sync_every]
 //          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
@@ -269,7 +269,7 @@ int run_multi_gpu(int nranks, int mode, int sync_every, int merge, const std::st
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als] [-g gpus] [-s sync_every] "
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|ials] [-a alpha] [-g gpus] [-s sync_every] "
                         "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
@@ -281,9 +281,17 @@ int main(int argc, char **argv) {
     int rank_k = 0;  // -k: 0 = no ranking line
     bool rank_given = false;
     float rank_threshold = -INFINITY;
+    bool implicit = false;  // -m ials: implicit-feedback ALS (cu2rec_train_implicit), not a cu2rec_sgd_mode
+    float alpha = 40.f;     // -a: its confidence weight per unit of r
     int opt;
-    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:")) != -1) {
         switch (opt) {
+            case 'a': {
+                char *end = nullptr;
+                alpha = std::strtof(optarg, &end);
+                if (end == optarg || *end != '\0') alpha = NAN;  // not a number: refused below
+                break;
+            }
             case 'k':
                 rank_given = true;
                 rank_k = std::atoi(optarg);
@@ -311,7 +319,9 @@ int main(int argc, char **argv) {
                 break;
             case 'm':
                 g_mode_given = true;
-                mode = std::strcmp(optarg, "serial") == 0    ? CU2REC_SGD_SERIAL
+                implicit = std::strcmp(optarg, "ials") == 0;
+                mode = implicit ? CU2REC_ALS
+                       : std::strcmp(optarg, "serial") == 0    ? CU2REC_SGD_SERIAL
                        : std::strcmp(optarg, "ordered") == 0 ? CU2REC_SGD_ORDERED
                        : std::strcmp(optarg, "pingpong") == 0 ? CU2REC_SGD_PINGPONG
                        : std::strcmp(optarg, "blocksolve") == 0 ? CU2REC_SGD_BLOCKSOLVE
@@ -339,9 +349,13 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -k is single-GPU only (not with -g)\n";
         return 1;
     }
+    if (implicit && !(std::isfinite(alpha) && alpha >= 0.f)) {
+        std::cerr << "mf: -a must be a finite number >= 0\n";
+        return 1;
+    }
     if (gpus > 1) {
         if (mode == CU2REC_ALS) {
-            std::cerr << "mf: -m als is single-GPU only (not with -g)\n";
+            std::cerr << "mf: -m " << (implicit ? "ials" : "als") << " is single-GPU only (not with -g)\n";
             return 1;
         }
         if (mode == CU2REC_SGD_PINGPONG) {
@@ -371,7 +385,10 @@ int main(int argc, char **argv) {
         cu2rec::CsrHandle d_train(train), d_test(test);
         cu2rec::ModelHandle model(train.rows, train.cols, cfg.n_factors, train.global_bias);
         std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
-        cu2rec::check(cu2rec_train(d_train.h, d_test.h, &cfg, model.h, mode, 1, losses.data(), nullptr));  // mf.cu:61
+        if (implicit)  // the test file is read (and checked) as always, but only -k looks at it
+            cu2rec::check(cu2rec_train_implicit(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
+        else
+            cu2rec::check(cu2rec_train(d_train.h, d_test.h, &cfg, model.h, mode, 1, losses.data(), nullptr));  // mf.cu:61
 
         std::vector<float> P(static_cast<size_t>(train.rows) * cfg.n_factors), Q(static_cast<size_t>(train.cols) * cfg.n_factors);
         std::vector<float> user_bias(train.rows), item_bias(train.cols);

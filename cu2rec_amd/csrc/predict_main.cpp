@@ -1,7 +1,7 @@
 // bin/predict -- partial fit for new users against a trained model, then recommendations.
 // Drop-in for the reference CLI (predict.cu:72-146):
 //
-//   bin/predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-k K] user_ratings.csv
+//   bin/predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-I alpha] [-k K] user_ratings.csv
 //
 // Q, item_bias and global_bias come from the files bin/mf wrote; only the users' factor rows and biases are
 // trained (is_train = false).  Unlike the reference, the frozen-item flag really reaches the device (there
@@ -18,6 +18,10 @@
 // (cu2rec_model_als, the config's P_reg and user_bias_reg) instead of the SGD loop: the optimum of each user's regularised
 // objective in one call.  Works with and without -u; scoring, ranking and output are unchanged.
 //
+// -I alpha: the implicit-feedback fold-in for a model trained by bin/mf -m ials -- ONE implicit user half-step against the frozen
+// q.csv (cu2rec_model_als_implicit with confidence weight alpha * r and the config's P_reg; every item of q.csv counts, the
+// file's items as positives).  Not together with -A.
+//
 //   bin/predict -c config -q q.csv -S [-k K] item_ids.txt
 //
 // -S fits no user: for each 0-based item index of the file (one per line, the numbers the "Item:" lines print) it lists the
@@ -25,6 +29,7 @@
 #include <getopt.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <fstream>
 #include <iostream>
@@ -101,15 +106,23 @@ int similar_items(const cu2rec_config &cfg, const std::string &q_path, const std
 int main(int argc, char **argv) {
     if (argc < 2) return 2;  // predict.cu:73-75
     std::string config_path, item_bias_path, global_bias_path, q_path;
-    bool many_users = false, similar = false, als = false;
+    bool many_users = false, similar = false, als = false, implicit = false;
+    float alpha = 0.f;  // -I
     int top_k = 0;  // 0: every unrated item, as the reference prints
     const char *k_arg = nullptr;
     int opt;
-    while ((opt = getopt(argc, argv, "c:i:g:q:uk:SA")) != -1) {
+    while ((opt = getopt(argc, argv, "c:i:g:q:uk:SAI:")) != -1) {
         switch (opt) {
             case 'u': many_users = true; break;
             case 'S': similar = true; break;
             case 'A': als = true; break;
+            case 'I': {
+                char *end = nullptr;
+                implicit = true;
+                alpha = std::strtof(optarg, &end);
+                if (end == optarg || *end != '\0') alpha = NAN;  // not a number: refused below
+                break;
+            }
             case 'k':
                 top_k = std::max(0, std::atoi(optarg));
                 k_arg = optarg;
@@ -143,7 +156,15 @@ int main(int argc, char **argv) {
         }
     }
     if (optind >= argc || config_path.empty() || item_bias_path.empty() || global_bias_path.empty() || q_path.empty()) {
-        std::cerr << "usage: predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-k K] user_ratings.csv\n";
+        std::cerr << "usage: predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-I alpha] [-k K] user_ratings.csv\n";
+        return 2;
+    }
+    if (als && implicit) {
+        std::cerr << "predict: -A and -I exclude each other\n";
+        return 2;
+    }
+    if (implicit && !(std::isfinite(alpha) && alpha >= 0.f)) {
+        std::cerr << "predict: -I must be a finite number >= 0\n";
         return 2;
     }
     try {
@@ -205,10 +226,11 @@ int main(int argc, char **argv) {
             ub0[u] = one_ub[0];
         }
         cu2rec::ModelHandle model(B, n_items, f, global_bias, P0.data(), Q.data, ub0.data(), item_bias.data);
-        if (als) {  // one exact user half-step: every user's optimum against the frozen items
+        if (als || implicit) {  // one exact user half-step: every user's optimum against the frozen items
             const cu2rec_hyper h{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
             int unsolved = 0;
-            cu2rec::check(cu2rec_model_als(model.h, d_users.h, &h, CU2REC_SIDE_USERS, &unsolved));
+            cu2rec::check(implicit ? cu2rec_model_als_implicit(model.h, d_users.h, &h, alpha, CU2REC_SIDE_USERS, &unsolved)
+                                   : cu2rec_model_als(model.h, d_users.h, &h, CU2REC_SIDE_USERS, &unsolved));
             if (unsolved) std::cerr << "predict: " << unsolved << " user(s) could not be fitted (non-finite values); they keep the initial factors\n";
         } else {
             std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));

@@ -54,7 +54,57 @@ void train(const DeviceCsr &train_csr, const DeviceCsr &test_csr, cu2rec_config 
         [&] { model.finish_swap(); });
 }
 
+// Implicit-feedback training (include/cu2rec_amd.h: cu2rec_train_implicit): the schedule above with implicit sweeps for the
+// iterations and the objective for the loss.  There is no test set and no learning rate: the schedule's own lines and its
+// patience stay off; the objective's line is printed here.
+void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &model, float alpha, bool verbose, double *objectives,
+                    cu2rec_train_stats *stats) {
+    require(cfg.n_factors == model.n_factors, "cu2rec_train_implicit: cfg.n_factors differs from the model's");
+    require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_implicit: bad iteration counts");
+    hipStream_t stream = nullptr;
+    if (objectives)
+        for (int i = 0; i < cfg.total_iterations; ++i) objectives[i] = std::numeric_limits<double>::quiet_NaN();
+    cu2rec_hyper hyper{};
+    double solved = 0.0;
+    int done = 0;
+    cu2rec_train_stats st{};
+    train_schedule(
+        cfg, false, false, 0.0, nullptr, &st, stream,
+        [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
+            hyper = h;
+            for (int k = 0; k < n; ++k) {
+                const int u = model.ials(train_csr, h, alpha, CU2REC_SIDE_USERS, s);
+                solved += train_csr.als->users.rows_with_ratings - u;
+                if (cfg.is_train) {
+                    const int i = model.ials(train_csr, h, alpha, CU2REC_SIDE_ITEMS, s);
+                    solved += train_csr.als->items.rows_with_ratings - i;
+                }
+            }
+            done += n;
+        },
+        [&](bool on_train, float *mae, float *rmse) {
+            *mae = *rmse = 0.f;  // no residual metrics in this model
+            if (!on_train) return;
+            const double L = model.implicit_objective(train_csr, hyper, alpha, stream);
+            if (verbose) std::printf("TRAIN: Iteration %d GPU implicit objective: %f\n", done, L);
+            if (objectives) objectives[done - 1] = L;
+        },
+        [] {}, /*decay_lr=*/false);
+    if (verbose) std::printf("Time taken for %d of iterations is %lf\n", cfg.total_iterations, st.seconds_total);
+    st.updates = solved;
+    if (stats) *stats = st;
+}
+
 }  // namespace cu2rec
+
+extern "C" int cu2rec_train_implicit(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose,
+                                     double *objectives, cu2rec_train_stats *stats) {
+    using namespace cu2rec;
+    return guarded([&] {
+        require(train && cfg && model, "cu2rec_train_implicit: null argument");
+        cu2rec::train_implicit(unwrap(train), *cfg, unwrap(model), alpha, verbose != 0, objectives, stats);
+    });
+}
 
 extern "C" int cu2rec_train(const cu2rec_csr *train, const cu2rec_csr *test, cu2rec_config *cfg, cu2rec_model *model,
                             int mode, int verbose, float *losses, cu2rec_train_stats *stats) {

@@ -473,6 +473,39 @@ enum { CU2REC_ALS_MAX_FACTORS = 252, CU2REC_ALS_STEP = 32, CU2REC_ALS_CHUNK = 10
 int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *unsolved);
 
 /* ------------------------------------------------------------------------------------------
+ * Implicit feedback: confidence-weighted alternating least squares (Hu, Koren, Volinsky: Collaborative Filtering for Implicit
+ * Feedback Datasets, ICDM 2008).  Every user x item pair of the CSR's shape counts: U = train rows, I = train cols, each stored
+ * entry (u, i, r) is an observation of weight w = alpha * r (repeated pairs count separately), s_ui = p_u . q_i; there are no
+ * biases and no global bias:
+ *   L = 1/2 sum_(u < U, i < I) s_ui^2 + 1/2 sum_entries (w (1 - s_ui)^2 + 1 - 2 s_ui)
+ *     + 1/2 P_reg sum_(u < U) |p_u|^2 + 1/2 Q_reg sum_(i < I) |q_i|^2
+ * -- for pairs stored once, sum c (p - s)^2 with c = 1 + w, p = 1 on stored pairs and c = 1, p = 0 elsewhere.  The regulariser is
+ * plain reg here, NOT n_u reg / m_i reg as in the explicit objective above.
+ * A user half-step solves, for EVERY user u < U, with Y = Q[0:I]:
+ *   (Y^T Y + sum_entries w q_i q_i^T + P_reg I_f) p_u = sum_entries (1 + w) q_i;
+ * a user without entries has right-hand side 0: its row is written as zeros, not factorised and not counted.  The item half-step
+ * is the mirror image on the item-major view with X = P[0:U] and Q_reg.  After a half-step the solved side's biases of the rows
+ * inside the CSR are 0 and its padding floats are 0; model rows past the CSR's rows / cols and the whole other side keep their bits.
+ * Y^T Y is formed once per half-step: the partner rows in tiles of CU2REC_ALS_CHUNK, one workgroup per tile on the explicit
+ * half-step's matrix-core accumulation, the tiles' partial Grams added in tile order (in batches through the same workspace) --
+ * a function of the partner rows alone.  A row's own sum starts from it and adds its entries exactly as the explicit half-step
+ * does (same stage, chunk cut and chunk-order summation; the entries are staged as the two operands [w q | 1 + w] and [q | 0], so
+ * w = 0 is an ordinary entry), then the order-f system is solved by the same Cholesky.  A row's result depends only on its own
+ * entries and the partner rows [0, I) or [0, U): bit-identical across runs, and a user solved from a one-user CSR of the same cols
+ * equals that user solved among all the others.  A row is left unchanged and counted in *unsolved (may be NULL) when a pivot is
+ * not a finite positive float (possible only with negative or non-finite data) or its solution is not finite.
+ * CU2REC_EINVAL, checked before the device or the model is touched: a null m / train / hyper, a bad side, a factor regulariser of
+ * the side that is not finite and > 0, alpha not finite or < 0, a CSR whose rows or cols exceed the model's.  The bias
+ * regularisers and the learning rate are ignored.  n_factors > CU2REC_ALS_MAX_FACTORS: CU2REC_EUNSUPPORTED.  Single GPU.
+ * ---------------------------------------------------------------------------------------- */
+int cu2rec_model_als_implicit(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
+                              int *unsolved);
+/* *L = the objective above at the model's current values: the all-pairs term as 1/2 <P^T P, Q^T Q> from two global Grams (f32, as
+ * the half-step forms them), the entries term and the two norms from one pass over the entries and the rows, summed in double
+ * like the loss pass.  Regularisers >= 0 are accepted here.  Reads the model only. */
+int cu2rec_model_implicit_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, double *L);
+
+/* ------------------------------------------------------------------------------------------
  * train() -- replaces both overloads of train (training.h:12-15, training.cu:21-217):
  * total_iterations iterations; loss on train and test when i == 0, (i+1) % check_error == 0
  * or last (training.cu:118) printed as "TRAIN: Iteration %d GPU MAE: %f RMSE: %f" / "TEST: ..."
@@ -496,6 +529,13 @@ typedef struct cu2rec_train_stats {
 
 int cu2rec_train(const cu2rec_csr *train, const cu2rec_csr *test, cu2rec_config *cfg, cu2rec_model *model,
                  int mode, int verbose, float *losses, cu2rec_train_stats *stats);
+/* Implicit-feedback training: total_iterations sweeps of cu2rec_model_als_implicit -- the users, then the items when cfg->is_train
+ * -- with the objective evaluated at the loss cadence above, printed as "TRAIN: Iteration %d GPU implicit objective: %f" when
+ * `verbose`, and stored in objectives[i] (host, total_iterations doubles, may be NULL; NaN elsewhere).  There is no test set and no
+ * learning rate: no decay, cfg->learning_rate stays as it is; cfg->cur_iterations advances.  stats->updates = rows solved (rows
+ * without entries, written as zeros, are not counted); the stats' MAE / RMSE fields are 0. */
+int cu2rec_train_implicit(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose,
+                          double *objectives, cu2rec_train_stats *stats);
 
 /* ------------------------------------------------------------------------------------------
  * Sharding by user (multi-GPU; the reference is single device).  Host-side planner:

@@ -1,13 +1,18 @@
 """Times the alternating-least-squares half-steps (cu2rec_model_als) on the synthetic ML-20M and Netflix shapes and prints each time
 next to its Gram roofline.
 
-    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3]
+    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3] [--implicit [--alpha 40]]
 
 For every shape: the item half-step's first call on a fresh cu2rec_csr (it builds the item-major view), the item half-step again
 (view cached), the user half-step, and a whole sweep (users then items).  Times are wall clock around the synchronous call (the
 call returns after a device-to-host read of its unsolved count), best of --reps.  Roofline: the Gram of a half-step is
 2 nnz (f + 2)^2 flop when formed whole; its lower triangle half that; at 155 TF/s (fp32 MFMA peak of the MI355X) -- the partner-row
-gather (nnz x 4 (f + 1) bytes) and the per-row Cholesky (about rows x (f + 1)^3 / 3 flop) come on top."""
+gather (nnz x 4 (f + 1) bytes) and the per-row Cholesky (about rows x (f + 1)^3 / 3 flop) come on top.
+
+--implicit: after the explicit rows, the implicit-feedback half-steps and sweep (cu2rec_model_als_implicit) in the same process, on
+the same cu2rec_csr and a model of their own, with the ratio implicit / explicit of the sweeps.  An implicit half-step does the
+same per-entry work, solves EVERY row (rows without entries are written as zeros) and forms the partner side's global Gram first
+(rows x f^2 multiply-adds over both half-steps of a sweep: users + items rows)."""
 import argparse
 import os
 import sys
@@ -39,6 +44,8 @@ def main():
     ap.add_argument("--shapes", default="ml-20m,netflix")
     ap.add_argument("--factors", type=int, default=100)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--implicit", action="store_true")
+    ap.add_argument("--alpha", type=float, default=40.0)
     args = ap.parse_args()
     f = args.factors
     for name in args.shapes.split(","):
@@ -66,6 +73,18 @@ def main():
             print("  %-38s %9.2f ms   (lower-triangle Gram roofline %.2f ms: %.1fx)" % (label, 1e3 * t, roof, 1e3 * t / roof),
                   flush=True)
         m.close()
+        if args.implicit:
+            explicit_sweep = rows[-1][1]
+            m = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
+            assert m.ials(d, HYPER, args.alpha, "both") == 0  # warm: both sides' plans exist already
+            rows = [("implicit items", best(lambda: m.ials(d, HYPER, args.alpha, "items"), args.reps)),
+                    ("implicit users", best(lambda: m.ials(d, HYPER, args.alpha, "users"), args.reps)),
+                    ("implicit sweep (users + items)", best(lambda: m.ials(d, HYPER, args.alpha, "both"), args.reps))]
+            for label, t in rows:
+                print("  %-38s %9.2f ms" % (label, 1e3 * t), flush=True)
+            print("  implicit / explicit sweep: %.2f   (global Grams: (%d + %d) rows x f^2 = %.2e multiply-adds per sweep)"
+                  % (rows[-1][1] / explicit_sweep, tr.rows, tr.cols, (tr.rows + tr.cols) * float(f) ** 2), flush=True)
+            m.close()
         d.close()
 
 
