@@ -161,6 +161,30 @@ def model_from(state, gb, f=None):
     return cu.Model(P.shape[0], Q.shape[0], P.shape[1] if f is None else f, gb, P=P, Q=Q, user_bias=ub, item_bias=ib)
 
 
+def same_state(a, b):
+    return all(same_bits(x, y) for x, y in zip(a, b))
+
+
+def interplay(steps, tr, f, state=None, objects=None):
+    """`steps` on one Model and one DeviceCSR against the same steps with the model downloaded and re-created, and the
+    DeviceCSR uploaded afresh, between every two of them: after every step the two states are equal bit for bit, and so is
+    what the step returned (a count of unsolved rows, an objective).  state: the float32 values to start from (default: the
+    seed-42 initial model); objects: a list that receives the kept Model and DeviceCSR.  Returns the last state."""
+    kept_model = cu.Model(tr.rows, tr.cols, f, tr.global_bias) if state is None else model_from(state, tr.global_bias)
+    kept_csr = cu.DeviceCSR(tr)
+    if objects is not None:
+        objects += [kept_model, kept_csr]
+    state = kept_model.download()
+    for k, step in enumerate(steps):
+        on_kept = step(kept_model, kept_csr)
+        fresh = model_from(state, tr.global_bias)
+        on_fresh = step(fresh, cu.DeviceCSR(tr))
+        state = fresh.download()
+        assert same_state(kept_model.download(), state), ("step %d differs on the shared objects" % k)
+        assert on_kept == on_fresh, ("step %d returns something else on the shared objects" % k, on_kept, on_fresh)
+    return state
+
+
 # ---- rating sets -----------------------------------------------------------------------------------------------------------
 def csr_from_rows(per_row, cols, ratings_rng, gb=None, ratings=None):
     """per_row: one array of partner ids per row (in the order given).  Ratings: half stars 0.5 .. 5 unless given."""

@@ -17,7 +17,8 @@ csr: anything with indptr / indices / data / rows / cols (api.HostCSR)."""
 import numpy as np
 
 STEP, CHUNK, MAX_CHUNKS = 32, 1024, 64  # CU2REC_ALS_STEP, CU2REC_ALS_CHUNK, CU2REC_ALS_MAX_CHUNKS (tests/test_ials_cpu.py pins them)
-MUTATIONS = ("n_reg", "no_g0", "gram_1_plus_w", "rhs_w")
+MUTATIONS = ("n_reg", "no_g0", "gram_1_plus_w", "rhs_w", "tile_pair")
+GRAM_BLOCK = 1 << 16  # partner rows widened to float64 at a time by gram64()
 
 
 def _f32(x):
@@ -36,27 +37,68 @@ def own_major(csr, side):
     return indptr, rows_of[order], np.asarray(csr.data, np.float64)[order], csr.rows
 
 
-def solve_rows(indptr, indices, data, X, reg, alpha, rows=None, mutation=None):
-    """Rows `rows` (default: all) of one half-step in float64 against the partner rows X (all of them enter G0) -> (len(rows), f).
-    mutation: one of MUTATIONS -- the four deliberate mistakes the tests must be able to see: "n_reg" (n reg on the diagonal, the
-    explicit objective's regulariser), "no_g0" (the all-pairs Gram left out), "gram_1_plus_w" (weights 1 + w in the Gram),
-    "rhs_w" (the right-hand side weighted by w)."""
-    assert mutation is None or mutation in MUTATIONS
-    X = np.asarray(X, np.float64)
+def ials_tiles(f):
+    """32-column tiles of the staged operands: f factor columns and the right-hand side's weight (als.hpp: ials_tiles)."""
+    return (f + 1 + 31) // 32
+
+
+def gram64(X):
+    """X^T X in float64, GRAM_BLOCK rows at a time: a float32 X of many rows is never widened as a whole."""
     f = X.shape[1]
-    G0 = np.zeros((f, f)) if mutation == "no_g0" else X.T @ X
+    G = np.zeros((f, f))
+    for lo in range(0, len(X), GRAM_BLOCK):
+        B = np.asarray(X[lo:lo + GRAM_BLOCK], np.float64)
+        G += B.T @ B
+    return G
+
+
+def row_system(indptr, indices, data, X, reg, alpha, r, G0, mutation=None):
+    """(A, b) of row r in float64: A = G0 + sum w q q^T + reg I, b = sum (1 + w) q; `mutation` as in solve_rows."""
+    f = X.shape[1]
+    lo, hi = int(indptr[r]), int(indptr[r + 1])
+    Z = np.asarray(X[indices[lo:hi]], np.float64)
+    w = _f32(alpha) * np.asarray(data[lo:hi], np.float64)
+    gw = 1.0 + w if mutation == "gram_1_plus_w" else w
+    bw = w if mutation == "rhs_w" else 1.0 + w
+    W, b = (Z * gw[:, None]).T @ Z, Z.T @ bw
+    if mutation == "tile_pair":
+        nt = ials_tiles(f)
+        r0 = 32 * (nt - 1)
+        if nt == 1:
+            block = (slice(0, f), slice(0, f))
+        else:
+            block = (slice(r0, f), slice(0, 32))
+        if W[block].size and W[block].any():
+            W[block] = 0.0
+            W[block[1], block[0]] = 0.0
+        else:
+            b[:32] = 0.0
+    return G0 + W + (hi - lo if mutation == "n_reg" else 1) * _f32(reg) * np.eye(f), b
+
+
+def solve_rows(indptr, indices, data, X, reg, alpha, rows=None, mutation=None, G0=None):
+    """Rows `rows` (default: all) of one half-step in float64 against the partner rows X (all of them enter G0) -> (len(rows), f).
+    G0: X^T X in float64 where the caller has it already (gram64).
+    mutation: one of MUTATIONS -- the five deliberate mistakes the tests must be able to see: "n_reg" (n reg on the diagonal, the
+    explicit objective's regulariser), "no_g0" (the all-pairs Gram left out), "gram_1_plus_w" (weights 1 + w in the Gram),
+    "rhs_w" (the right-hand side weighted by w), and "tile_pair", an error confined to ONE accumulator of the kernel: of the
+    row's own sums [sum w q q^T ; sum (1 + w) q] (row f is the right-hand side, as in als.hip) tile pair (NT - 1, 0) -- rows
+    32 (NT - 1) .. and columns 0 .. 31 -- holds the Gram block of rows 32 (NT - 1) .. f - 1, which is zeroed (with its mirror
+    image: the kernel reads the lower triangle of a symmetric system); at NT = 1 the whole own Gram is.  Where that changes
+    nothing -- f a multiple of 32: the last tile holds no Gram row; alpha = 0: the own Gram is zero -- the other thing the same
+    accumulator holds, the right-hand side's entries 0 .. 31, is zeroed instead."""
+    assert mutation is None or mutation in MUTATIONS
+    f = X.shape[1]
+    if mutation == "no_g0":
+        G0 = np.zeros((f, f))
+    elif G0 is None:
+        G0 = gram64(X)
     rows = np.arange(len(indptr) - 1) if rows is None else np.asarray(rows, np.int64)
     out = np.zeros((len(rows), f))
     for k, r in enumerate(rows):
-        lo, hi = int(indptr[r]), int(indptr[r + 1])
-        if hi == lo:
+        if indptr[r + 1] == indptr[r]:
             continue
-        Z = X[indices[lo:hi]]
-        w = _f32(alpha) * np.asarray(data[lo:hi], np.float64)
-        gw = 1.0 + w if mutation == "gram_1_plus_w" else w
-        bw = w if mutation == "rhs_w" else 1.0 + w
-        A = G0 + (Z * gw[:, None]).T @ Z + (hi - lo if mutation == "n_reg" else 1) * _f32(reg) * np.eye(f)
-        out[k] = np.linalg.solve(A, Z.T @ bw)
+        out[k] = np.linalg.solve(*row_system(indptr, indices, data, X, reg, alpha, r, G0, mutation))
     return out
 
 
@@ -143,14 +185,14 @@ def cholesky_solve_f32(G, b):
     return y if np.isfinite(y).all() else None
 
 
-def solve_rows_f32(indptr, indices, data, X, reg, alpha, rows=None):
-    """solve_rows() in float32, in the kernels' order: G0 by gram_f32; a row of at most CHUNK entries adds (w q) q^T and (1 + w) q
-    to G0 entry by entry; a longer row is cut into chunks whose sums, each from zero, are added to G0 in chunk order; reg on the
-    diagonal; cholesky_solve_f32.  A row that cannot be solved comes back as NaN."""
+def solve_rows_f32(indptr, indices, data, X, reg, alpha, rows=None, G0=None):
+    """solve_rows() in float32, in the kernels' order: G0 by gram_f32 (or as given: gram_f32(X) computed before); a row of at
+    most CHUNK entries adds (w q) q^T and (1 + w) q to G0 entry by entry; a longer row is cut into chunks whose sums, each from
+    zero, are added to G0 in chunk order; reg on the diagonal; cholesky_solve_f32.  A row that cannot be solved comes back as NaN."""
     F = np.float32
     X = np.asarray(X, F)
     f = X.shape[1]
-    G0 = gram_f32(X)
+    G0 = gram_f32(X) if G0 is None else np.asarray(G0, F)
     rows = np.arange(len(indptr) - 1) if rows is None else np.asarray(rows, np.int64)
     out = np.zeros((len(rows), f), F)
     for k, r in enumerate(rows):

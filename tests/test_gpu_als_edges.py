@@ -202,41 +202,27 @@ def test_workspace_is_regrown_when_one_csr_serves_a_wider_model():
 
 
 # ---- B.5: the SGD modes around ALS on shared objects --------------------------------------------------------------------------
-def _interplay(steps, tr, f, hyper):
-    """`steps` on one Model and one DeviceCSR against the same steps with the model downloaded and re-created, and the
-    DeviceCSR uploaded afresh, between every two of them."""
-    kept_model, kept_csr = cu.Model(tr.rows, tr.cols, f, tr.global_bias), cu.DeviceCSR(tr)
-    state = kept_model.download()
-    for k, step in enumerate(steps):
-        step(kept_model, kept_csr)
-        fresh = model_from(state, tr.global_bias)
-        step(fresh, cu.DeviceCSR(tr))
-        state = fresh.download()
-        assert _same_state(kept_model.download(), state), ("step %d differs on the shared objects" % k)
-    return state
-
-
 def test_pingpong_als_pingpong_on_one_model():
     tr, _ = synth.make_ratings(300, 80, 5000, min_degree=2, seed=81)
     hyper = (0.01, 0.05, 0.04, 0.02, 0.03)
-    first = _interplay([lambda m, d: m.sgd(d, hyper, 42, 0, 3, mode="pingpong"),
-                        lambda m, d: m.als(d, hyper, "items"),
-                        lambda m, d: m.sgd(d, hyper, 42, 3, 3, mode="pingpong"),
-                        lambda m, d: m.als(d, hyper, "both"),
-                        lambda m, d: m.sgd(d, hyper, 42, 6, 2, mode="pingpong")], tr, 16, hyper)
+    first = chk.interplay([lambda m, d: m.sgd(d, hyper, 42, 0, 3, mode="pingpong"),
+                           lambda m, d: m.als(d, hyper, "items"),
+                           lambda m, d: m.sgd(d, hyper, 42, 3, 3, mode="pingpong"),
+                           lambda m, d: m.als(d, hyper, "both"),
+                           lambda m, d: m.sgd(d, hyper, 42, 6, 2, mode="pingpong")], tr, 16)
     assert all(np.isfinite(a).all() for a in first)
 
 
 def test_ordered_and_blocksolve_around_als_on_one_csr():
     tr, _ = synth.make_ratings(300, 80, 5000, min_degree=2, seed=82)
     hyper = (0.01, 0.05, 0.04, 0.02, 0.03)
-    last = _interplay([lambda m, d: m.sgd(d, hyper, 42, 0, 2, mode="ordered"),
-                       lambda m, d: m.als(d, hyper, "both"),
-                       lambda m, d: m.sgd(d, hyper, 42, 2, 2, mode="blocksolve"),
-                       lambda m, d: m.als(d, hyper, "users"),
-                       lambda m, d: m.sgd(d, hyper, 42, 4, 2, mode="ordered"),
-                       lambda m, d: m.als(d, hyper, "items"),
-                       lambda m, d: m.sgd(d, hyper, 42, 6, 2, mode="blocksolve")], tr, 16, hyper)
+    last = chk.interplay([lambda m, d: m.sgd(d, hyper, 42, 0, 2, mode="ordered"),
+                          lambda m, d: m.als(d, hyper, "both"),
+                          lambda m, d: m.sgd(d, hyper, 42, 2, 2, mode="blocksolve"),
+                          lambda m, d: m.als(d, hyper, "users"),
+                          lambda m, d: m.sgd(d, hyper, 42, 4, 2, mode="ordered"),
+                          lambda m, d: m.als(d, hyper, "items"),
+                          lambda m, d: m.sgd(d, hyper, 42, 6, 2, mode="blocksolve")], tr, 16)
     assert all(np.isfinite(a).all() for a in last)
 
 

@@ -4,7 +4,7 @@ cu2rec_train_implicit, bin/mf -m ials, bin/predict -I) against the float64 refer
 The bar for a solved row x against the float64 optimum x* of the same system, built from the same float32 state, is the
 project's: max |x - x*| <= 1e-3 max(1, |x*|_inf).  tests/test_ials_cpu.py shows on the CPU that a float32 restatement of the
 kernels' arithmetic meets it on every row judged here (at 3e-5 .. 9e-4 of the bar on the large sets, 0.19 on the small-partner
-set) and that four deliberate mistakes in the model do not.  The judge itself lives in tests/ials_checks.py."""
+set) and that five deliberate mistakes in the model do not.  The judge itself lives in tests/ials_checks.py."""
 import ctypes as C
 import os
 import subprocess
@@ -33,9 +33,10 @@ def _same_state(a, b):
 
 @pytest.mark.parametrize("name", sorted(chk.cases()))
 def test_half_step_matches_float64(name):
-    """Widths 1, 8, 30, 31, 100, 126, 252 x rows of 1 .. 4,097 entries (at 31 and 252 also 64 x 1,024 + 1) on both sides, long
-    item rows over one and two workspace batches, 40 partners at f = 100, and the messy set (entries of 0, repeated pairs, rows
-    without entries) at alpha 40 and 0, and partner matrices of exactly 1,024, 1,025 and 2,049 rows (the G0 tile edges)."""
+    """Widths 1, 8, 30, 31, 100, 126, 252 and both edges of every tile count (ials_checks.EDGE_WIDTHS) x rows of 1 .. 4,097
+    entries (at 31, 95 and 252 also 64 x 1,024 + 1) on both sides, long item rows over one and two workspace batches, 40
+    partners at f = 100, and the messy set (entries of 0, repeated pairs, rows without entries) at alpha 40 and 0, and partner
+    matrices of exactly 1,024, 1,025 and 2,049 rows (the G0 tile edges)."""
     case = chk.cases()[name]
     model = model_from(case.state(), case.csr.global_bias)
     report = {}
@@ -96,8 +97,9 @@ OBJECTIVE_TOLERANCE = 4 * chk.OBJECTIVE_RESTATEMENT_ERROR
 def test_objective_matches_float64(name):
     """cu2rec_model_implicit_objective against the float64 objective, relative.  The tolerance is measured: the float32
     restatement of the objective (float32 Grams summed in the kernels' order, everything else float64:
-    ials_reference64.objective_f32) is off by at most 3.7e-9 on these sets (tests/test_ials_cpu.py prints 3.69e-9, 2.25e-9,
-    2.04e-9, 7.9e-11); times 4 for the freedom in accumulation order: 1.48e-8."""
+    ials_reference64.objective_f32) is off by at most 4.7e-8 on these sets (tests/test_ials_cpu.py prints 3.69e-9, 2.25e-9,
+    2.04e-9, 7.9e-11 on the first four and up to 4.68e-8 on the edge widths, listed beside ials_checks.OBJECTIVE_SETS); times 4 for
+    the freedom in accumulation order: 1.88e-7."""
     case = chk.cases()[name]
     state = case.state()
     model = model_from(state, 0.0)
