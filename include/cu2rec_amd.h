@@ -133,6 +133,11 @@ int cu2rec_sampler_index(uint64_t seed, uint64_t user, uint64_t iteration, int l
  * All pointers are device pointers on the current device unless marked host.  `stream` is a
  * hipStream_t passed as void* (NULL = default stream).  Calls are asynchronous unless they
  * return host results.
+ * Streams: what the library owns -- a cu2rec_schedule's workspace, the process-wide state of the resident launches -- it orders
+ * itself: a call that uses it on another stream than its previous call starts behind that call, and the library's internal streams
+ * start behind everything queued on `stream` ahead of the call.  Ordering the caller's own buffers across streams stays the
+ * caller's duty.  One exception to "asynchronous": cu2rec_sgd_update_blocksolve waits on the host for `stream` on a schedule's
+ * first block-solve call and whenever ldq differs from the schedule's previous call (it re-allocates a workspace sized by ldq).
  * ---------------------------------------------------------------------------------------- */
 typedef struct cu2rec_hyper { /* the kernel-visible subset of config (config.h:9-18) */
     float learning_rate, P_reg, Q_reg, user_bias_reg, item_bias_reg;

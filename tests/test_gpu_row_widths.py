@@ -123,13 +123,17 @@ def test_pingpong_bit_exact_in_both_buffer_pairs(f):
             np.testing.assert_array_equal(_raw(other, tr.cols, ldq)[:, :f], Qt)
 
 
-@pytest.mark.parametrize("f", FACTORS)
-def test_hogwild_bit_exact_where_no_update_races(f):
+def _own_item_set(f, n=300):
     # every user rates only its own item: no two updates of an iteration touch the same row, so the streaming Hogwild launch
     # has the sequential result bit for bit (the construction of test_sgd_hogwild_exact_when_no_item_is_shared)
-    n = 300
     rng = np.random.RandomState(f)
-    m = cu.HostCSR(np.arange(n + 1), rng.permutation(n), rng.randint(1, 6, n).astype(np.float32), n, n, 3.0)
+    return cu.HostCSR(np.arange(n + 1), rng.permutation(n), rng.randint(1, 6, n).astype(np.float32), n, n, 3.0)
+
+
+@pytest.mark.parametrize("f", FACTORS)
+def test_hogwild_bit_exact_where_no_update_races(f):
+    n = 300
+    m = _own_item_set(f, n)
     prev = lib().cu2rec_hogwild_resident(0)  # streaming launches only
     try:
         state = orc.init_model(n, n, f)
