@@ -1,5 +1,6 @@
 // Launch interface of the block-solve SGD mode (CU2REC_SGD_BLOCKSOLVE): sequential semantics
-// (mf_sequential.cu:102-143) with the long item chains solved block-wise; see blocksolve.hip.
+// (mf_sequential.cu:102-143) with the long item chains solved block-wise; see blocksolve.hip (entry points, launches) and the
+// phase headers it includes (blocksolve_gram.hpp, blocksolve_solve.hpp, blocksolve_lookahead.hpp, blocksolve_update.hpp).
 #pragma once
 
 #include <functional>
@@ -57,7 +58,7 @@ struct BsIteration {
     // (BlockSolve's constructor); the block table is dense and the workgroups stride through it, so a busier iteration is still
     // done completely
     int launch_blocks;
-    // Look-ahead chains (blocksolve.hip, "look-ahead form"): popularity ranks [0, la_ranks) -- the long chains, whose length IS the
+    // Look-ahead chains (blocksolve_lookahead.hpp, "the look-ahead form"): popularity ranks [0, la_ranks) -- the long chains, whose length IS the
     // iteration's critical path.  Phase 1 also builds the block of lr L that couples each of their blocks to the one before it
     // (la_grid more workgroups in its launch), and phase 2 runs them with the item row OFF the dependent path.
     int la_ranks;

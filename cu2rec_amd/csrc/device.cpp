@@ -82,7 +82,7 @@ static void check_faults() {
     (void)hipMemset(r.status + DeviceRuntime::kBlocksolveWord, 0, sizeof(unsigned));
     host[1] = 0;
     const char *ordered = "CU2REC_SGD_ORDERED is the same result without concurrent launches";
-    if (bs == 2u)  // a look-ahead ring wait (blocksolve.hip, la_wait*): the fork / join had no part in it
+    if (bs == 2u)  // a look-ahead ring wait (blocksolve_lookahead.hpp, la_wait*): the fork / join had no part in it
         fail(CU2REC_EHIP, std::string("cu2rec_amd: a block-solve iteration gave up at a wait inside a phase-2 workgroup (its wavefronts hand "
                                       "blocks over through flags: is another process or stream holding this GPU's compute units?); the "
                                       "model state is undefined.  ") + ordered);

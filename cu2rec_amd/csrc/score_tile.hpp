@@ -7,13 +7,12 @@
 
 #include <cstddef>
 
+#include "mfma_f32.hpp"
+
 namespace cu2rec {
 
 constexpr int kTile = 32;
 constexpr size_t kMaxLds = 160 * 1024;  // LDS of one workgroup on gfx950
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
 // 32 rows x slots [slot0, slot0 + n) of a row-major matrix into an LDS tile [32][RS], by one wavefront: 8 lanes x 16 bytes
 // per row piece, 8 rows per pass; rows beyond n_rows are zero.  Loads are unconditional at clamped addresses.

@@ -2,12 +2,13 @@
 grid (every row width x pinned chain lengths), their rating sets and starting models, the two CPU references and the bound a GPU
 result is held to.  Nothing here needs a GPU to be imported.
 
-What decides the mode's code path, restated below from cu2rec_amd/csrc/blocksolve.hip:
+What decides the mode's code path, restated below from cu2rec_amd/csrc/blocksolve.hip and its phase headers (blocksolve_*.hpp):
   * the row width nslots = ceil(f / 4) float4 slots: launch_solve's seven phase-2 instantiations SW (sw_bucket), bs_solve_kernel's
     five look-ahead instantiations NSM (nsm_bucket, rows of at most kLaMaxSlots = 29 slots), launch_update's one to four phase-3
     wavefronts, the odd LDS row stride nslots | 1;
-  * the chain length: blocks of kB = 64 links in two halves of 32; solve_chain's long_chain path above kDepth = 4 blocks with
-    n_intervals rounded up to a multiple of 4; chain_lookahead from two blocks on (chain_is_lookahead), rings of 3 / 2 / 2.
+  * the chain length: blocks of kB = 64 links in two halves of 32; solve_chain's (blocksolve_solve.hpp) long_chain path above
+    kDepth = 4 blocks with n_intervals rounded up to a multiple of 4; chain_lookahead (blocksolve_lookahead.hpp) from two blocks on
+    (chain_is_lookahead), rings of 3 / 2 / 2.
 Chain lengths are made EXACT instead of sampled: a user with one rating samples it in every iteration, so an item rated by L such users
 has a chain of exactly L links (users ascending) in every iteration, and its expected update rate is exactly L.
 
@@ -37,7 +38,7 @@ TOL_FLOOR, TOL_CAP = 2e-6, 1e-5
 NAMES = ("P", "Q", "user_bias", "item_bias")
 
 NSLOTS = list(range(1, 64))
-LA_MAX_SLOTS = 29  # blocksolve.hip, kLaMaxSlots / la_supported
+LA_MAX_SLOTS = 29  # blocksolve_lookahead.hpp, kLaMaxSlots / la_supported
 
 
 def width(nslots):
@@ -54,8 +55,8 @@ def sw_bucket(nslots):
 
 
 def nsm_bucket(nslots):
-    """blocksolve.hip, bs_solve_kernel: chain_lookahead<min(4 SW, kLaMaxSlots)>, taken only for SW <= 8 and (la_supported, read in
-    BlockSolve::begin) nslots <= kLaMaxSlots."""
+    """blocksolve.hip, bs_solve_kernel: chain_lookahead<min(4 SW, kLaMaxSlots)>, taken only for SW <= 8 and (la_supported,
+    blocksolve_lookahead.hpp, read in BlockSolve::begin) nslots <= kLaMaxSlots."""
     assert 1 <= nslots <= LA_MAX_SLOTS
     return min(4 * sw_bucket(nslots), LA_MAX_SLOTS)
 

@@ -77,7 +77,7 @@ def test_blocksolve_matches_sequential_oracle(min_rate, users, items, nnz, f, it
 ])
 def test_blocksolve_lookahead_form_matches_sequential_oracle(min_rate, users, items, nnz, f, iters, rate, la):
     """cu2rec_blocksolve_lookahead_blocks: the leading chains run phase 2 as e_i = M_i (pre_i - N_i e_(i-1)) on one wavefront,
-    the item row one block behind (blocksolve.hip, chain_lookahead); the formulas: tests/test_blocksolve_algebra.py."""
+    the item row one block behind (blocksolve_lookahead.hpp, chain_lookahead); the formulas: tests/test_blocksolve_algebra.py."""
     min_rate(rate)
     prev = cu.api.blocksolve_lookahead_blocks(la)
     try:

@@ -38,9 +38,9 @@ def settings():
 
 
 def lookahead_items(csr, la_min, min_rate):
-    """blocksolve.hip, BlockSolve::BlockSolve and chain_is_lookahead: the leading ranks (rate descending) with rate >= 64 la_min are
-    look-ahead ranks; such a chain runs the look-ahead form in an iteration in which it has at least two blocks and its blocks -- the
-    first of the block table, in rank order -- end within la_cap.  -> (the ranks' items, la_cap)"""
+    """blocksolve.hip, BlockSolve::BlockSolve, and blocksolve_device.hpp, chain_is_lookahead: the leading ranks (rate descending) with
+    rate >= 64 la_min are look-ahead ranks; such a chain runs the look-ahead form in an iteration in which it has at least two blocks
+    and its blocks -- the first of the block table, in rank order -- end within la_cap.  -> (the ranks' items, la_cap)"""
     rate = api.item_update_rates(csr)
     order = np.argsort(-rate, kind="stable")
     n_hot = int((rate >= min_rate).sum())
@@ -103,7 +103,8 @@ def test_lookahead_form_every_width_every_length(settings, nslots):
 
 @pytest.mark.parametrize("nslots", [30, 32, 33, 63])
 def test_lookahead_setting_is_ignored_above_29_slots(settings, nslots):
-    """la_supported (BlockSolve::begin) takes rows of at most 29 slots, and bs_solve_kernel compiles the form for SW <= 8 only."""
+    """la_supported (blocksolve_lookahead.hpp; read in BlockSolve::begin) takes rows of at most 29 slots, and bs_solve_kernel compiles
+    the form for SW <= 8 only."""
     assert nslots > bc.LA_MAX_SLOTS and {bc.sw_bucket(n) for n in (30, 32, 33, 63)} == {8, 12, 16}
     tr, f = bc.length_set(), bc.width(nslots)
     start, (ref,) = bc.references("lengths", tr, f)
