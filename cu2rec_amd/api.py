@@ -24,10 +24,17 @@ METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE}
 MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "pingpong": SGD_PINGPONG,
          "blocksolve": SGD_BLOCKSOLVE, "als": ALS}
 ALS_SIDES = {"users": (SIDE_USERS,), "items": (SIDE_ITEMS,), "both": (SIDE_USERS, SIDE_ITEMS)}
+IALS_SOLVERS = ("cholesky", "cg")  # Model.ials / train(mode="ials"): the exact solver, or conjugate-gradient steps per row
+ALS_CG_MAX_STEPS = 256             # CU2REC_ALS_CG_MAX_STEPS
 
 
 def _mode(mode):
     return MODES[mode] if isinstance(mode, str) else int(mode)
+
+
+def _solver(solver):
+    if solver not in IALS_SOLVERS:
+        raise ValueError("solver must be one of %s, not %r" % (list(IALS_SOLVERS), solver))
 
 
 def _choice(table, value, what):
@@ -296,18 +303,24 @@ class Model:
                 total += n.value
         return total
 
-    def ials(self, train, hyper, alpha=40.0, side="both", sweeps=1):
+    def ials(self, train, hyper, alpha=40.0, side="both", sweeps=1, solver="cholesky", cg_steps=3):
         """Implicit-feedback half-steps (cu2rec_model_als_implicit): every user x item pair of train's shape counts, a stored entry
         (u, i, r) with confidence weight alpha * r; no biases.  side and sweeps as in als(); of hyper only P_reg and Q_reg are read.
-        Rows without entries become zero rows.  Returns the number of rows left unchanged by a failed pivot."""
+        Rows without entries become zero rows.  solver "cholesky" solves every row exactly; "cg" gives the rows of at most
+        ALS_CHUNK entries cg_steps conjugate-gradient steps from their current factors (cu2rec_model_als_implicit_cg; cg_steps is
+        not read otherwise).  Returns the number of rows left unchanged (a failed pivot; a non-finite or negative curvature)."""
         h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
         if side not in ALS_SIDES:
             raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        _solver(solver)
         total = 0
         for _ in range(int(sweeps)):
             for s in ALS_SIDES[side]:
                 n = C.c_int()
-                check(lib().cu2rec_model_als_implicit(self._h, train._h, C.byref(h), float(alpha), s, C.byref(n)))
+                if solver == "cg":
+                    check(lib().cu2rec_model_als_implicit_cg(self._h, train._h, C.byref(h), float(alpha), s, int(cg_steps), C.byref(n)))
+                else:
+                    check(lib().cu2rec_model_als_implicit(self._h, train._h, C.byref(h), float(alpha), s, C.byref(n)))
                 total += n.value
         return total
 
@@ -428,23 +441,30 @@ def default_mode(n_factors):
 
 
 def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=None, mode=None, verbose=True,
-          P=None, user_bias=None, return_stats=False, alpha=40.0):
+          P=None, user_bias=None, return_stats=False, alpha=40.0, solver="cholesky", cg_steps=3):
     """train() (training.h:12-15).  mode None = default_mode(cfg.n_factors); "hogwild" opts into sgd.cu's racy semantics; "als"
     trains by alternating least squares (one iteration = one sweep; no learning rate, so no decay); "ials" by its implicit-feedback
     form with confidence weight alpha * r (cu2rec_train_implicit: test_matrix is not read and may be None, and the third element
-    returned is the objective at the checked sweeps, float64, NaN elsewhere).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
+    returned is the objective at the checked sweeps, float64, NaN elsewhere; solver="cg" runs the sweeps with cg_steps conjugate-gradient
+    steps per row, cu2rec_train_implicit_cg -- solver and cg_steps are read in this mode only).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
     otherwise everything starts from the seed-42 normal init.  Returns (P, Q, losses, user_bias,
     item_bias) like the reference's out-pointers; cfg.learning_rate / cfg.cur_iterations are
     updated in place."""
+    if mode == "ials":
+        _solver(solver)
     tr = train_matrix if isinstance(train_matrix, DeviceCSR) else DeviceCSR(train_matrix)
     gb = tr.host.global_bias if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
     stats = TrainStats()
     if mode == "ials":
         losses = np.empty(max(cfg.total_iterations, 1), np.float64)
-        check(lib().cu2rec_train_implicit(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses),
-                                          C.byref(stats)))
+        if solver == "cg":
+            check(lib().cu2rec_train_implicit_cg(tr._h, C.byref(cfg), model._h, float(alpha), int(cg_steps), 1 if verbose else 0,
+                                                 _ptr(losses), C.byref(stats)))
+        else:
+            check(lib().cu2rec_train_implicit(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses),
+                                              C.byref(stats)))
     else:
         te = test_matrix if isinstance(test_matrix, DeviceCSR) else DeviceCSR(test_matrix)
         losses = np.empty(max(cfg.total_iterations, 1), np.float32)

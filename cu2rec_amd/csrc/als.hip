@@ -21,7 +21,8 @@
 // layout [pair][16][64].  (2) A row's own entries are staged as two operands, A = [w q | 1 + w] and B = [q | 0] (w = alpha r), so
 // that the product's first f rows are sum w q q^T and its row f is the right-hand side sum (1 + w) q; the accumulators start from
 // G0 (AlsKind::Implicit).  (3) The system has order f (no bias), plain reg on the diagonal, and a row without entries is written
-// as zeros.
+// as zeros.  With cg_steps > 0 (cu2rec_model_als_implicit_cg) the rows of at most kAlsChunk entries go to als_cg.hip instead of the
+// short kernel; G0 and the long rows' kernels are the same.
 #include <hip/hip_runtime.h>
 
 #include <cstring>  // (rocPRIM's headers call memset without including it)
@@ -363,7 +364,7 @@ void run_global_gram(AlsCache &c, const float *X, int ldx, int n, int n_factors,
 }
 
 template <int NT, AlsKind K>
-int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
+int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps = 0) {
     constexpr int pairs = AlsShape<NT>::pairs;
     constexpr int operands = K == AlsKind::Implicit ? 2 : 1;
     const size_t stage_bytes = static_cast<size_t>(operands) * kAlsStep * AlsShape<NT>::C * sizeof(float);
@@ -392,7 +393,9 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
         a.g0 = c.g0.ptr;
     }
     const int grid = std::min(side.rows, max_rows);
-    if (grid > 0)
+    if (K == AlsKind::Implicit && cg_steps > 0)  // the short rows by conjugate gradients (als_cg.hip); the long rows as always
+        ials_cg_short_rows(c, side, p, max_rows, cg_steps, stream);
+    else if (grid > 0)
         hipLaunchKernelGGL((als_short_kernel<NT, K>), dim3(grid), dim3(kAlsThreads), short_bytes, stream, a);
     CU2REC_HIP(hipGetLastError());
     const int L = static_cast<int>(side.long_rows.size());
@@ -618,9 +621,9 @@ int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
                            [&](auto tiles) { return run_half_step<tiles(), AlsKind::Explicit>(c, side, p, max_rows, stream); });
 }
 
-int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
+int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps) {
     return dispatch_1_to_8(ials_tiles(p.n_factors), "cu2rec_model_als_implicit: n_factors above 252 is not supported",
-                           [&](auto tiles) { return run_half_step<tiles(), AlsKind::Implicit>(c, side, p, max_rows, stream); });
+                           [&](auto tiles) { return run_half_step<tiles(), AlsKind::Implicit>(c, side, p, max_rows, stream, cg_steps); });
 }
 
 double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t stream) {

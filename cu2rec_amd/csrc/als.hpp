@@ -57,6 +57,7 @@ struct AlsCache {
     // implicit feedback: X^T X of the partner side (and of the other side, for the objective) in the accumulator layout
     // [tile pair][16][64] of als.hip, rebuilt by every call that reads it; the objective pass's per-block partial sums
     DeviceBuffer<float> g0, g0_other;
+    DeviceBuffer<float> g0_dense;  // the conjugate-gradient half-step's G0: dense [f][f rounded up to 4], unpacked from g0 (als_cg.hip)
     DeviceBuffer<double> objective;
 };
 
@@ -98,8 +99,15 @@ void als_plan_side(AlsSide &side, hipStream_t stream);
 // one half-step over every row of `side` (rows < max_rows); returns the number of rows left unchanged by a failed pivot
 int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream);
 // the implicit-feedback half-step: G0 = X^T X over partner rows [0, p.x_rows), then every row of `side` -- rows without entries become
-// zero rows; p.global_bias, p.reg_bias and p.xb are not read, the solved biases are written as 0.  Returns als_half_step's count
-int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream);
+// zero rows; p.global_bias, p.reg_bias and p.xb are not read, the solved biases are written as 0.  Returns als_half_step's count.
+// cg_steps > 0: the rows of 1 .. kAlsChunk entries take cg_steps conjugate-gradient steps from their current factors instead
+// (ials_cg_short_rows); the longer rows are solved exactly by the same kernels, to the same bits, either way
+int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps = 0);
+// als_cg.hip: c.g0 (formed by the caller on `stream`) unpacked into c.g0_dense, then every row of `side` (rows < max_rows) of at
+// most kAlsChunk entries: cg_steps steps of CG on its order-f system applied as an operator; rows without entries become zero
+// rows, longer rows are not touched.  A row whose iteration meets a non-finite or negative curvature, or ends non-finite, keeps
+// its bits and is counted in c.unsolved (allocated and zeroed by the caller)
+void ials_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, int max_rows, int cg_steps, hipStream_t stream);
 // the implicit objective L (two global Grams, one pass over the entries and both sides' rows in double); synchronises the stream
 double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t stream);
 

@@ -531,14 +531,15 @@ int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hi
 }
 
 // Implicit feedback (include/cu2rec_amd.h: cu2rec_model_als_implicit).  The same order as als(): argument checks, then the device.
-int DeviceModel::ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream) {
-    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, "cu2rec_model_als_implicit: side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+int DeviceModel::ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream, int cg_steps) {
+    const std::string fn = cg_steps > 0 ? "cu2rec_model_als_implicit_cg" : "cu2rec_model_als_implicit";
+    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, (fn + ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS").c_str());
     const bool users = side == CU2REC_SIDE_USERS;
     const float reg = users ? h.P_reg : h.Q_reg;
-    require(std::isfinite(reg) && reg > 0.f, "cu2rec_model_als_implicit: the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
-    require(std::isfinite(alpha) && alpha >= 0.f, "cu2rec_model_als_implicit: alpha must be finite and >= 0");
-    require(train.rows <= rows && train.max_item < cols && train.cols <= cols, "cu2rec_model_als_implicit: ratings exceed the model's shape");
-    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als_implicit: n_factors above 252 is not supported");
+    require(std::isfinite(reg) && reg > 0.f, (fn + ": the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0").c_str());
+    require(std::isfinite(alpha) && alpha >= 0.f, (fn + ": alpha must be finite and >= 0").c_str());
+    require(train.rows <= rows && train.max_item < cols && train.cols <= cols, (fn + ": ratings exceed the model's shape").c_str());
+    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, fn + ": n_factors above 252 is not supported");
     require_device();
     check_faults();
     finish_swap();
@@ -547,7 +548,7 @@ int DeviceModel::ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha
                          : AlsProblem{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, 0.f, reg, 0.f};
     p.alpha = alpha;
     p.x_rows = users ? train.cols : train.rows;  // every partner row inside the CSR counts
-    const int unsolved = ials_half_step(*train.als, rows_of_side, p, users ? rows : cols, stream);
+    const int unsolved = ials_half_step(*train.als, rows_of_side, p, users ? rows : cols, stream, cg_steps);
     other_in_sync = false;
     return unsolved;
 }
@@ -870,6 +871,16 @@ int cu2rec_model_als_implicit(cu2rec_model *m, const cu2rec_csr *train, const cu
     return guarded([&] {
         require(m && train && hyper, "cu2rec_model_als_implicit: null argument");
         const int n = m->impl.ials(train->impl, *hyper, alpha, side, nullptr);
+        if (unsolved) *unsolved = n;
+    });
+}
+
+int cu2rec_model_als_implicit_cg(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
+                                 int cg_steps, int *unsolved) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_als_implicit_cg: null argument");
+        require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_model_als_implicit_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
+        const int n = m->impl.ials(train->impl, *hyper, alpha, side, nullptr, cg_steps);
         if (unsolved) *unsolved = n;
     });
 }

@@ -88,7 +88,9 @@ struct DeviceModel {
     // one exact ALS half-step (side: CU2REC_SIDE_USERS / CU2REC_SIDE_ITEMS); returns the rows a failed pivot left unchanged
     int als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream);
     // one implicit-feedback half-step (confidence weight alpha * r per entry, every user x item pair counted); same return
-    int ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream);
+    // cg_steps > 0: rows of at most CU2REC_ALS_CHUNK entries take that many conjugate-gradient steps from their current factors
+    // (cu2rec_model_als_implicit_cg)
+    int ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream, int cg_steps = 0);
     // the implicit objective at the current model (synchronises)
     double implicit_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream);
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,

@@ -56,9 +56,10 @@ void train(const DeviceCsr &train_csr, const DeviceCsr &test_csr, cu2rec_config 
 
 // Implicit-feedback training (include/cu2rec_amd.h: cu2rec_train_implicit): the schedule above with implicit sweeps for the
 // iterations and the objective for the loss.  There is no test set and no learning rate: the schedule's own lines and its
-// patience stay off; the objective's line is printed here.
-void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &model, float alpha, bool verbose, double *objectives,
-                    cu2rec_train_stats *stats) {
+// patience stay off; the objective's line is printed here.  cg_steps > 0 (cu2rec_train_implicit_cg): the same loop with
+// conjugate-gradient half-steps.
+void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &model, float alpha, int cg_steps, bool verbose,
+                    double *objectives, cu2rec_train_stats *stats) {
     require(cfg.n_factors == model.n_factors, "cu2rec_train_implicit: cfg.n_factors differs from the model's");
     require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_implicit: bad iteration counts");
     hipStream_t stream = nullptr;
@@ -73,10 +74,10 @@ void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel 
         [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
             hyper = h;
             for (int k = 0; k < n; ++k) {
-                const int u = model.ials(train_csr, h, alpha, CU2REC_SIDE_USERS, s);
+                const int u = model.ials(train_csr, h, alpha, CU2REC_SIDE_USERS, s, cg_steps);
                 solved += train_csr.als->users.rows_with_ratings - u;
                 if (cfg.is_train) {
-                    const int i = model.ials(train_csr, h, alpha, CU2REC_SIDE_ITEMS, s);
+                    const int i = model.ials(train_csr, h, alpha, CU2REC_SIDE_ITEMS, s, cg_steps);
                     solved += train_csr.als->items.rows_with_ratings - i;
                 }
             }
@@ -102,7 +103,17 @@ extern "C" int cu2rec_train_implicit(const cu2rec_csr *train, cu2rec_config *cfg
     using namespace cu2rec;
     return guarded([&] {
         require(train && cfg && model, "cu2rec_train_implicit: null argument");
-        cu2rec::train_implicit(unwrap(train), *cfg, unwrap(model), alpha, verbose != 0, objectives, stats);
+        cu2rec::train_implicit(unwrap(train), *cfg, unwrap(model), alpha, 0, verbose != 0, objectives, stats);
+    });
+}
+
+extern "C" int cu2rec_train_implicit_cg(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int cg_steps,
+                                        int verbose, double *objectives, cu2rec_train_stats *stats) {
+    using namespace cu2rec;
+    return guarded([&] {
+        require(train && cfg && model, "cu2rec_train_implicit_cg: null argument");
+        require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_train_implicit_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
+        cu2rec::train_implicit(unwrap(train), *cfg, unwrap(model), alpha, cg_steps, verbose != 0, objectives, stats);
     });
 }
 

@@ -505,6 +505,28 @@ int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hype
  * ---------------------------------------------------------------------------------------- */
 int cu2rec_model_als_implicit(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
                               int *unsolved);
+/* The same half-step by conjugate gradients (Takacs, Pilaszy, Tikk: Applications of the conjugate gradient method for implicit
+ * feedback collaborative filtering, RecSys 2011): an approximate solver, warm-started from the row's current factors, that never
+ * forms the row's Gram.  With A v = G0 v + sum_entries w (q . v) q + reg v applied as an operator (G0 = X^T X over the partner
+ * rows inside the CSR, formed as above) and b = sum_entries (1 + w) q, a row is treated by its length:
+ *   0 entries: written as zeros, not counted -- as above.
+ *   more than CU2REC_ALS_CHUNK entries: solved exactly by the kernels of cu2rec_model_als_implicit, bit for bit what that call
+ *     writes.  Long rows are solved exactly whatever cg_steps is.
+ *   1 .. CU2REC_ALS_CHUNK entries: x0 = the row's current n_factors factors (the padding floats are never read as data; if any
+ *     of them is not finite, x0 = 0); r = b - A x0, p = r, rho = r . r; then cg_steps times: if rho == 0 stop and keep x;
+ *     d = p . A p; if d == 0 stop and keep x; a = rho / d; x += a p; r -= a A p; rho' = r . r; p = r + (rho' / rho) p; rho = rho'.
+ *     x is written with padding floats 0 and bias +0.0.
+ * A row is left with the bits it had and counted in *unsolved when a rho or a d is not finite, a d is negative or the final x is
+ * not finite.  CG does NOT promise to detect an indefinite system: negative weights are outside the model, and a row that holds
+ * some may come back solved, wrong and uncounted (the Cholesky call above counts it).
+ * Determinism as above: every sum's order is a function of the row's own length and n_factors, there are no float atomics,
+ * results are bit-identical run to run, and a row solved from a one-row CSR of the same cols equals that row solved among all the
+ * others.  One wavefront per row; G0 is unpacked once per call into a dense matrix of n_factors^2 floats kept with the cu2rec_csr.
+ * cg_steps must lie in [1, CU2REC_ALS_CG_MAX_STEPS], else CU2REC_EINVAL, checked -- like everything cu2rec_model_als_implicit
+ * checks, with the same codes -- before the device or the model is touched. */
+enum { CU2REC_ALS_CG_MAX_STEPS = 256 };
+int cu2rec_model_als_implicit_cg(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
+                                 int cg_steps, int *unsolved);
 /* *L = the objective above at the model's current values: the all-pairs term as 1/2 <P^T P, Q^T Q> from two global Grams (f32, as
  * the half-step forms them), the entries term and the two norms from one pass over the entries and the rows, summed in double
  * like the loss pass.  Regularisers >= 0 are accepted here.  Reads the model only. */
@@ -541,6 +563,10 @@ int cu2rec_train(const cu2rec_csr *train, const cu2rec_csr *test, cu2rec_config 
  * without entries, written as zeros, are not counted); the stats' MAE / RMSE fields are 0. */
 int cu2rec_train_implicit(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose,
                           double *objectives, cu2rec_train_stats *stats);
+/* cu2rec_train_implicit's loop, lines, cadence and stats with sweeps of cu2rec_model_als_implicit_cg at cg_steps steps
+ * (cg_steps outside [1, CU2REC_ALS_CG_MAX_STEPS]: CU2REC_EINVAL before anything is touched). */
+int cu2rec_train_implicit_cg(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int cg_steps,
+                             int verbose, double *objectives, cu2rec_train_stats *stats);
 
 /* ------------------------------------------------------------------------------------------
  * Sharding by user (multi-GPU; the reference is single device).  Host-side planner:

@@ -1,7 +1,7 @@
 """Times the alternating-least-squares half-steps (cu2rec_model_als) on the synthetic ML-20M and Netflix shapes and prints each time
 next to its Gram roofline.
 
-    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3] [--implicit [--alpha 40]]
+    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3] [--implicit [--alpha 40] [--cg-steps N]]
 
 For every shape: the item half-step's first call on a fresh cu2rec_csr (it builds the item-major view), the item half-step again
 (view cached), the user half-step, and a whole sweep (users then items).  Times are wall clock around the synchronous call (the
@@ -12,7 +12,12 @@ gather (nnz x 4 (f + 1) bytes) and the per-row Cholesky (about rows x (f + 1)^3 
 --implicit: after the explicit rows, the implicit-feedback half-steps and sweep (cu2rec_model_als_implicit) in the same process, on
 the same cu2rec_csr and a model of their own, with the ratio implicit / explicit of the sweeps.  An implicit half-step does the
 same per-entry work, solves EVERY row (rows without entries are written as zeros) and forms the partner side's global Gram first
-(rows x f^2 multiply-adds over both half-steps of a sweep: users + items rows)."""
+(rows x f^2 multiply-adds over both half-steps of a sweep: users + items rows).
+
+--cg-steps N (with --implicit): after the implicit rows, the same half-steps and sweep by N conjugate-gradient steps per row
+(cu2rec_model_als_implicit_cg) on a model of their own, each with its ratio to the implicit Cholesky time above it.  Per row of n
+entries CG does (N + 1) x (f^2 + 2 n f) multiply-adds -- one operator application for the starting residual, one per step --
+against n f^2 / 2 for the Gram's lower triangle plus f^3 / 3 for Cholesky."""
 import argparse
 import os
 import sys
@@ -46,6 +51,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--implicit", action="store_true")
     ap.add_argument("--alpha", type=float, default=40.0)
+    ap.add_argument("--cg-steps", type=int, default=0)
     args = ap.parse_args()
     f = args.factors
     for name in args.shapes.split(","):
@@ -85,6 +91,25 @@ def main():
             print("  implicit / explicit sweep: %.2f   (global Grams: (%d + %d) rows x f^2 = %.2e multiply-adds per sweep)"
                   % (rows[-1][1] / explicit_sweep, tr.rows, tr.cols, (tr.rows + tr.cols) * float(f) ** 2), flush=True)
             m.close()
+            if args.cg_steps > 0:
+                exact = [t for _, t in rows]
+                kw = dict(solver="cg", cg_steps=args.cg_steps)
+                m = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
+                assert m.ials(d, HYPER, args.alpha, "both", **kw) == 0
+                rows = [("implicit CG-%d items" % args.cg_steps, best(lambda: m.ials(d, HYPER, args.alpha, "items", **kw), args.reps)),
+                        ("implicit CG-%d users" % args.cg_steps, best(lambda: m.ials(d, HYPER, args.alpha, "users", **kw), args.reps)),
+                        ("implicit CG-%d sweep (users + items)" % args.cg_steps,
+                         best(lambda: m.ials(d, HYPER, args.alpha, "both", **kw), args.reps))]
+                for (label, t), t_exact in zip(rows, exact):
+                    print("  %-38s %9.2f ms   (%.2f x the implicit Cholesky time)" % (label, 1e3 * t, t / t_exact), flush=True)
+                n_users, n_items = np.diff(tr.indptr), np.bincount(tr.indices, minlength=tr.cols)
+                for side, n in (("users", n_users), ("items", n_items)):
+                    short = n[(n > 0) & (n <= cu.api.ALS_CHUNK)].astype(np.float64)
+                    cg = (args.cg_steps + 1) * (len(short) * float(f) ** 2 + 2.0 * short.sum() * f)
+                    chol = short.sum() * f ** 2 / 2.0 + len(short) * f ** 3 / 3.0
+                    print("  rows of 1 .. %d entries, %s: %d (%d longer ones solved exactly); CG %.2e multiply-adds, Gram + Cholesky %.2e"
+                          % (cu.api.ALS_CHUNK, side, len(short), int((n > cu.api.ALS_CHUNK).sum()), cg, chol), flush=True)
+                m.close()
         d.close()
 
 
