@@ -134,6 +134,8 @@ SIGNATURES = {
     "cu2rec_model_similar": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_model_top_users": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_model_als": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_int, _ip]),
+    "cu2rec_model_als_cg": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_int, C.c_int, _ip]),
+    "cu2rec_train_als_cg": (C.c_int, [_P, _P, C.POINTER(Config), _P, C.c_int, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_model_als_implicit": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_float, C.c_int, _ip]),
     "cu2rec_model_implicit_objective": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_float, _dp]),
     "cu2rec_train_implicit": (C.c_int, [_P, C.POINTER(Config), _P, C.c_float, C.c_int, _P, C.POINTER(TrainStats)]),

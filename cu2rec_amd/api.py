@@ -24,7 +24,7 @@ METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE}
 MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "pingpong": SGD_PINGPONG,
          "blocksolve": SGD_BLOCKSOLVE, "als": ALS}
 ALS_SIDES = {"users": (SIDE_USERS,), "items": (SIDE_ITEMS,), "both": (SIDE_USERS, SIDE_ITEMS)}
-IALS_SOLVERS = ("cholesky", "cg")  # Model.ials / train(mode="ials"): the exact solver, or conjugate-gradient steps per row
+IALS_SOLVERS = ("cholesky", "cg")  # Model.als / Model.ials / train(mode="als" | "ials"): the exact solver, or conjugate-gradient steps per row
 ALS_CG_MAX_STEPS = 256             # CU2REC_ALS_CG_MAX_STEPS
 
 
@@ -287,19 +287,25 @@ class Model:
         check(lib().cu2rec_model_sgd(self._h, train._h, C.byref(h), int(seed), int(iter0), int(n_iters), _mode(mode),
                                      1 if update_items else 0))
 
-    def als(self, train, hyper, side="both", sweeps=1):
-        """Exact alternating-least-squares half-steps on the SGD modes' objective (cu2rec_model_als): side "users" solves P and
+    def als(self, train, hyper, side="both", sweeps=1, solver="cholesky", cg_steps=3):
+        """Alternating-least-squares half-steps on the SGD modes' objective (cu2rec_model_als): side "users" solves P and
         user_bias against the frozen items, "items" the reverse, "both" a sweep (users, then items); repeated `sweeps` times.
         hyper: Hyper or (learning_rate, P_reg, Q_reg, user_bias_reg, item_bias_reg) -- the learning rate is ignored.
-        Returns the number of rows left unchanged by a failed pivot (summed over the half-steps)."""
+        solver "cholesky" solves every row exactly; "cg" gives the rows of at most ALS_CHUNK ratings cg_steps conjugate-gradient
+        steps from their current factors and bias (cu2rec_model_als_cg; cg_steps is not read otherwise).
+        Returns the number of rows left unchanged (a failed pivot; a non-finite or negative curvature), summed over the half-steps."""
         h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
         if side not in ALS_SIDES:
             raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        _solver(solver)
         total = 0
         for _ in range(int(sweeps)):
             for s in ALS_SIDES[side]:
                 n = C.c_int()
-                check(lib().cu2rec_model_als(self._h, train._h, C.byref(h), s, C.byref(n)))
+                if solver == "cg":
+                    check(lib().cu2rec_model_als_cg(self._h, train._h, C.byref(h), s, int(cg_steps), C.byref(n)))
+                else:
+                    check(lib().cu2rec_model_als(self._h, train._h, C.byref(h), s, C.byref(n)))
                 total += n.value
         return total
 
@@ -446,12 +452,13 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     trains by alternating least squares (one iteration = one sweep; no learning rate, so no decay); "ials" by its implicit-feedback
     form with confidence weight alpha * r (cu2rec_train_implicit: test_matrix is not read and may be None, and the third element
     returned is the objective at the checked sweeps, float64, NaN elsewhere; solver="cg" runs the sweeps with cg_steps conjugate-gradient
-    steps per row, cu2rec_train_implicit_cg -- solver and cg_steps are read in this mode only).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
+    steps per row, cu2rec_train_implicit_cg; with mode "als" it is cu2rec_train_als_cg -- solver and cg_steps are read in these two modes
+    only).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
     otherwise everything starts from the seed-42 normal init.  Returns (P, Q, losses, user_bias,
     item_bias) like the reference's out-pointers; cfg.learning_rate / cfg.cur_iterations are
     updated in place."""
-    if mode == "ials":
+    if mode in ("als", "ials"):
         _solver(solver)
     tr = train_matrix if isinstance(train_matrix, DeviceCSR) else DeviceCSR(train_matrix)
     gb = tr.host.global_bias if global_bias is None else global_bias
@@ -469,8 +476,12 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
         te = test_matrix if isinstance(test_matrix, DeviceCSR) else DeviceCSR(test_matrix)
         losses = np.empty(max(cfg.total_iterations, 1), np.float32)
         mode = default_mode(cfg.n_factors) if mode is None else mode
-        check(lib().cu2rec_train(tr._h, te._h, C.byref(cfg), model._h, _mode(mode), 1 if verbose else 0, _ptr(losses),
-                                 C.byref(stats)))
+        if mode == "als" and solver == "cg":
+            check(lib().cu2rec_train_als_cg(tr._h, te._h, C.byref(cfg), model._h, int(cg_steps), 1 if verbose else 0, _ptr(losses),
+                                            C.byref(stats)))
+        else:
+            check(lib().cu2rec_train(tr._h, te._h, C.byref(cfg), model._h, _mode(mode), 1 if verbose else 0, _ptr(losses),
+                                     C.byref(stats)))
     Pn, Qn, ub, ib = model.download()
     model.close()
     out = (Pn, Qn, losses[:cfg.total_iterations], ub, ib)

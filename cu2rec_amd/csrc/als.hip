@@ -22,7 +22,8 @@
 // that the product's first f rows are sum w q q^T and its row f is the right-hand side sum (1 + w) q; the accumulators start from
 // G0 (AlsKind::Implicit).  (3) The system has order f (no bias), plain reg on the diagonal, and a row without entries is written
 // as zeros.  With cg_steps > 0 (cu2rec_model_als_implicit_cg) the rows of at most kAlsChunk entries go to als_cg.hip instead of the
-// short kernel; G0 and the long rows' kernels are the same.
+// short kernel; G0 and the long rows' kernels are the same.  The explicit half-step has the same switch (cu2rec_model_als_cg): its
+// short rows go to als_cg.hip's explicit instantiation, which needs no G0 at all.
 #include <hip/hip_runtime.h>
 
 #include <cstring>  // (rocPRIM's headers call memset without including it)
@@ -41,10 +42,6 @@ namespace {
 
 constexpr int kAlsThreads = 512;
 constexpr int kAlsWaves = kAlsThreads / 64;
-
-// What a kernel template is compiled for: the explicit half-step ([x | 1 | t] staged once, order f + 1), the implicit one (two
-// operands, seeded from G0, order f), or a tile of the global Gram G0 itself ([x | 0] gathered by row number).
-enum class AlsKind { Explicit, Implicit, Gram };
 
 struct AlsArgs {
     const int *indptr, *indices;
@@ -373,7 +370,7 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
     if (short_bytes > kMaxLds)
         fail(CU2REC_EUNSUPPORTED, std::string(K == AlsKind::Implicit ? "cu2rec_model_als_implicit" : "cu2rec_model_als") +
                                       ": n_factors too large for the LDS of one workgroup");
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_short_kernel<NT, K>), kMaxLds);
+    if (cg_steps <= 0) ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_short_kernel<NT, K>), kMaxLds);
     ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_chunk_kernel<NT, K>), kMaxLds);
     ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_long_kernel<NT, K>), kMaxLds);
     if (!c.unsolved.ptr) c.unsolved.allocate(1);
@@ -393,9 +390,10 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
         a.g0 = c.g0.ptr;
     }
     const int grid = std::min(side.rows, max_rows);
-    if (K == AlsKind::Implicit && cg_steps > 0)  // the short rows by conjugate gradients (als_cg.hip); the long rows as always
-        ials_cg_short_rows(c, side, p, max_rows, cg_steps, stream);
-    else if (grid > 0)
+    if (cg_steps > 0) {  // the short rows by conjugate gradients (als_cg.hip); the long rows as always
+        if constexpr (K == AlsKind::Implicit) ials_cg_short_rows(c, side, p, max_rows, cg_steps, stream);
+        else als_cg_short_rows(c, side, p, max_rows, cg_steps, stream);
+    } else if (grid > 0)
         hipLaunchKernelGGL((als_short_kernel<NT, K>), dim3(grid), dim3(kAlsThreads), short_bytes, stream, a);
     CU2REC_HIP(hipGetLastError());
     const int L = static_cast<int>(side.long_rows.size());
@@ -615,10 +613,10 @@ void als_plan_side(AlsSide &side, hipStream_t stream) {
     put(side.d_chunk_hi, hi);
 }
 
-int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream) {
+int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps) {
     const int nt = (p.n_factors + 2 + 31) / 32;  // columns f + 2: factors, the 1, t
     return dispatch_1_to_8(nt, "cu2rec_model_als: n_factors above 252 is not supported",
-                           [&](auto tiles) { return run_half_step<tiles(), AlsKind::Explicit>(c, side, p, max_rows, stream); });
+                           [&](auto tiles) { return run_half_step<tiles(), AlsKind::Explicit>(c, side, p, max_rows, stream, cg_steps); });
 }
 
 int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps) {

@@ -24,6 +24,11 @@ constexpr int kAlsMaxChunks = CU2REC_ALS_MAX_CHUNKS;     // 64
 constexpr size_t kAlsWorkspaceBytes = CU2REC_ALS_WORKSPACE_BYTES;  // 64 MiB of partial Grams at once: the workspace bound
 constexpr int kAlsMaxFactors = CU2REC_ALS_MAX_FACTORS;   // 252: system order f + 1 <= 253, the packed factor fits one workgroup's LDS
 
+// What a kernel template is compiled for: the explicit half-step ([x | 1 | t] staged once, order f + 1), the implicit one (two
+// operands, seeded from G0, order f), or a tile of the global Gram G0 itself ([x | 0] gathered by row number).  The
+// conjugate-gradient kernel (als_cg.hip) is compiled for the first two.
+enum class AlsKind { Explicit, Implicit, Gram };
+
 __host__ __device__ inline int als_chunks(int n) {
     const int c = (n + kAlsChunk - 1) / kAlsChunk;
     return c < kAlsMaxChunks ? c : kAlsMaxChunks;
@@ -97,7 +102,15 @@ void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, con
 // fills side.long_rows / chunk lists from the device indptr (once per side)
 void als_plan_side(AlsSide &side, hipStream_t stream);
 // one half-step over every row of `side` (rows < max_rows); returns the number of rows left unchanged by a failed pivot
-int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream);
+// cg_steps > 0 (cu2rec_model_als_cg): the rows of 1 .. kAlsChunk ratings take cg_steps conjugate-gradient steps from their current
+// [factors; bias] instead (als_cg_short_rows); the longer rows are solved exactly by the same kernels, to the same bits, either way
+int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps = 0);
+// als_cg.hip: every row of `side` (rows < max_rows) of 1 .. kAlsChunk ratings: cg_steps steps of CG on its order-(f + 1) system
+//   A v = sum_i z_i (z_i . v) + n diag(reg, ..., reg, reg_bias) v,   b = sum_i t_i z_i,   z_i = [x_i; 1]
+// applied as an operator, from x0 = [the row's factors; its bias].  Rows without ratings and longer rows are not touched.  A row whose
+// iteration meets a non-finite or negative curvature, or ends non-finite, keeps its bits and is counted in c.unsolved (allocated and
+// zeroed by the caller)
+void als_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, int max_rows, int cg_steps, hipStream_t stream);
 // the implicit-feedback half-step: G0 = X^T X over partner rows [0, p.x_rows), then every row of `side` -- rows without entries become
 // zero rows; p.global_bias, p.reg_bias and p.xb are not read, the solved biases are written as 0.  Returns als_half_step's count.
 // cg_steps > 0: the rows of 1 .. kAlsChunk entries take cg_steps conjugate-gradient steps from their current factors instead

@@ -16,6 +16,14 @@
 // lanes by a butterfly and w (q . v) q accumulated per group; the four groups' partial sums go through LDS and are added in group
 // order.  Every sum's order is a function of the row's length and f alone: no float atomics, nothing that depends on which
 // wavefront or workgroup picked the row up.
+//
+// The explicit half-step (als.hpp: als_cg_short_rows; cu2rec_model_als_cg) is the AlsKind::Explicit case of the same templates: the
+// system has order D = f + 1, x = [factors; bias], z_e = [q_e; 1] and
+//   A v = sum_e (z_e . v) z_e + n diag(reg, ..., reg, reg_bias) v,   b = sum_e t_e z_e,   t_e = (r_e - gb) - the partner's bias.
+// OWNER: E = ceil((f + 1) / 64), the bias is element f.  ENTRY: the same gather with column f a synthesised 1.0 (never loaded, also
+// where f is a multiple of 4 and column f starts a float4 of its own); the per-entry scalar is (z . v), the right-hand side's
+// weight t.  There is no G0: nothing is unpacked or staged, the diagonal term is formed in registers, and the kernel has no
+// workgroup barrier at all.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,7 +44,7 @@ struct CgArgs {
     const int *indptr, *indices;
     const float *data;
     AlsProblem p;
-    const float *g0;  // dense, symmetric: [f][S]
+    const float *g0;  // dense, symmetric: [f][S] (AlsKind::Implicit only)
     int S, rows, steps;
     int *unsolved;
 };
@@ -80,7 +88,9 @@ __device__ __forceinline__ float owner_dot(const float (&a)[E], const float (&b)
     return wave_sum(s);
 }
 
-// partner row `idx`, columns c0 .. c0 + 3 (c0 < 64 E), zero from column F on: the padding floats are never read as data
+// partner row `idx`, columns c0 .. c0 + 3 (c0 < 64 E), zero from column F on: the padding floats are never read as data.
+// AlsKind::Explicit: column F is the constant 1 of z = [q; 1], synthesised here
+template <AlsKind K>
 __device__ __forceinline__ float4 load_q(const AlsProblem &p, int idx, int c0) {
     const int F = p.n_factors;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -90,12 +100,18 @@ __device__ __forceinline__ float4 load_q(const AlsProblem &p, int idx, int c0) {
         if (c0 + 2 >= F) v.z = 0.f;
         if (c0 + 3 >= F) v.w = 0.f;
     }
+    if constexpr (K == AlsKind::Explicit) {
+        if (c0 == F) v.x = 1.f;
+        if (c0 + 1 == F) v.y = 1.f;
+        if (c0 + 2 == F) v.z = 1.f;
+        if (c0 + 3 == F) v.w = 1.f;
+    }
     return v;
 }
 
 // ENTRY pass over entries [lo, hi): t = sum_e w_e (q_e . v) q_e with v read from pv; FIRST: also b = sum_e (1 + w_e) q_e.
-// Results in the OWNER map.  part: the wavefront's [4][64 E] floats.
-template <int E, bool FIRST>
+// AlsKind::Explicit: t = sum_e (z_e . v) z_e and b = sum_e t_e z_e.  Results in the OWNER map.  part: the wavefront's [4][64 E] floats.
+template <int E, bool FIRST, AlsKind K>
 __device__ __forceinline__ void entry_pass(const CgArgs &a, int lo, int hi, const float *pv, float *part, float (&t)[E],
                                            float (&b)[E]) {
     constexpr int FS = 64 * E;
@@ -109,7 +125,7 @@ __device__ __forceinline__ void entry_pass(const CgArgs &a, int lo, int hi, cons
     }
     for (int e0 = lo; e0 < hi; e0 += 8) {  // two entries per group in flight; each group still adds its entries in ascending order
         float4 q[2][E];
-        float w[2];
+        float w[2];  // the entry's weight; AlsKind::Explicit: its right-hand side weight t (read by the first pass only)
         bool on[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -117,9 +133,11 @@ __device__ __forceinline__ void entry_pass(const CgArgs &a, int lo, int hi, cons
             on[u] = e < hi;
             const int ec = on[u] ? e : hi - 1;
             const int idx = a.indices[ec];
-            w[u] = a.p.alpha * a.data[ec];
+            if constexpr (K == AlsKind::Implicit) w[u] = a.p.alpha * a.data[ec];
+            else if constexpr (FIRST) w[u] = (a.data[ec] - a.p.global_bias) - a.p.xb[idx];
+            else w[u] = 0.f;
 #pragma unroll
-            for (int k = 0; k < E; ++k) q[u][k] = load_q(a.p, idx, 4 * l16 + 64 * k);
+            for (int k = 0; k < E; ++k) q[u][k] = load_q<K>(a.p, idx, 4 * l16 + 64 * k);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -134,8 +152,8 @@ __device__ __forceinline__ void entry_pass(const CgArgs &a, int lo, int hi, cons
 #pragma unroll
             for (int m = 8; m > 0; m >>= 1) d = d + __shfl_xor(d, m, 16);
             if (on[u]) {
-                const float s = w[u] * d;
-                [[maybe_unused]] const float bw = 1.f + w[u];
+                const float s = K == AlsKind::Implicit ? w[u] * d : d;
+                [[maybe_unused]] const float bw = K == AlsKind::Implicit ? 1.f + w[u] : w[u];
 #pragma unroll
                 for (int k = 0; k < E; ++k) {
                     acc[k].x = fmaf(s, q[u][k].x, acc[k].x);
@@ -209,6 +227,19 @@ __device__ __forceinline__ void apply_a(const CgArgs &a, const float *G, const f
     for (int k = 0; k < E; ++k) out[k] = lane + 64 * k < F ? (s[k] + t[k]) + a.p.reg * v[k] : 0.f;
 }
 
+// the explicit system's A v in the OWNER map: t + n diag(reg, ..., reg, reg_bias) v for a row of n ratings, zero from f + 1 on
+template <int E>
+__device__ __forceinline__ void apply_a_explicit(const CgArgs &a, int n, const float (&t)[E], const float (&v)[E], float (&out)[E]) {
+    const int lane = threadIdx.x & 63, F = a.p.n_factors;
+    const float nf = static_cast<float>(n);
+    const float nreg = nf * a.p.reg, nreg_bias = nf * a.p.reg_bias;
+#pragma unroll
+    for (int k = 0; k < E; ++k) {
+        const int c = lane + 64 * k;
+        out[k] = c <= F ? fmaf(c < F ? nreg : nreg_bias, v[k], t[k]) : 0.f;
+    }
+}
+
 template <int E>
 __device__ __forceinline__ void put_v(float *pv, const float (&v)[E]) {
     const int lane = threadIdx.x & 63;
@@ -218,15 +249,17 @@ __device__ __forceinline__ void put_v(float *pv, const float (&v)[E]) {
     wave_sync();
 }
 
-template <int E>
-__global__ __launch_bounds__(kCgThreads) void ials_cg_kernel(CgArgs a) {
+template <int E, AlsKind K>
+__global__ __launch_bounds__(kCgThreads) void als_cg_kernel(CgArgs a) {
     extern __shared__ float4 cg_smem[];
     constexpr int FS = 64 * E;
-    constexpr bool G0_IN_LDS = E <= kCgLdsElems;
+    constexpr bool explicit_kind = K == AlsKind::Explicit;
+    constexpr bool G0_IN_LDS = !explicit_kind && E <= kCgLdsElems;
     float *lds = reinterpret_cast<float *>(cg_smem);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int F = a.p.n_factors, S = a.S;
-    const float *G = a.g0;
+    const int F = a.p.n_factors;
+    [[maybe_unused]] const int S = a.S;
+    [[maybe_unused]] const float *G = a.g0;
     float *wave_lds = lds;
     if constexpr (G0_IN_LDS) {
         const int n4 = F * S / 4;
@@ -240,9 +273,11 @@ __global__ __launch_bounds__(kCgThreads) void ials_cg_kernel(CgArgs a) {
     for (int row = blockIdx.x * kCgWaves + wave; row < a.rows; row += gridDim.x * kCgWaves) {
         const int lo = a.indptr[row], hi = a.indptr[row + 1];
         float *y = a.p.Y + static_cast<size_t>(row) * a.p.ldy;
-        if (hi <= lo) {  // right-hand side 0: the zero row, not counted
-            for (int c = lane; c < a.p.ldy; c += 64) y[c] = 0.f;
-            if (lane == 0) a.p.yb[row] = 0.f;
+        if (hi <= lo) {  // right-hand side 0: the zero row, not counted; AlsKind::Explicit: the row keeps its values
+            if constexpr (!explicit_kind) {
+                for (int c = lane; c < a.p.ldy; c += 64) y[c] = 0.f;
+                if (lane == 0) a.p.yb[row] = 0.f;
+            }
             continue;
         }
         if (hi - lo > kAlsChunk) continue;  // the long rows are solved exactly by the chunk -> long kernels
@@ -252,6 +287,8 @@ __global__ __launch_bounds__(kCgThreads) void ials_cg_kernel(CgArgs a) {
         for (int k = 0; k < E; ++k) {
             const int c = lane + 64 * k;
             x[k] = c < F ? y[c] : 0.f;
+            if constexpr (explicit_kind)
+                if (c == F) x[k] = a.p.yb[row];  // element f: the row's bias
             finite = finite && isfinite(x[k]);
         }
         if (__any(!finite)) {
@@ -259,8 +296,9 @@ __global__ __launch_bounds__(kCgThreads) void ials_cg_kernel(CgArgs a) {
             for (int k = 0; k < E; ++k) x[k] = 0.f;
         }
         put_v<E>(pv, x);
-        entry_pass<E, true>(a, lo, hi, pv, part, t, b);
-        apply_a<E>(a, G, pv, t, x, ap);
+        entry_pass<E, true, K>(a, lo, hi, pv, part, t, b);
+        if constexpr (explicit_kind) apply_a_explicit<E>(a, hi - lo, t, x, ap);
+        else apply_a<E>(a, G, pv, t, x, ap);
 #pragma unroll
         for (int k = 0; k < E; ++k) {
             r[k] = b[k] - ap[k];
@@ -271,8 +309,9 @@ __global__ __launch_bounds__(kCgThreads) void ials_cg_kernel(CgArgs a) {
         for (int step = 0; ok && step < a.steps; ++step) {  // rho, d: the same bits in every lane, the exits are uniform
             if (rho == 0.f) break;
             put_v<E>(pv, p);
-            entry_pass<E, false>(a, lo, hi, pv, part, t, b);
-            apply_a<E>(a, G, pv, t, p, ap);
+            entry_pass<E, false, K>(a, lo, hi, pv, part, t, b);
+            if constexpr (explicit_kind) apply_a_explicit<E>(a, hi - lo, t, p, ap);
+            else apply_a<E>(a, G, pv, t, p, ap);
             const float d = owner_dot<E>(p, ap);
             if (!(isfinite(d) && d >= 0.f)) {
                 ok = false;
@@ -306,19 +345,35 @@ __global__ __launch_bounds__(kCgThreads) void ials_cg_kernel(CgArgs a) {
         for (int k = 0; k < E; ++k) {
             const int c = lane + 64 * k;
             if (c < a.p.ldy) y[c] = c < F ? x[k] : 0.f;
+            if constexpr (explicit_kind)
+                if (c == F) a.p.yb[row] = x[k];
         }
         for (int c = lane + FS; c < a.p.ldy; c += 64) y[c] = 0.f;
-        if (lane == 0) a.p.yb[row] = 0.f;
+        if constexpr (!explicit_kind)
+            if (lane == 0) a.p.yb[row] = 0.f;
     }
 }
 
-template <int E>
+template <int E, AlsKind K>
 void launch_cg(const CgArgs &a, int grid, hipStream_t stream) {
-    const size_t g_bytes = E <= kCgLdsElems ? static_cast<size_t>(a.p.n_factors) * a.S * sizeof(float) : 0;
-    const size_t bytes = g_bytes + static_cast<size_t>(kCgWaves) * 5 * 64 * E * sizeof(float);
-    ensure_max_dynamic_lds(reinterpret_cast<const void *>(&ials_cg_kernel<E>), 160 * 1024);
-    hipLaunchKernelGGL((ials_cg_kernel<E>), dim3(grid), dim3(kCgThreads), bytes, stream, a);
+    const size_t g_bytes = K == AlsKind::Implicit && E <= kCgLdsElems ? static_cast<size_t>(a.p.n_factors) * a.S * sizeof(float) : 0;
+    const size_t bytes = g_bytes + static_cast<size_t>(kCgWaves) * 5 * 64 * E * sizeof(float);  // explicit: 20 KiB at most
+    if constexpr (K == AlsKind::Implicit) ensure_max_dynamic_lds(reinterpret_cast<const void *>(&als_cg_kernel<E, K>), 160 * 1024);
+    hipLaunchKernelGGL((als_cg_kernel<E, K>), dim3(grid), dim3(kCgThreads), bytes, stream, a);
     CU2REC_HIP(hipGetLastError());
+}
+
+// every row of the side, kCgWaves per workgroup; elems: the per-lane element count E of the system's order
+template <AlsKind K>
+void launch_cg_rows(const CgArgs &a, int elems, hipStream_t stream) {
+    if (a.rows <= 0) return;
+    const int grid = std::min((a.rows + kCgWaves - 1) / kCgWaves, kCgMaxBlocks);
+    switch (elems) {
+        case 1: launch_cg<1, K>(a, grid, stream); break;
+        case 2: launch_cg<2, K>(a, grid, stream); break;
+        case 3: launch_cg<3, K>(a, grid, stream); break;
+        default: launch_cg<4, K>(a, grid, stream); break;
+    }
 }
 
 }  // namespace
@@ -333,14 +388,14 @@ void ials_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, i
                        c.g0.ptr, c.g0_dense.ptr, F, S);
     CU2REC_HIP(hipGetLastError());
     CgArgs a{side.indptr, side.indices, side.data, p, c.g0_dense.ptr, S, std::min(side.rows, max_rows), cg_steps, c.unsolved.ptr};
-    if (a.rows <= 0) return;
-    const int grid = std::min((a.rows + kCgWaves - 1) / kCgWaves, kCgMaxBlocks);
-    switch ((F + 63) / 64) {
-        case 1: launch_cg<1>(a, grid, stream); break;
-        case 2: launch_cg<2>(a, grid, stream); break;
-        case 3: launch_cg<3>(a, grid, stream); break;
-        default: launch_cg<4>(a, grid, stream); break;
-    }
+    launch_cg_rows<AlsKind::Implicit>(a, (F + 63) / 64, stream);
+}
+
+void als_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, int max_rows, int cg_steps, hipStream_t stream) {
+    const int F = p.n_factors;
+    if (F < 1 || F > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als_cg: n_factors above 252 is not supported");
+    CgArgs a{side.indptr, side.indices, side.data, p, nullptr, 0, std::min(side.rows, max_rows), cg_steps, c.unsolved.ptr};
+    launch_cg_rows<AlsKind::Explicit>(a, (F + 1 + 63) / 64, stream);  // order f + 1 <= 253: E <= 4
 }
 
 }  // namespace cu2rec

@@ -510,14 +510,18 @@ AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream) {
 }  // namespace
 
 // Argument checks first: nothing on the device or in the model is touched by a call that fails them.
-int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream) {
-    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, "cu2rec_model_als: side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream, int cg_steps) {
+    const char *fn = cg_steps > 0 ? "cu2rec_model_als_cg" : "cu2rec_model_als";
+    auto need = [fn](bool ok, int code, const char *what) {  // the message is put together only when a check fails
+        if (!ok) fail(code, std::string(fn) + what);
+    };
+    need(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
     const bool users = side == CU2REC_SIDE_USERS;
     const float reg = users ? h.P_reg : h.Q_reg, reg_bias = users ? h.user_bias_reg : h.item_bias_reg;
-    require(std::isfinite(reg) && reg > 0.f, "cu2rec_model_als: the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
-    require(std::isfinite(reg_bias) && reg_bias >= 0.f, "cu2rec_model_als: the bias regulariser must be finite and >= 0");
-    require(train.rows <= rows && train.max_item < cols, "cu2rec_model_als: ratings exceed the model's shape");
-    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als: n_factors above 252 is not supported");
+    need(std::isfinite(reg) && reg > 0.f, CU2REC_EINVAL, ": the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
+    need(std::isfinite(reg_bias) && reg_bias >= 0.f, CU2REC_EINVAL, ": the bias regulariser must be finite and >= 0");
+    need(train.rows <= rows && train.max_item < cols, CU2REC_EINVAL, ": ratings exceed the model's shape");
+    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
     require_device();
     check_faults();
     finish_swap();
@@ -525,7 +529,7 @@ int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hi
     AlsCache &c = *train.als;
     const AlsProblem p = users ? AlsProblem{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, global_bias, reg, reg_bias}
                                : AlsProblem{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, global_bias, reg, reg_bias};
-    const int unsolved = als_half_step(c, rows_of_side, p, users ? rows : cols, stream);
+    const int unsolved = als_half_step(c, rows_of_side, p, users ? rows : cols, stream, cg_steps);
     other_in_sync = false;  // Q moved on without the ping-pong pair
     return unsolved;
 }
@@ -862,6 +866,15 @@ int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hype
     return guarded([&] {
         require(m && train && hyper, "cu2rec_model_als: null argument");
         const int n = m->impl.als(train->impl, *hyper, side, nullptr);
+        if (unsolved) *unsolved = n;
+    });
+}
+
+int cu2rec_model_als_cg(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int cg_steps, int *unsolved) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_als_cg: null argument");
+        require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_model_als_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
+        const int n = m->impl.als(train->impl, *hyper, side, nullptr, cg_steps);
         if (unsolved) *unsolved = n;
     });
 }

@@ -86,7 +86,9 @@ struct DeviceModel {
              int update_items, hipStream_t stream, bool defer_last_swap = false, int user_offset = 0);
     void finish_swap();
     // one exact ALS half-step (side: CU2REC_SIDE_USERS / CU2REC_SIDE_ITEMS); returns the rows a failed pivot left unchanged
-    int als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream);
+    // cg_steps > 0: rows of at most CU2REC_ALS_CHUNK ratings take that many conjugate-gradient steps from their current factors
+    // and bias (cu2rec_model_als_cg)
+    int als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream, int cg_steps = 0);
     // one implicit-feedback half-step (confidence weight alpha * r per entry, every user x item pair counted); same return
     // cg_steps > 0: rows of at most CU2REC_ALS_CHUNK entries take that many conjugate-gradient steps from their current factors
     // (cu2rec_model_als_implicit_cg)

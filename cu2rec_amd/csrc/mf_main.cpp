@@ -2,13 +2,15 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|ials] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
 //          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
 // for bit).  `-m hogwild` opts into sgd.cu's own racy semantics (fastest, 1e-3 away from the sequential result while
 // the model is still moving).  `-m als` trains by alternating least squares instead of SGD: total_iterations sweeps (user
 // half-step, item half-step) with the config's regularisers, no learning rate; single GPU, n_factors up to 252.
+// `-m alscg` is `-m als` by conjugate gradients: rows of at most 1,024 ratings take -C steps (default 3) per half-step instead of
+// the exact solve (cu2rec_train_als_cg).
 // `-m ials` is its implicit-feedback form (-a alpha: the confidence weight per unit of r); with -C steps its rows of at most 1,024
 // entries take that many conjugate-gradient steps per sweep instead of the exact solve (cu2rec_train_implicit_cg).
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
@@ -271,7 +273,7 @@ int run_multi_gpu(int nranks, int mode, int sync_every, int merge, const std::st
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|ials] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
                         "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
@@ -285,7 +287,8 @@ int main(int argc, char **argv) {
     float rank_threshold = -INFINITY;
     bool implicit = false;  // -m ials: implicit-feedback ALS (cu2rec_train_implicit), not a cu2rec_sgd_mode
     float alpha = 40.f;     // -a: its confidence weight per unit of r
-    bool cg_given = false;  // -C steps: -m ials by conjugate gradients (cu2rec_train_implicit_cg)
+    bool als_cg = false;    // -m alscg: explicit ALS by conjugate gradients (cu2rec_train_als_cg), -C steps or 3
+    bool cg_given = false;  // -C steps: -m ials by conjugate gradients (cu2rec_train_implicit_cg), or -m alscg's step count
     long cg_steps = 0;
     int opt;
     while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:")) != -1) {
@@ -331,7 +334,8 @@ int main(int argc, char **argv) {
             case 'm':
                 g_mode_given = true;
                 implicit = std::strcmp(optarg, "ials") == 0;
-                mode = implicit ? CU2REC_ALS
+                als_cg = std::strcmp(optarg, "alscg") == 0;
+                mode = implicit || als_cg ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0    ? CU2REC_SGD_SERIAL
                        : std::strcmp(optarg, "ordered") == 0 ? CU2REC_SGD_ORDERED
                        : std::strcmp(optarg, "pingpong") == 0 ? CU2REC_SGD_PINGPONG
@@ -360,17 +364,18 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -k is single-GPU only (not with -g)\n";
         return 1;
     }
-    if (cg_given && (!implicit || cg_steps < 1 || cg_steps > CU2REC_ALS_CG_MAX_STEPS)) {  // before the GPU is touched
-        std::cerr << "mf: -C needs -m ials and a step count between 1 and " << CU2REC_ALS_CG_MAX_STEPS << "\n" << usage;
+    if (cg_given && (!(implicit || als_cg) || cg_steps < 1 || cg_steps > CU2REC_ALS_CG_MAX_STEPS)) {  // before the GPU is touched
+        std::cerr << "mf: -C needs -m ials or -m alscg and a step count between 1 and " << CU2REC_ALS_CG_MAX_STEPS << "\n" << usage;
         return 1;
     }
+    if (als_cg && !cg_given) cg_steps = 3;
     if (implicit && !(std::isfinite(alpha) && alpha >= 0.f)) {
         std::cerr << "mf: -a must be a finite number >= 0\n";
         return 1;
     }
     if (gpus > 1) {
         if (mode == CU2REC_ALS) {
-            std::cerr << "mf: -m " << (implicit ? "ials" : "als") << " is single-GPU only (not with -g)\n";
+            std::cerr << "mf: -m " << (implicit ? "ials" : als_cg ? "alscg" : "als") << " is single-GPU only (not with -g)\n";
             return 1;
         }
         if (mode == CU2REC_SGD_PINGPONG) {
@@ -404,6 +409,8 @@ int main(int argc, char **argv) {
             cu2rec::check(cu2rec_train_implicit_cg(d_train.h, &cfg, model.h, alpha, static_cast<int>(cg_steps), 1, nullptr, nullptr));
         else if (implicit)  // the test file is read (and checked) as always, but only -k looks at it
             cu2rec::check(cu2rec_train_implicit(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
+        else if (als_cg)
+            cu2rec::check(cu2rec_train_als_cg(d_train.h, d_test.h, &cfg, model.h, static_cast<int>(cg_steps), 1, losses.data(), nullptr));
         else
             cu2rec::check(cu2rec_train(d_train.h, d_test.h, &cfg, model.h, mode, 1, losses.data(), nullptr));  // mf.cu:61
 

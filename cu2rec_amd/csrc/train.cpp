@@ -4,31 +4,37 @@
 // stream and timed by HIP events.  No ping-pong buffers, no per-iteration memset, no RNG state:
 // item rows are updated in place (mf_sequential.cu semantics, the parity target) -- except in
 // CU2REC_SGD_PINGPONG, which keeps the reference GPU loop's two item buffers and its loss-before-swap order.
-// CU2REC_ALS runs the same schedule with exact half-steps (als.hip) in place of the SGD iterations.
+// CU2REC_ALS runs the same schedule with exact half-steps (als.hip) in place of the SGD iterations; cg_steps > 0
+// (cu2rec_train_als_cg): with conjugate-gradient half-steps (als_cg.hip).
 #include "train_schedule.hpp"
 
 namespace cu2rec {
 
 void train(const DeviceCsr &train_csr, const DeviceCsr &test_csr, cu2rec_config &cfg, DeviceModel &model, int mode,
-           bool verbose, float *losses, cu2rec_train_stats *stats) {
-    require(cfg.n_factors == model.n_factors, "cu2rec_train: cfg.n_factors differs from the model's");
-    require(train_csr.rows <= model.rows && train_csr.max_item < model.cols, "cu2rec_train: train ratings exceed the model");
+           bool verbose, float *losses, cu2rec_train_stats *stats, int cg_steps = 0) {
+    const bool cg = cg_steps > 0;  // reached through cu2rec_train_als_cg: the same checks under that name
+    require(cfg.n_factors == model.n_factors, cg ? "cu2rec_train_als_cg: cfg.n_factors differs from the model's"
+                                                 : "cu2rec_train: cfg.n_factors differs from the model's");
+    require(train_csr.rows <= model.rows && train_csr.max_item < model.cols,
+            cg ? "cu2rec_train_als_cg: train ratings exceed the model" : "cu2rec_train: train ratings exceed the model");
     require(test_csr.rows <= model.rows && test_csr.max_item < model.cols,
-            "cu2rec_train: test ratings name users/items the model does not have");
+            cg ? "cu2rec_train_als_cg: test ratings name users/items the model does not have"
+               : "cu2rec_train: test ratings name users/items the model does not have");
     hipStream_t stream = nullptr;  // the reference runs everything on the default stream
     if (mode == CU2REC_ALS) {
         // one "iteration" is one sweep: the user half-step, then the item half-step unless the items are frozen.  The same loss
         // cadence and lines; no learning rate, so no patience / decay; stats->updates = rows solved
-        if (cfg.n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_train: CU2REC_ALS supports n_factors up to 252");
+        if (cfg.n_factors > kAlsMaxFactors)
+            fail(CU2REC_EUNSUPPORTED, cg ? "cu2rec_train_als_cg: n_factors up to 252 are supported" : "cu2rec_train: CU2REC_ALS supports n_factors up to 252");
         double solved = 0.0;
         train_schedule(
             cfg, verbose, true, 0.0, losses, stats, stream,
             [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
                 for (int k = 0; k < n; ++k) {
-                    const int u = model.als(train_csr, h, CU2REC_SIDE_USERS, s);
+                    const int u = model.als(train_csr, h, CU2REC_SIDE_USERS, s, cg_steps);
                     solved += train_csr.als->users.rows_with_ratings - u;
                     if (cfg.is_train) {
-                        const int i = model.als(train_csr, h, CU2REC_SIDE_ITEMS, s);
+                        const int i = model.als(train_csr, h, CU2REC_SIDE_ITEMS, s, cg_steps);
                         solved += train_csr.als->items.rows_with_ratings - i;
                     }
                 }
@@ -114,6 +120,16 @@ extern "C" int cu2rec_train_implicit_cg(const cu2rec_csr *train, cu2rec_config *
         require(train && cfg && model, "cu2rec_train_implicit_cg: null argument");
         require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_train_implicit_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
         cu2rec::train_implicit(unwrap(train), *cfg, unwrap(model), alpha, cg_steps, verbose != 0, objectives, stats);
+    });
+}
+
+extern "C" int cu2rec_train_als_cg(const cu2rec_csr *train, const cu2rec_csr *test, cu2rec_config *cfg, cu2rec_model *model, int cg_steps,
+                                   int verbose, float *losses, cu2rec_train_stats *stats) {
+    using namespace cu2rec;
+    return guarded([&] {
+        require(train && test && cfg && model, "cu2rec_train_als_cg: null argument");
+        require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_train_als_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
+        cu2rec::train(unwrap(train), unwrap(test), *cfg, unwrap(model), CU2REC_ALS, verbose != 0, losses, stats, cg_steps);
     });
 }
 

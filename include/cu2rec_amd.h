@@ -476,6 +476,26 @@ int cu2rec_model_rank_metrics(const cu2rec_model *m, const cu2rec_csr *exclude, 
 enum { CU2REC_ALS_MAX_FACTORS = 252, CU2REC_ALS_STEP = 32, CU2REC_ALS_CHUNK = 1024, CU2REC_ALS_MAX_CHUNKS = 64,
        CU2REC_ALS_WORKSPACE_BYTES = 64 << 20 };
 int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *unsolved);
+/* The same half-step by conjugate gradients: an approximate solver, warm-started from the row's current values, that never forms
+ * the row's Gram.  In the notation above (x = [factors; bias], z_i = [partner factors; 1], t_i = (r_i - gb) - partner bias, n the
+ * row's ratings, D = n_factors + 1) the system is applied as an operator,
+ *   A v = sum_i z_i (z_i . v) + n diag(reg, ..., reg, reg_bias) v,   b = sum_i t_i z_i,
+ * and a row is treated by its length:
+ *   0 ratings: the row keeps its values and is not counted -- as above.
+ *   more than CU2REC_ALS_CHUNK ratings: solved exactly by the kernels of cu2rec_model_als, bit for bit what that call writes.  Long
+ *     rows are solved exactly whatever cg_steps is.
+ *   1 .. CU2REC_ALS_CHUNK ratings: x0 = [the row's n_factors factors; its bias] (the padding floats are never read as data; if any
+ *     of the D values is not finite, x0 = 0); r = b - A x0, p = r, rho = r . r; then cg_steps times: if rho == 0 stop and keep x;
+ *     d = p . A p; if d == 0 stop and keep x; a = rho / d; x += a p; r -= a A p; rho' = r . r; p = r + (rho' / rho) p; rho = rho'
+ *     -- the iteration of cu2rec_model_als_implicit_cg below.  Factors and bias are both written, the padding floats as 0.
+ * A row is left with the bits it had and counted in *unsolved when a rho or a d is not finite, a d is negative or the final x is
+ * not finite (e.g. a NaN rating, a partner row that overflows).
+ * Determinism as above: every sum's order is a function of the row's own length and n_factors, there are no float atomics,
+ * results are bit-identical run to run, and a row solved from a one-row CSR equals that row solved among all the others.  One
+ * wavefront per row; there is no global Gram, so nothing is staged and no workspace is used by these rows.
+ * cg_steps must lie in [1, CU2REC_ALS_CG_MAX_STEPS] (256, below), else CU2REC_EINVAL, checked -- like everything cu2rec_model_als
+ * checks, with the same codes -- before the device or the model is touched. */
+int cu2rec_model_als_cg(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int cg_steps, int *unsolved);
 
 /* ------------------------------------------------------------------------------------------
  * Implicit feedback: confidence-weighted alternating least squares (Hu, Koren, Volinsky: Collaborative Filtering for Implicit
@@ -556,6 +576,11 @@ typedef struct cu2rec_train_stats {
 
 int cu2rec_train(const cu2rec_csr *train, const cu2rec_csr *test, cu2rec_config *cfg, cu2rec_model *model,
                  int mode, int verbose, float *losses, cu2rec_train_stats *stats);
+/* cu2rec_train's CU2REC_ALS loop, lines, cadence, losses and stats with sweeps of cu2rec_model_als_cg at cg_steps steps.  The same
+ * argument checks with the same codes as cu2rec_train, and cg_steps outside [1, CU2REC_ALS_CG_MAX_STEPS]: CU2REC_EINVAL, all before
+ * the device or the model is touched. */
+int cu2rec_train_als_cg(const cu2rec_csr *train, const cu2rec_csr *test, cu2rec_config *cfg, cu2rec_model *model, int cg_steps,
+                        int verbose, float *losses, cu2rec_train_stats *stats);
 /* Implicit-feedback training: total_iterations sweeps of cu2rec_model_als_implicit -- the users, then the items when cfg->is_train
  * -- with the objective evaluated at the loss cadence above, printed as "TRAIN: Iteration %d GPU implicit objective: %f" when
  * `verbose`, and stored in objectives[i] (host, total_iterations doubles, may be NULL; NaN elsewhere).  There is no test set and no

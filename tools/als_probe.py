@@ -1,7 +1,7 @@
 """Times the alternating-least-squares half-steps (cu2rec_model_als) on the synthetic ML-20M and Netflix shapes and prints each time
 next to its Gram roofline.
 
-    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3] [--implicit [--alpha 40] [--cg-steps N]]
+    python tools/als_probe.py [--shapes ml-20m,netflix] [--factors 100] [--reps 3] [--cg-steps N] [--implicit [--alpha 40]]
 
 For every shape: the item half-step's first call on a fresh cu2rec_csr (it builds the item-major view), the item half-step again
 (view cached), the user half-step, and a whole sweep (users then items).  Times are wall clock around the synchronous call (the
@@ -17,7 +17,12 @@ same per-entry work, solves EVERY row (rows without entries are written as zeros
 --cg-steps N (with --implicit): after the implicit rows, the same half-steps and sweep by N conjugate-gradient steps per row
 (cu2rec_model_als_implicit_cg) on a model of their own, each with its ratio to the implicit Cholesky time above it.  Per row of n
 entries CG does (N + 1) x (f^2 + 2 n f) multiply-adds -- one operator application for the starting residual, one per step --
-against n f^2 / 2 for the Gram's lower triangle plus f^3 / 3 for Cholesky."""
+against n f^2 / 2 for the Gram's lower triangle plus f^3 / 3 for Cholesky.
+
+--cg-steps N without --implicit: after the explicit rows, the explicit half-steps and sweep by N conjugate-gradient steps per row
+(cu2rec_model_als_cg) on a model of their own, each with its ratio to the explicit Cholesky time above it, and the rows of each side
+that CG takes (1 .. 1,024 ratings) against those solved exactly.  Per row of n ratings explicit CG does (N + 1) x 2 n (f + 1)
+multiply-adds against n F^2 / 2 + (f + 1)^3 / 3, F = f + 2 rounded up to 32 (the Gram's MFMA tiles)."""
 import argparse
 import os
 import sys
@@ -79,6 +84,27 @@ def main():
             print("  %-38s %9.2f ms   (lower-triangle Gram roofline %.2f ms: %.1fx)" % (label, 1e3 * t, roof, 1e3 * t / roof),
                   flush=True)
         m.close()
+        if args.cg_steps > 0 and not args.implicit:
+            exact = [t for _, t in rows[1:]]  # items, users, sweep
+            kw = dict(solver="cg", cg_steps=args.cg_steps)
+            m = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
+            assert m.als(d, HYPER, "both", **kw) == 0  # warm: the kernels' first launches
+            rows = [("CG-%d items" % args.cg_steps, best(lambda: m.als(d, HYPER, "items", **kw), args.reps)),
+                    ("CG-%d users" % args.cg_steps, best(lambda: m.als(d, HYPER, "users", **kw), args.reps)),
+                    ("CG-%d sweep (users + items)" % args.cg_steps, best(lambda: m.als(d, HYPER, "both", **kw), args.reps))]
+            for (label, t), t_exact in zip(rows, exact):
+                print("  %-38s %9.2f ms   (%.2f x the Cholesky time)" % (label, 1e3 * t, t / t_exact), flush=True)
+            n_users, n_items = np.diff(tr.indptr), np.bincount(tr.indices, minlength=tr.cols)
+            for side, n in (("users", n_users), ("items", n_items)):
+                short = n[(n > 0) & (n <= cu.api.ALS_CHUNK)].astype(np.float64)
+                long_n = n[n > cu.api.ALS_CHUNK].astype(np.float64)
+                cg = (args.cg_steps + 1) * 2.0 * short.sum() * (f + 1)
+                F = -(-(f + 2) // 32) * 32  # the Gram's staged columns: f + 2 rounded up to whole 32-column MFMA tiles
+                chol = short.sum() * F ** 2 / 2.0 + len(short) * (f + 1) ** 3 / 3.0
+                print("  rows of 1 .. %d ratings, %s: %d with %d ratings (%d longer ones with %d ratings solved exactly); CG %.2e "
+                      "multiply-adds, Gram + Cholesky %.2e" % (cu.api.ALS_CHUNK, side, len(short), int(short.sum()), len(long_n),
+                                                               int(long_n.sum()), cg, chol), flush=True)
+            m.close()
         if args.implicit:
             explicit_sweep = rows[-1][1]
             m = cu.Model(tr.rows, tr.cols, f, tr.global_bias)
