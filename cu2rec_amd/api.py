@@ -337,6 +337,54 @@ class Model:
         check(lib().cu2rec_model_implicit_objective(self._h, train._h, C.byref(h), float(alpha), C.byref(L)))
         return L.value
 
+    def lmf(self, train, hyper, alpha=1.0, side="both", sweeps=1):
+        """Logistic matrix factorization half-steps (cu2rec_model_lmf; Johnson 2014, full batch): the gradient of the log-posterior
+        over every user x item pair of train's shape, a stored entry (u, i, r) with weight alpha * r, then an AdaGrad step at
+        hyper's learning rate.  The score includes both biases and the global bias; all four regularisers are read.  side and
+        sweeps as in als().  alpha defaults to 1.0, not ials()'s 40: here the weight multiplies a log-odds gradient, and 40 x a
+        5-star rating saturates it.  The AdaGrad accumulators stay with the model (lmf_state, lmf_reset).
+        Returns the number of rows left unchanged (a non-finite gradient or step), summed over the half-steps."""
+        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        if side not in ALS_SIDES:
+            raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        total = 0
+        for _ in range(int(sweeps)):
+            for s in ALS_SIDES[side]:
+                n = C.c_int()
+                check(lib().cu2rec_model_lmf(self._h, train._h, C.byref(h), float(alpha), s, C.byref(n)))
+                total += n.value
+        return total
+
+    def lmf_gradient(self, train, hyper, alpha, side):
+        """The gradient lmf() would step along for side "users" or "items" (cu2rec_model_lmf_gradient) -> (grad, bias_grad),
+        float32 of shapes (n, n_factors) and (n,), n = train's rows or cols.  The model and the accumulators are untouched."""
+        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        if side not in ("users", "items"):
+            raise ValueError("side must be 'users' or 'items', not %r" % (side,))
+        n = train.rows if side == "users" else train.cols
+        grad, bias = np.empty((n, self.n_factors), np.float32), np.empty(n, np.float32)
+        check(lib().cu2rec_model_lmf_gradient(self._h, train._h, C.byref(h), float(alpha), ALS_SIDES[side][0], _ptr(grad), _ptr(bias)))
+        return grad, bias
+
+    def lmf_objective(self, train, hyper, alpha):
+        """The log-posterior lmf() climbs, at the model's current values (cu2rec_model_lmf_objective) -> float."""
+        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        L = C.c_double()
+        check(lib().cu2rec_model_lmf_objective(self._h, train._h, C.byref(h), float(alpha), C.byref(L)))
+        return L.value
+
+    def lmf_state(self):
+        """The AdaGrad accumulators of lmf() -> aP, aQ, a_user_bias, a_item_bias, shaped like download(); zeros before the first call."""
+        aP = np.empty((self.rows, self.n_factors), np.float32)
+        aQ = np.empty((self.cols, self.n_factors), np.float32)
+        aub, aib = np.empty(self.rows, np.float32), np.empty(self.cols, np.float32)
+        check(lib().cu2rec_model_lmf_state(self._h, _ptr(aP), _ptr(aQ), _ptr(aub), _ptr(aib)))
+        return aP, aQ, aub, aib
+
+    def lmf_reset(self):
+        """Zeroes the AdaGrad accumulators of lmf()."""
+        check(lib().cu2rec_model_lmf_reset(self._h))
+
     def loss(self, ratings):
         """calculate_loss_gpu + get_error_metrics_gpu (loss.cu:40-49,195-200) -> dict(mae, rmse, sum_abs, sum_sq)."""
         sa, ss, mae, rmse = C.c_double(), C.c_double(), C.c_float(), C.c_float()
@@ -447,24 +495,32 @@ def default_mode(n_factors):
 
 
 def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=None, mode=None, verbose=True,
-          P=None, user_bias=None, return_stats=False, alpha=40.0, solver="cholesky", cg_steps=3):
+          P=None, user_bias=None, return_stats=False, alpha=None, solver="cholesky", cg_steps=3):
     """train() (training.h:12-15).  mode None = default_mode(cfg.n_factors); "hogwild" opts into sgd.cu's racy semantics; "als"
     trains by alternating least squares (one iteration = one sweep; no learning rate, so no decay); "ials" by its implicit-feedback
     form with confidence weight alpha * r (cu2rec_train_implicit: test_matrix is not read and may be None, and the third element
     returned is the objective at the checked sweeps, float64, NaN elsewhere; solver="cg" runs the sweeps with cg_steps conjugate-gradient
     steps per row, cu2rec_train_implicit_cg; with mode "als" it is cu2rec_train_als_cg -- solver and cg_steps are read in these two modes
-    only).  train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
+    only); "lmf" by logistic matrix factorization (cu2rec_train_lmf: like "ials", test_matrix may be None and the third element is the
+    log-posterior at the checked sweeps; cfg.learning_rate is AdaGrad's and does not decay).  alpha None is 40.0 for "ials" and 1.0 for
+    "lmf", where the weight multiplies a log-odds gradient and 40 x a 5-star rating saturates it.
+    train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
     otherwise everything starts from the seed-42 normal init.  Returns (P, Q, losses, user_bias,
     item_bias) like the reference's out-pointers; cfg.learning_rate / cfg.cur_iterations are
     updated in place."""
     if mode in ("als", "ials"):
         _solver(solver)
+    if alpha is None:
+        alpha = 1.0 if mode == "lmf" else 40.0
     tr = train_matrix if isinstance(train_matrix, DeviceCSR) else DeviceCSR(train_matrix)
     gb = tr.host.global_bias if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
     stats = TrainStats()
-    if mode == "ials":
+    if mode == "lmf":
+        losses = np.empty(max(cfg.total_iterations, 1), np.float64)
+        check(lib().cu2rec_train_lmf(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses), C.byref(stats)))
+    elif mode == "ials":
         losses = np.empty(max(cfg.total_iterations, 1), np.float64)
         if solver == "cg":
             check(lib().cu2rec_train_implicit_cg(tr._h, C.byref(cfg), model._h, float(alpha), int(cg_steps), 1 if verbose else 0,

@@ -572,6 +572,110 @@ double DeviceModel::implicit_objective(const DeviceCsr &train, const cu2rec_hype
     return ials_objective(*train.als, o, stream);
 }
 
+// Logistic matrix factorization (include/cu2rec_amd.h: cu2rec_model_lmf).  The checks of ials(), in its order, before the device.
+void DeviceModel::lmf_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, const int *side) const {
+    auto need = [fn](bool ok, int code, const char *what) {
+        if (!ok) fail(code, std::string(fn) + what);
+    };
+    need(!side || *side == CU2REC_SIDE_USERS || *side == CU2REC_SIDE_ITEMS, CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    for (float reg : {h.P_reg, h.Q_reg, h.user_bias_reg, h.item_bias_reg})
+        need(std::isfinite(reg) && reg >= 0.f, CU2REC_EINVAL, ": every regulariser must be finite and >= 0");
+    need(std::isfinite(alpha) && alpha >= 0.f, CU2REC_EINVAL, ": alpha must be finite and >= 0");
+    need(std::isfinite(h.learning_rate) && h.learning_rate > 0.f, CU2REC_EINVAL, ": learning_rate must be finite and > 0");
+    need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": entries exceed the model's shape");
+    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
+}
+
+namespace {
+// the half-step's view of one side; the item side reads the item-major view cached on the CSR by the ALS calls
+LmfProblem lmf_problem(DeviceModel &m, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, bool users, hipStream_t stream) {
+    const AlsSide &s = als_side(train, users, stream);
+    if (users)
+        return {s.indptr, s.indices, s.data, m.P.ptr, m.ld, m.user_bias.ptr, train.rows, m.Q.ptr, m.ldq, m.item_bias.ptr, train.cols,
+                m.n_factors, m.global_bias, alpha, h.P_reg, h.user_bias_reg, h.learning_rate};
+    return {s.indptr, s.indices, s.data, m.Q.ptr, m.ldq, m.item_bias.ptr, train.cols, m.P.ptr, m.ld, m.user_bias.ptr, train.rows,
+            m.n_factors, m.global_bias, alpha, h.Q_reg, h.item_bias_reg, h.learning_rate};
+}
+
+void lmf_ensure_state(DeviceModel &m) {  // allocated zeroed by the first logistic call
+    if (m.lmf_st.aP.ptr) return;
+    m.lmf_st.aP.allocate(std::max<size_t>(m.P.count, 1));
+    m.lmf_st.aQ.allocate(std::max<size_t>(m.Q.count, 1));
+    m.lmf_st.a_ub.allocate(m.user_bias.count);
+    m.lmf_st.a_ib.allocate(m.item_bias.count);
+    m.lmf_reset();
+}
+}  // namespace
+
+int DeviceModel::lmf(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream) {
+    lmf_check("cu2rec_model_lmf", train, h, alpha, &side);
+    require_device();
+    check_faults();
+    finish_swap();
+    lmf_ensure_state(*this);
+    const bool users = side == CU2REC_SIDE_USERS;
+    const LmfProblem p = lmf_problem(*this, train, h, alpha, users, stream);
+    cu2rec::lmf_gradient(lmf_st, p, stream);
+    const int unchanged = lmf_step(lmf_st, p, users ? lmf_st.aP.ptr : lmf_st.aQ.ptr, users ? lmf_st.a_ub.ptr : lmf_st.a_ib.ptr, stream);
+    other_in_sync = false;  // Q may have moved on without the ping-pong pair
+    return unchanged;
+}
+
+void DeviceModel::lmf_gradient(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, float *grad_out, float *bias_grad_out,
+                               hipStream_t stream) {
+    lmf_check("cu2rec_model_lmf_gradient", train, h, alpha, &side);
+    require_device();
+    check_faults();
+    finish_swap();
+    const LmfProblem p = lmf_problem(*this, train, h, alpha, side == CU2REC_SIDE_USERS, stream);
+    if (p.n_own == 0) return;
+    cu2rec::lmf_gradient(lmf_st, p, stream);
+    const size_t ldg = static_cast<size_t>(32) * lmf_tiles(n_factors) * sizeof(float);
+    CU2REC_HIP(hipStreamSynchronize(stream));
+    if (grad_out)
+        CU2REC_HIP(hipMemcpy2D(grad_out, static_cast<size_t>(n_factors) * sizeof(float), lmf_st.grad.ptr, ldg,
+                               static_cast<size_t>(n_factors) * sizeof(float), p.n_own, hipMemcpyDeviceToHost));
+    if (bias_grad_out)
+        CU2REC_HIP(hipMemcpy2D(bias_grad_out, sizeof(float), lmf_st.grad.ptr + n_factors, ldg, sizeof(float), p.n_own, hipMemcpyDeviceToHost));
+}
+
+double DeviceModel::lmf_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream) {
+    lmf_check("cu2rec_model_lmf_objective", train, h, alpha, nullptr);
+    require_device();
+    check_faults();
+    finish_swap();
+    const LmfProblem p = lmf_problem(*this, train, h, alpha, true, stream);
+    const double dense = lmf_dense_objective(lmf_st, p, stream);
+    double s[5];
+    lmf_sparse_objective(lmf_st, p, train.nnz, s, stream);
+    return (s[0] - dense) - 0.5 * (static_cast<double>(h.P_reg) * s[1] + static_cast<double>(h.user_bias_reg) * s[2] +
+                                   static_cast<double>(h.Q_reg) * s[3] + static_cast<double>(h.item_bias_reg) * s[4]);
+}
+
+void DeviceModel::lmf_download_state(float *aP, float *aQ, float *a_ub, float *a_ib) {
+    if (!lmf_st.aP.ptr) {
+        if (aP) std::fill(aP, aP + static_cast<size_t>(rows) * n_factors, 0.f);
+        if (aQ) std::fill(aQ, aQ + static_cast<size_t>(cols) * n_factors, 0.f);
+        if (a_ub) std::fill(a_ub, a_ub + rows, 0.f);
+        if (a_ib) std::fill(a_ib, a_ib + cols, 0.f);
+        return;
+    }
+    CU2REC_HIP(hipDeviceSynchronize());
+    if (aP) download_padded(lmf_st.aP, aP, rows, n_factors, ld);
+    if (aQ) download_padded(lmf_st.aQ, aQ, cols, n_factors, ldq);
+    if (a_ub && rows) lmf_st.a_ub.download(a_ub, rows);
+    if (a_ib && cols) lmf_st.a_ib.download(a_ib, cols);
+}
+
+void DeviceModel::lmf_reset() {
+    if (!lmf_st.aP.ptr) return;
+    CU2REC_HIP(hipDeviceSynchronize());
+    lmf_st.aP.zero();
+    lmf_st.aQ.zero();
+    lmf_st.a_ub.zero();
+    lmf_st.a_ib.zero();
+}
+
 void DeviceModel::loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
                        hipStream_t stream) const {
     // Appendix quirk 6: a test file may have fewer users than train, never more
@@ -902,6 +1006,43 @@ int cu2rec_model_implicit_objective(cu2rec_model *m, const cu2rec_csr *train, co
     return guarded([&] {
         require(m && train && hyper && L, "cu2rec_model_implicit_objective: null argument");
         *L = m->impl.implicit_objective(train->impl, *hyper, alpha, nullptr);
+    });
+}
+
+int cu2rec_model_lmf(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side, int *n_unchanged) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_lmf: null argument");
+        const int n = m->impl.lmf(train->impl, *hyper, alpha, side, nullptr);
+        if (n_unchanged) *n_unchanged = n;
+    });
+}
+
+int cu2rec_model_lmf_gradient(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
+                              float *grad_out, float *bias_grad_out) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_lmf_gradient: null argument");
+        m->impl.lmf_gradient(train->impl, *hyper, alpha, side, grad_out, bias_grad_out, nullptr);
+    });
+}
+
+int cu2rec_model_lmf_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, double *L) {
+    return guarded([&] {
+        require(m && train && hyper && L, "cu2rec_model_lmf_objective: null argument");
+        *L = m->impl.lmf_objective(train->impl, *hyper, alpha, nullptr);
+    });
+}
+
+int cu2rec_model_lmf_state(cu2rec_model *m, float *aP, float *aQ, float *a_ub, float *a_ib) {
+    return guarded([&] {
+        require(m, "cu2rec_model_lmf_state: model is null");
+        m->impl.lmf_download_state(aP, aQ, a_ub, a_ib);
+    });
+}
+
+int cu2rec_model_lmf_reset(cu2rec_model *m) {
+    return guarded([&] {
+        require(m, "cu2rec_model_lmf_reset: model is null");
+        m->impl.lmf_reset();
     });
 }
 

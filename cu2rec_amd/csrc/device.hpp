@@ -9,6 +9,7 @@
 
 #include "als.hpp"
 #include "hip_check.hpp"
+#include "lmf.hpp"
 #include "ordered.hpp"
 
 struct cu2rec_csr;
@@ -95,6 +96,17 @@ struct DeviceModel {
     int ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream, int cg_steps = 0);
     // the implicit objective at the current model (synchronises)
     double implicit_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream);
+    // one logistic-MF half-step (lmf.hpp: gradient over every pair, then AdaGrad); returns the rows left unchanged
+    int lmf(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream);
+    // the same gradient to the host ([n][n_factors] and [n], n = the side's rows inside the CSR); the model and accumulators untouched
+    void lmf_gradient(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, float *grad_out, float *bias_grad_out,
+                      hipStream_t stream);
+    // the logistic log-posterior at the current model (synchronises)
+    double lmf_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream);
+    void lmf_download_state(float *aP, float *aQ, float *a_ub, float *a_ib);  // zeros before the first logistic call
+    void lmf_reset();
+    // the argument checks of the logistic calls (side may be null), before the device or the model is touched; fn names the caller
+    void lmf_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, const int *side) const;
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
               hipStream_t stream) const;
     FactorsRef ref() const { return {P.ptr, ld, Q.ptr, ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors}; }
@@ -104,6 +116,7 @@ struct DeviceModel {
     bool other_in_sync = false;   // Q_other / item_bias_other were last written by the ping-pong mode itself
     bool swap_pending = false;
     mutable DeviceBuffer<double> workspace;
+    LmfState lmf_st;  // AdaGrad accumulators and workspace of the logistic trainer, created by its first call
     int rows, cols, n_factors;
     int ld;   // row stride of P in floats: n_factors rounded up to 4 (16-byte aligned rows)
     int ldq;  // row stride of Q: rounded up to 32 floats, so that every item row is a whole number of 128-byte lines --

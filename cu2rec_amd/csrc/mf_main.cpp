@@ -2,7 +2,7 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
 //          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
@@ -13,6 +13,9 @@
 // the exact solve (cu2rec_train_als_cg).
 // `-m ials` is its implicit-feedback form (-a alpha: the confidence weight per unit of r); with -C steps its rows of at most 1,024
 // entries take that many conjugate-gradient steps per sweep instead of the exact solve (cu2rec_train_implicit_cg).
+// `-m lmf` trains by logistic matrix factorization (cu2rec_train_lmf): total_iterations full-batch sweeps with AdaGrad at the config's
+// learning rate, -a alpha the weight per unit of r (default 1 here, not ials's 40); single GPU, no -C.  The AdaGrad accumulators
+// are not written out: a run started from the five files begins them at zero.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -273,7 +276,7 @@ int run_multi_gpu(int nranks, int mode, int sync_every, int merge, const std::st
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
                         "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
@@ -286,7 +289,9 @@ int main(int argc, char **argv) {
     bool rank_given = false;
     float rank_threshold = -INFINITY;
     bool implicit = false;  // -m ials: implicit-feedback ALS (cu2rec_train_implicit), not a cu2rec_sgd_mode
-    float alpha = 40.f;     // -a: its confidence weight per unit of r
+    bool logistic = false;  // -m lmf: logistic matrix factorization (cu2rec_train_lmf)
+    float alpha = 40.f;     // -a: the weight per unit of r of -m ials (default 40) and -m lmf (default 1)
+    bool alpha_given = false;
     bool als_cg = false;    // -m alscg: explicit ALS by conjugate gradients (cu2rec_train_als_cg), -C steps or 3
     bool cg_given = false;  // -C steps: -m ials by conjugate gradients (cu2rec_train_implicit_cg), or -m alscg's step count
     long cg_steps = 0;
@@ -295,6 +300,7 @@ int main(int argc, char **argv) {
         switch (opt) {
             case 'a': {
                 char *end = nullptr;
+                alpha_given = true;
                 alpha = std::strtof(optarg, &end);
                 if (end == optarg || *end != '\0') alpha = NAN;  // not a number: refused below
                 break;
@@ -335,7 +341,8 @@ int main(int argc, char **argv) {
                 g_mode_given = true;
                 implicit = std::strcmp(optarg, "ials") == 0;
                 als_cg = std::strcmp(optarg, "alscg") == 0;
-                mode = implicit || als_cg ? CU2REC_ALS
+                logistic = std::strcmp(optarg, "lmf") == 0;
+                mode = implicit || als_cg || logistic ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0    ? CU2REC_SGD_SERIAL
                        : std::strcmp(optarg, "ordered") == 0 ? CU2REC_SGD_ORDERED
                        : std::strcmp(optarg, "pingpong") == 0 ? CU2REC_SGD_PINGPONG
@@ -369,7 +376,12 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (als_cg && !cg_given) cg_steps = 3;
-    if (implicit && !(std::isfinite(alpha) && alpha >= 0.f)) {
+    if (logistic && gpus > 1) {  // before the GPU is touched
+        std::cerr << "mf: -m lmf is single-GPU only (not with -g)\n" << usage;
+        return 1;
+    }
+    if (logistic && !alpha_given) alpha = 1.f;
+    if ((implicit || logistic) && !(std::isfinite(alpha) && alpha >= 0.f)) {
         std::cerr << "mf: -a must be a finite number >= 0\n";
         return 1;
     }
@@ -405,7 +417,9 @@ int main(int argc, char **argv) {
         cu2rec::CsrHandle d_train(train), d_test(test);
         cu2rec::ModelHandle model(train.rows, train.cols, cfg.n_factors, train.global_bias);
         std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
-        if (implicit && cg_given)
+        if (logistic)
+            cu2rec::check(cu2rec_train_lmf(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
+        else if (implicit && cg_given)
             cu2rec::check(cu2rec_train_implicit_cg(d_train.h, &cfg, model.h, alpha, static_cast<int>(cg_steps), 1, nullptr, nullptr));
         else if (implicit)  // the test file is read (and checked) as always, but only -k looks at it
             cu2rec::check(cu2rec_train_implicit(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));

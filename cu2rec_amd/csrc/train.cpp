@@ -102,7 +102,54 @@ void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel 
     if (stats) *stats = st;
 }
 
+// Logistic matrix factorization (include/cu2rec_amd.h: cu2rec_train_lmf): train_implicit's loop with full-batch logistic half-steps
+// for the iterations and the log-posterior for the loss.  The learning rate is AdaGrad's and does not decay.
+void train_lmf(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &model, float alpha, bool verbose, double *objectives,
+               cu2rec_train_stats *stats) {
+    require(cfg.n_factors == model.n_factors, "cu2rec_train_lmf: cfg.n_factors differs from the model's");
+    require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_lmf: bad iteration counts");
+    cu2rec_hyper hyper{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
+    model.lmf_check("cu2rec_train_lmf", train_csr, hyper, alpha, nullptr);
+    model.lmf_reset();
+    hipStream_t stream = nullptr;
+    if (objectives)
+        for (int i = 0; i < cfg.total_iterations; ++i) objectives[i] = std::numeric_limits<double>::quiet_NaN();
+    double stepped = 0.0;
+    int done = 0;
+    cu2rec_train_stats st{};
+    train_schedule(
+        cfg, false, false, 0.0, nullptr, &st, stream,
+        [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
+            hyper = h;
+            for (int k = 0; k < n; ++k) {
+                stepped += train_csr.rows - model.lmf(train_csr, h, alpha, CU2REC_SIDE_USERS, s);
+                if (cfg.is_train) stepped += train_csr.cols - model.lmf(train_csr, h, alpha, CU2REC_SIDE_ITEMS, s);
+            }
+            done += n;
+        },
+        [&](bool on_train, float *mae, float *rmse) {
+            *mae = *rmse = 0.f;  // no residual metrics in this model
+            if (!on_train) return;
+            const double L = model.lmf_objective(train_csr, hyper, alpha, stream);
+            if (verbose) std::printf("TRAIN: Iteration %d GPU logistic objective: %f\n", done, L);
+            if (objectives) objectives[done - 1] = L;
+        },
+        [] {}, /*decay_lr=*/false);
+    if (verbose) std::printf("Time taken for %d of iterations is %lf\n", cfg.total_iterations, st.seconds_total);
+    st.updates = stepped;
+    if (stats) *stats = st;
+}
+
 }  // namespace cu2rec
+
+extern "C" int cu2rec_train_lmf(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose,
+                                double *objectives, cu2rec_train_stats *stats) {
+    using namespace cu2rec;
+    return guarded([&] {
+        require(train && cfg && model, "cu2rec_train_lmf: null argument");
+        cu2rec::train_lmf(unwrap(train), *cfg, unwrap(model), alpha, verbose != 0, objectives, stats);
+    });
+}
 
 extern "C" int cu2rec_train_implicit(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose,
                                      double *objectives, cu2rec_train_stats *stats) {

@@ -553,6 +553,47 @@ int cu2rec_model_als_implicit_cg(cu2rec_model *m, const cu2rec_csr *train, const
 int cu2rec_model_implicit_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, double *L);
 
 /* ------------------------------------------------------------------------------------------
+ * Implicit feedback: logistic matrix factorization (Johnson: Logistic Matrix Factorization for Implicit Feedback Data, 2014), in
+ * its full-batch form.  U = train rows, I = train cols; every stored entry (u, i, r) has weight w = alpha * r (repeated pairs count
+ * separately); the score is the one the ranking calls use, s_ui = global_bias + user_bias[u] + item_bias[i] + p_u . q_i, and
+ * sigma(s_ui) is the probability that u interacts with i.  The log-posterior to be MAXIMISED is
+ *   L = sum_entries w s_ui - sum_(u < U, i < I) softplus(s_ui) - sum_entries w softplus(s_ui)
+ *     - 1/2 P_reg sum_(u < U) |p_u|^2 - 1/2 Q_reg sum_(i < I) |q_i|^2 - 1/2 user_bias_reg sum ub^2 - 1/2 item_bias_reg sum ib^2
+ * (bias regularisers of 0: the paper's model).  global_bias is read, never trained.
+ * A user half-step (the item half-step is its mirror image on the item-major view the ALS calls cache on the cu2rec_csr) forms,
+ * for EVERY u < U -- a user without entries is an ordinary row, the all-pairs term still moves it --
+ *   g_u  = sum_(entries of u) w (1 - sigma(s_ui)) q_i - sum_(i < I) sigma(s_ui) q_i - P_reg p_u
+ *   gb_u = sum_(entries of u) w (1 - sigma(s_ui))     - sum_(i < I) sigma(s_ui)     - user_bias_reg ub_u
+ * and then takes an AdaGrad step, element-wise in float32 without contraction, lr = hyper->learning_rate (no decay):
+ *   a' = a + g g;   x' = x + (lr g) / sqrtf(a') where a' > 0, else x' = x.
+ * The accumulators a, one float per factor and per bias, live with the cu2rec_model: allocated zeroed by the first logistic call,
+ * untouched by every other call.  A row keeps its values AND its accumulators bit for bit, and is counted in *n_unchanged (may be
+ * NULL), when any of its n_factors + 1 gradient values, new values or new accumulators is not finite.  Model rows past the CSR's
+ * rows / cols and the whole other side keep their bits.
+ * The all-pairs sum never forms the U x I matrix: 32 own rows per workgroup against the partner side 128 rows at a time, scored in
+ * float32 on the matrix cores as cu2rec_model_top_users scores, sigma(s) pushed through a second matrix-core product against the
+ * partner tile.  Every sum's order is a function of the partner index or the entry's position alone, there are no float atomics:
+ * results are bit-identical run to run, a row's gradient from a one-row CSR of the same cols equals its gradient among all the
+ * others, and the item half-step equals the user half-step of the transposed problem.
+ * CU2REC_EINVAL, all checked before the device or the model is touched: a null m / train / hyper, a bad side, any of the four
+ * regularisers not finite or < 0, alpha not finite or < 0, learning_rate not finite or <= 0, a CSR whose rows or cols exceed the
+ * model's.  n_factors > CU2REC_ALS_MAX_FACTORS: CU2REC_EUNSUPPORTED.  Single GPU.
+ * ---------------------------------------------------------------------------------------- */
+int cu2rec_model_lmf(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side, int *n_unchanged);
+/* The gradient cu2rec_model_lmf would step along, to the host: grad_out [n x n_factors] and bias_grad_out [n] (either may be
+ * NULL), n = the CSR's rows (CU2REC_SIDE_USERS) or cols (CU2REC_SIDE_ITEMS).  The model and the accumulators are untouched. */
+int cu2rec_model_lmf_gradient(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
+                              float *grad_out, float *bias_grad_out);
+/* *L = the log-posterior above at the model's current values: the all-pairs term from float32 matrix-core scores, softplus and
+ * every sum in double (per lane, per workgroup, the workgroups in order); the entries' term and the norms from scores in double.
+ * The same checks as cu2rec_model_lmf (no side), and L not NULL.  Reads the model only. */
+int cu2rec_model_lmf_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, double *L);
+/* The AdaGrad accumulators to the host, dense like cu2rec_model_download (any pointer may be NULL); zeros before the first
+ * logistic call.  cu2rec_model_lmf_reset zeroes them. */
+int cu2rec_model_lmf_state(cu2rec_model *m, float *aP, float *aQ, float *a_ub, float *a_ib);
+int cu2rec_model_lmf_reset(cu2rec_model *m);
+
+/* ------------------------------------------------------------------------------------------
  * train() -- replaces both overloads of train (training.h:12-15, training.cu:21-217):
  * total_iterations iterations; loss on train and test when i == 0, (i+1) % check_error == 0
  * or last (training.cu:118) printed as "TRAIN: Iteration %d GPU MAE: %f RMSE: %f" / "TEST: ..."
@@ -592,6 +633,13 @@ int cu2rec_train_implicit(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_mo
  * (cg_steps outside [1, CU2REC_ALS_CG_MAX_STEPS]: CU2REC_EINVAL before anything is touched). */
 int cu2rec_train_implicit_cg(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int cg_steps,
                              int verbose, double *objectives, cu2rec_train_stats *stats);
+/* Logistic matrix factorization training: the accumulators are reset, then total_iterations sweeps of cu2rec_model_lmf -- the users,
+ * then the items when cfg->is_train -- at learning rate cfg->learning_rate (AdaGrad's own; no decay) with the log-posterior
+ * evaluated at cu2rec_train_implicit's cadence, printed as "TRAIN: Iteration %d GPU logistic objective: %f" when `verbose`, and
+ * stored in objectives[i] (may be NULL; NaN elsewhere).  stats->updates = rows stepped (rows left unchanged are not counted).
+ * cu2rec_model_lmf's checks with its codes, before the device or the model is touched. */
+int cu2rec_train_lmf(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose, double *objectives,
+                     cu2rec_train_stats *stats);
 
 /* ------------------------------------------------------------------------------------------
  * Sharding by user (multi-GPU; the reference is single device).  Host-side planner:
