@@ -37,6 +37,25 @@ def _solver(solver):
         raise ValueError("solver must be one of %s, not %r" % (list(IALS_SOLVERS), solver))
 
 
+def _hyper(hyper):
+    """Hyper, or (learning_rate, P_reg, Q_reg, user_bias_reg, item_bias_reg) -> Hyper."""
+    return hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+
+
+def _half_steps(side, sweeps, call):
+    """`sweeps` times over the half-steps of side "users", "items" or "both" (users, then items): call(side code, byref(count))
+    is one library call's status; returns the counts summed."""
+    if side not in ALS_SIDES:
+        raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+    total = 0
+    for _ in range(int(sweeps)):
+        for s in ALS_SIDES[side]:
+            n = C.c_int()
+            check(call(s, C.byref(n)))
+            total += n.value
+    return total
+
+
 def _choice(table, value, what):
     if not isinstance(value, str):
         return int(value)
@@ -283,7 +302,7 @@ class Model:
 
     def sgd(self, train, hyper, seed, iter0, n_iters, mode=SGD_HOGWILD, update_items=True):
         """n_iters reference iterations of sgd_update (sgd.cu:22-75) starting at global iteration iter0."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        h = _hyper(hyper)
         check(lib().cu2rec_model_sgd(self._h, train._h, C.byref(h), int(seed), int(iter0), int(n_iters), _mode(mode),
                                      1 if update_items else 0))
 
@@ -294,20 +313,11 @@ class Model:
         solver "cholesky" solves every row exactly; "cg" gives the rows of at most ALS_CHUNK ratings cg_steps conjugate-gradient
         steps from their current factors and bias (cu2rec_model_als_cg; cg_steps is not read otherwise).
         Returns the number of rows left unchanged (a failed pivot; a non-finite or negative curvature), summed over the half-steps."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
-        if side not in ALS_SIDES:
-            raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        h = _hyper(hyper)
         _solver(solver)
-        total = 0
-        for _ in range(int(sweeps)):
-            for s in ALS_SIDES[side]:
-                n = C.c_int()
-                if solver == "cg":
-                    check(lib().cu2rec_model_als_cg(self._h, train._h, C.byref(h), s, int(cg_steps), C.byref(n)))
-                else:
-                    check(lib().cu2rec_model_als(self._h, train._h, C.byref(h), s, C.byref(n)))
-                total += n.value
-        return total
+        if solver == "cg":
+            return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_als_cg(self._h, train._h, C.byref(h), s, int(cg_steps), n))
+        return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_als(self._h, train._h, C.byref(h), s, n))
 
     def ials(self, train, hyper, alpha=40.0, side="both", sweeps=1, solver="cholesky", cg_steps=3):
         """Implicit-feedback half-steps (cu2rec_model_als_implicit): every user x item pair of train's shape counts, a stored entry
@@ -315,24 +325,16 @@ class Model:
         Rows without entries become zero rows.  solver "cholesky" solves every row exactly; "cg" gives the rows of at most
         ALS_CHUNK entries cg_steps conjugate-gradient steps from their current factors (cu2rec_model_als_implicit_cg; cg_steps is
         not read otherwise).  Returns the number of rows left unchanged (a failed pivot; a non-finite or negative curvature)."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
-        if side not in ALS_SIDES:
-            raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
+        h = _hyper(hyper)
         _solver(solver)
-        total = 0
-        for _ in range(int(sweeps)):
-            for s in ALS_SIDES[side]:
-                n = C.c_int()
-                if solver == "cg":
-                    check(lib().cu2rec_model_als_implicit_cg(self._h, train._h, C.byref(h), float(alpha), s, int(cg_steps), C.byref(n)))
-                else:
-                    check(lib().cu2rec_model_als_implicit(self._h, train._h, C.byref(h), float(alpha), s, C.byref(n)))
-                total += n.value
-        return total
+        if solver == "cg":
+            return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_als_implicit_cg(self._h, train._h, C.byref(h), float(alpha), s,
+                                                                                             int(cg_steps), n))
+        return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_als_implicit(self._h, train._h, C.byref(h), float(alpha), s, n))
 
     def implicit_objective(self, train, hyper, alpha):
         """The objective ials() minimises, at the model's current values (cu2rec_model_implicit_objective) -> float."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        h = _hyper(hyper)
         L = C.c_double()
         check(lib().cu2rec_model_implicit_objective(self._h, train._h, C.byref(h), float(alpha), C.byref(L)))
         return L.value
@@ -344,21 +346,13 @@ class Model:
         sweeps as in als().  alpha defaults to 1.0, not ials()'s 40: here the weight multiplies a log-odds gradient, and 40 x a
         5-star rating saturates it.  The AdaGrad accumulators stay with the model (lmf_state, lmf_reset).
         Returns the number of rows left unchanged (a non-finite gradient or step), summed over the half-steps."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
-        if side not in ALS_SIDES:
-            raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
-        total = 0
-        for _ in range(int(sweeps)):
-            for s in ALS_SIDES[side]:
-                n = C.c_int()
-                check(lib().cu2rec_model_lmf(self._h, train._h, C.byref(h), float(alpha), s, C.byref(n)))
-                total += n.value
-        return total
+        h = _hyper(hyper)
+        return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_lmf(self._h, train._h, C.byref(h), float(alpha), s, n))
 
     def lmf_gradient(self, train, hyper, alpha, side):
         """The gradient lmf() would step along for side "users" or "items" (cu2rec_model_lmf_gradient) -> (grad, bias_grad),
         float32 of shapes (n, n_factors) and (n,), n = train's rows or cols.  The model and the accumulators are untouched."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        h = _hyper(hyper)
         if side not in ("users", "items"):
             raise ValueError("side must be 'users' or 'items', not %r" % (side,))
         n = train.rows if side == "users" else train.cols
@@ -368,7 +362,7 @@ class Model:
 
     def lmf_objective(self, train, hyper, alpha):
         """The log-posterior lmf() climbs, at the model's current values (cu2rec_model_lmf_objective) -> float."""
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        h = _hyper(hyper)
         L = C.c_double()
         check(lib().cu2rec_model_lmf_objective(self._h, train._h, C.byref(h), float(alpha), C.byref(L)))
         return L.value
@@ -550,7 +544,7 @@ def sgd_update(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias,
                hyper, seed, iter0, n_iters, mode=SGD_HOGWILD, update_items=True, user_offset=0, stream=None,
                sample_pairs=None):
     """cu2rec_sgd_update(_ex) on raw device addresses (ints); sample_pairs: the optional side-by-side sample array."""
-    h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+    h = _hyper(hyper)
     check(lib().cu2rec_sgd_update_ex(indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias, item_bias,
                                      float(global_bias), n_factors, C.byref(h), int(seed), int(iter0), int(n_iters),
                                      _mode(mode), 1 if update_items else 0, int(user_offset), sample_pairs, stream))
@@ -584,7 +578,7 @@ def sgd_update_ordered(schedule, indptr, indices, data, n_rows, n_cols, P, ldp, 
                        global_bias, n_factors, hyper, seed, iter0, n_iters, update_items=True, user_offset=0,
                        stream=None):
     """cu2rec_sgd_update_ordered on raw device addresses."""
-    h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+    h = _hyper(hyper)
     check(lib().cu2rec_sgd_update_ordered(schedule._h, indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq, user_bias,
                                           item_bias, float(global_bias), n_factors, C.byref(h), int(seed), int(iter0),
                                           int(n_iters), 1 if update_items else 0, int(user_offset), stream))
@@ -594,7 +588,7 @@ def sgd_update_blocksolve(schedule, indptr, indices, data, n_rows, n_cols, P, ld
                           global_bias, n_factors, hyper, seed, iter0, n_iters, update_items=True, user_offset=0,
                           stream=None):
     """cu2rec_sgd_update_blocksolve on raw device addresses."""
-    h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+    h = _hyper(hyper)
     check(lib().cu2rec_sgd_update_blocksolve(schedule._h, indptr, indices, data, n_rows, n_cols, P, ldp, Q, ldq,
                                              user_bias, item_bias, float(global_bias), n_factors, C.byref(h), int(seed),
                                              int(iter0), int(n_iters), 1 if update_items else 0, int(user_offset), stream))

@@ -34,6 +34,7 @@
 
 #include "als.hpp"
 #include "kernels.hpp"
+#include "objective_pass.hpp"
 #include "score_tile.hpp"
 
 namespace cu2rec {
@@ -60,8 +61,6 @@ struct AlsShape {
     static constexpr int pairs = NT * (NT + 1) / 2;
     static constexpr int per_wave = (pairs + kAlsWaves - 1) / kAlsWaves;
 };
-
-__host__ __device__ inline int tri(int i) { return i * (i + 1) / 2; }
 
 __device__ inline void pair_tiles(int p, int &ti, int &tj) {  // pair p of the row-major lower triangle of tiles
     ti = 0;
@@ -425,8 +424,6 @@ int run_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows,
 }
 
 // ---- the implicit objective ----------------------------------------------------------------------------------------------
-constexpr int kObjThreads = 256, kObjGroup = 16, kObjMaxBlocks = 4096;
-
 struct IalsObjectiveArgs {
     const int *indptr, *indices;
     const float *data;
@@ -436,20 +433,6 @@ struct IalsObjectiveArgs {
     double *partials;  // [blocks][3]: entries term, sum |p_u|^2, sum |q_i|^2
 };
 
-// x . y over the first f floats of two rows, in double, by one 16-lane group; every lane returns the sum
-__device__ inline double group_dot(const float *x, const float *y, int f, int lane16) {
-    double d = 0.0;
-    for (int c0 = 4 * lane16; c0 < f; c0 += 4 * kObjGroup) {
-        const float4 a = *reinterpret_cast<const float4 *>(x + c0), b = *reinterpret_cast<const float4 *>(y + c0);
-        d += static_cast<double>(a.x) * static_cast<double>(b.x);
-        if (c0 + 1 < f) d += static_cast<double>(a.y) * static_cast<double>(b.y);
-        if (c0 + 2 < f) d += static_cast<double>(a.z) * static_cast<double>(b.z);
-        if (c0 + 3 < f) d += static_cast<double>(a.w) * static_cast<double>(b.w);
-    }
-    for (int m = kObjGroup / 2; m > 0; m >>= 1) d += __shfl_xor(d, m, kObjGroup);
-    return d;
-}
-
 // one pass over the entries and the rows of both sides, a 16-lane group per entry / row, sums in double; per-block partials
 __global__ __launch_bounds__(kObjThreads) void ials_objective_kernel(IalsObjectiveArgs a) {
     __shared__ double red[3][kObjThreads];
@@ -457,13 +440,8 @@ __global__ __launch_bounds__(kObjThreads) void ials_objective_kernel(IalsObjecti
     const int group = (blockIdx.x * kObjThreads + tid) / kObjGroup, groups = gridDim.x * (kObjThreads / kObjGroup);
     double s_e = 0.0, s_p = 0.0, s_q = 0.0;
     for (int k = group; k < a.nnz; k += groups) {
-        int lo = 0, hi = a.rows;  // the last u with indptr[u] <= k
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (a.indptr[mid] <= k) lo = mid;
-            else hi = mid - 1;
-        }
-        const double s = group_dot(a.P + static_cast<size_t>(lo) * a.ldp, a.Q + static_cast<size_t>(a.indices[k]) * a.ldq, a.n_factors, lane16);
+        const int u = row_of_entry(a.indptr, a.rows, k);
+        const double s = group_dot(a.P + static_cast<size_t>(u) * a.ldp, a.Q + static_cast<size_t>(a.indices[k]) * a.ldq, a.n_factors, lane16);
         const double w = static_cast<double>(a.alpha * a.data[k]);
         if (lane16 == 0) s_e += w * (1.0 - s) * (1.0 - s) + 1.0 - 2.0 * s;
     }
@@ -477,14 +455,8 @@ __global__ __launch_bounds__(kObjThreads) void ials_objective_kernel(IalsObjecti
         const double n2 = group_dot(x, x, a.n_factors, lane16);
         if (lane16 == 0) s_q += n2;
     }
-    red[0][tid] = s_e;
-    red[1][tid] = s_p;
-    red[2][tid] = s_q;
-    for (int stride = kObjThreads / 2; stride > 0; stride >>= 1) {
-        __syncthreads();
-        if (tid < stride)
-            for (int j = 0; j < 3; ++j) red[j][tid] += red[j][tid + stride];
-    }
+    const double sums[3] = {s_e, s_p, s_q};
+    block_reduce(sums, red);
     if (tid == 0)
         for (int j = 0; j < 3; ++j) a.partials[3 * blockIdx.x + j] = red[j][0];
 }
@@ -504,12 +476,7 @@ __global__ __launch_bounds__(kObjThreads) void ials_objective_reduce_kernel(cons
         pair_tiles(e / (16 * 64), ti, tj);
         s[3] += (ti == tj ? 1.0 : 2.0) * (static_cast<double>(gp[e]) * static_cast<double>(gq[e]));
     }
-    for (int j = 0; j < 4; ++j) red[j][tid] = s[j];
-    for (int stride = kObjThreads / 2; stride > 0; stride >>= 1) {
-        __syncthreads();
-        if (tid < stride)
-            for (int j = 0; j < 4; ++j) red[j][tid] += red[j][tid + stride];
-    }
+    block_reduce(s, red);
     if (tid == 0)
         for (int j = 0; j < 4; ++j) out[j] = red[j][0];
 }
@@ -518,13 +485,7 @@ __global__ __launch_bounds__(kObjThreads) void ials_objective_reduce_kernel(cons
 __global__ void als_row_of_kernel(const int *__restrict__ indptr, int rows, int nnz, int *__restrict__ row_of,
                                   int *__restrict__ pos) {
     for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += gridDim.x * blockDim.x) {
-        int lo = 0, hi = rows;  // the last u with indptr[u] <= k
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (indptr[mid] <= k) lo = mid;
-            else hi = mid - 1;
-        }
-        row_of[k] = lo;
+        row_of[k] = row_of_entry(indptr, rows, k);
         pos[k] = k;
     }
 }
@@ -630,9 +591,7 @@ double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t str
         run_global_gram<tiles()>(c, o.P, o.ldp, o.rows, o.n_factors, c.g0, stream);
         run_global_gram<tiles()>(c, o.Q, o.ldq, o.cols, o.n_factors, c.g0_other, stream);
     });
-    const size_t work = static_cast<size_t>(std::max(o.nnz, std::max(o.rows, o.cols)));
-    const int per_block = (kObjThreads / kObjGroup) * 8;  // eight entries per group
-    const int blocks = static_cast<int>(std::min<size_t>(std::max<size_t>((work + per_block - 1) / per_block, 1), kObjMaxBlocks));
+    const int blocks = objective_blocks(static_cast<size_t>(std::max(o.nnz, std::max(o.rows, o.cols))));
     if (c.objective.count < 3 * static_cast<size_t>(kObjMaxBlocks) + 4) c.objective.allocate(3 * static_cast<size_t>(kObjMaxBlocks) + 4);
     IalsObjectiveArgs a{o.indptr, o.indices, o.data, o.P, o.Q, o.ldp, o.ldq, o.rows, o.cols, o.nnz, o.n_factors, o.alpha, c.objective.ptr};
     hipLaunchKernelGGL(ials_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, a);

@@ -93,6 +93,8 @@ struct AlsObjectiveProblem {
     float alpha, P_reg, Q_reg;
 };
 
+__host__ __device__ inline int tri(int i) { return i * (i + 1) / 2; }  // tile pairs ti >= tj of the lower triangle: pair tri(ti) + tj
+
 // 32-column tiles of the implicit half-step's staged operands: f factor columns and the right-hand side's weight
 inline int ials_tiles(int n_factors) { return (n_factors + 1 + 31) / 32; }
 

@@ -9,13 +9,11 @@
 // into LDS once up to f = 128 (64 KiB) and reads it from L2 otherwise.  After that one barrier the wavefronts never
 // meet again.
 //
-// Two lane <-> element maps.  OWNER: lane l holds elements l, l + 64, ... of x, r, p, A p (E = ceil(f / 64) registers each); the
-// G0 product reads column i of the symmetric G0 for element i, a chain over j = 0 .. f - 1.  ENTRY: the wavefront is four groups
-// of 16 lanes, group g takes the row's entries e = g, g + 4, ... in ascending order, lane l16 of a group holds columns
-// 4 l16 + 64 k .. + 3 of the gathered partner row; the dot product against v (kept in LDS per wavefront) is reduced over the 16
-// lanes by a butterfly and w (q . v) q accumulated per group; the four groups' partial sums go through LDS and are added in group
-// order.  Every sum's order is a function of the row's length and f alone: no float atomics, nothing that depends on which
-// wavefront or workgroup picked the row up.
+// The two lane <-> element maps of row_wave.hpp.  OWNER: x, r, p, A p (E = ceil(f / 64) registers each); the G0 product reads
+// column i of the symmetric G0 for element i, a chain over j = 0 .. f - 1.  ENTRY: the gathered partner rows, two entries per group
+// in flight; the dot product is against v (kept in LDS per wavefront), and w (q . v) q is accumulated per group.  Every sum's order
+// is a function of the row's length and f alone: no float atomics, nothing that depends on which wavefront or workgroup picked the
+// row up.
 //
 // The explicit half-step (als.hpp: als_cg_short_rows; cu2rec_model_als_cg) is the AlsKind::Explicit case of the same templates: the
 // system has order D = f + 1, x = [factors; bias], z_e = [q_e; 1] and
@@ -31,6 +29,7 @@
 #include "als.hpp"
 #include "kernels.hpp"
 #include "mfma_f32.hpp"
+#include "row_wave.hpp"
 
 namespace cu2rec {
 
@@ -49,8 +48,6 @@ struct CgArgs {
     int *unsolved;
 };
 
-__device__ inline int cg_tri(int i) { return i * (i + 1) / 2; }
-
 // G0 from the accumulator layout [tile pair][16][64] (tile pairs ti >= tj of the lower triangle, als.hip) to dense [f][S]; the
 // upper triangle mirrors the lower one, the columns f .. S - 1 are zero
 __global__ void cg_unpack_g0_kernel(const float *__restrict__ acc, float *__restrict__ dense, int f, int S) {
@@ -60,24 +57,12 @@ __global__ void cg_unpack_g0_kernel(const float *__restrict__ acc, float *__rest
     float v = 0.f;
     if (j < f) {
         const int a = max(i, j), b = min(i, j);
-        const int ti = a >> 5, tj = b >> 5, ra = a & 31, r = b & 31;
-        const int h = (ra >> 2) & 1, reg = (ra & 3) + 4 * (ra >> 3);  // acc_row(reg, h) == ra
-        v = acc[(static_cast<size_t>(cg_tri(ti) + tj) * 16 + reg) * 64 + r + 32 * h];
+        const int ti = a >> 5, tj = b >> 5, r = b & 31;
+        int reg, h;
+        acc_reg_of_row(a & 31, reg, h);
+        v = acc[(static_cast<size_t>(tri(ti) + tj) * 16 + reg) * 64 + r + 32 * h];
     }
     dense[e] = v;
-}
-
-// the wavefront's LDS traffic is its own: order it for the compiler and the memory model, no instruction is needed beyond that
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// sum over the wavefront, the same bits in every lane (a butterfly: both partners add the same two values)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) v = v + __shfl_xor(v, m, 64);
-    return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
 }
 
 template <int E>
@@ -88,33 +73,11 @@ __device__ __forceinline__ float owner_dot(const float (&a)[E], const float (&b)
     return wave_sum(s);
 }
 
-// partner row `idx`, columns c0 .. c0 + 3 (c0 < 64 E), zero from column F on: the padding floats are never read as data.
-// AlsKind::Explicit: column F is the constant 1 of z = [q; 1], synthesised here
-template <AlsKind K>
-__device__ __forceinline__ float4 load_q(const AlsProblem &p, int idx, int c0) {
-    const int F = p.n_factors;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c0 < F) {
-        v = *reinterpret_cast<const float4 *>(p.X + static_cast<size_t>(idx) * p.ldx + c0);
-        if (c0 + 1 >= F) v.y = 0.f;
-        if (c0 + 2 >= F) v.z = 0.f;
-        if (c0 + 3 >= F) v.w = 0.f;
-    }
-    if constexpr (K == AlsKind::Explicit) {
-        if (c0 == F) v.x = 1.f;
-        if (c0 + 1 == F) v.y = 1.f;
-        if (c0 + 2 == F) v.z = 1.f;
-        if (c0 + 3 == F) v.w = 1.f;
-    }
-    return v;
-}
-
 // ENTRY pass over entries [lo, hi): t = sum_e w_e (q_e . v) q_e with v read from pv; FIRST: also b = sum_e (1 + w_e) q_e.
 // AlsKind::Explicit: t = sum_e (z_e . v) z_e and b = sum_e t_e z_e.  Results in the OWNER map.  part: the wavefront's [4][64 E] floats.
 template <int E, bool FIRST, AlsKind K>
 __device__ __forceinline__ void entry_pass(const CgArgs &a, int lo, int hi, const float *pv, float *part, float (&t)[E],
                                            float (&b)[E]) {
-    constexpr int FS = 64 * E;
     const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
     float4 v[E], acc[E], bacc[E];
 #pragma unroll
@@ -137,59 +100,28 @@ __device__ __forceinline__ void entry_pass(const CgArgs &a, int lo, int hi, cons
             else if constexpr (FIRST) w[u] = (a.data[ec] - a.p.global_bias) - a.p.xb[idx];
             else w[u] = 0.f;
 #pragma unroll
-            for (int k = 0; k < E; ++k) q[u][k] = load_q<K>(a.p, idx, 4 * l16 + 64 * k);
+            for (int k = 0; k < E; ++k) q[u][k] = load_partner4<K == AlsKind::Explicit>(a.p.X, a.p.ldx, a.p.n_factors, idx, 4 * l16 + 64 * k);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
-            float d = 0.f;
-#pragma unroll
-            for (int k = 0; k < E; ++k) {
-                d = fmaf(q[u][k].x, v[k].x, d);
-                d = fmaf(q[u][k].y, v[k].y, d);
-                d = fmaf(q[u][k].z, v[k].z, d);
-                d = fmaf(q[u][k].w, v[k].w, d);
-            }
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) d = d + __shfl_xor(d, m, 16);
+            const float d = group_dot4<E>(q[u], v);
             if (on[u]) {
                 const float s = K == AlsKind::Implicit ? w[u] * d : d;
                 [[maybe_unused]] const float bw = K == AlsKind::Implicit ? 1.f + w[u] : w[u];
 #pragma unroll
                 for (int k = 0; k < E; ++k) {
-                    acc[k].x = fmaf(s, q[u][k].x, acc[k].x);
-                    acc[k].y = fmaf(s, q[u][k].y, acc[k].y);
-                    acc[k].z = fmaf(s, q[u][k].z, acc[k].z);
-                    acc[k].w = fmaf(s, q[u][k].w, acc[k].w);
-                    if constexpr (FIRST) {
-                        bacc[k].x = fmaf(bw, q[u][k].x, bacc[k].x);
-                        bacc[k].y = fmaf(bw, q[u][k].y, bacc[k].y);
-                        bacc[k].z = fmaf(bw, q[u][k].z, bacc[k].z);
-                        bacc[k].w = fmaf(bw, q[u][k].w, bacc[k].w);
-                    }
+                    axpy4(s, q[u][k], acc[k]);
+                    if constexpr (FIRST) axpy4(bw, q[u][k], bacc[k]);
                 }
             }
         }
     }
-    // the four groups' sums, added in group order
-    wave_sync();
-#pragma unroll
-    for (int k = 0; k < E; ++k) *reinterpret_cast<float4 *>(part + g * FS + 4 * l16 + 64 * k) = acc[k];
-    wave_sync();
-#pragma unroll
-    for (int k = 0; k < E; ++k) {
-        const int i = lane + 64 * k;
-        t[k] = ((part[i] + part[FS + i]) + part[2 * FS + i]) + part[3 * FS + i];
-    }
+    float *mine = part + g * (64 * E) + 4 * l16;
+    wave_sync();  // the previous pass has read part
+    combine_groups<E>(acc, part, mine, lane, t);
     if constexpr (FIRST) {
         wave_sync();
-#pragma unroll
-        for (int k = 0; k < E; ++k) *reinterpret_cast<float4 *>(part + g * FS + 4 * l16 + 64 * k) = bacc[k];
-        wave_sync();
-#pragma unroll
-        for (int k = 0; k < E; ++k) {
-            const int i = lane + 64 * k;
-            b[k] = ((part[i] + part[FS + i]) + part[2 * FS + i]) + part[3 * FS + i];
-        }
+        combine_groups<E>(bacc, part, mine, lane, b);
     }
 }
 
@@ -363,17 +295,12 @@ void launch_cg(const CgArgs &a, int grid, hipStream_t stream) {
     CU2REC_HIP(hipGetLastError());
 }
 
-// every row of the side, kCgWaves per workgroup; elems: the per-lane element count E of the system's order
+// every row of the side, kCgWaves per workgroup; order: of the row's system, E = ceil(order / 64) elements per lane
 template <AlsKind K>
-void launch_cg_rows(const CgArgs &a, int elems, hipStream_t stream) {
+void launch_cg_rows(const CgArgs &a, int order, hipStream_t stream) {
     if (a.rows <= 0) return;
     const int grid = std::min((a.rows + kCgWaves - 1) / kCgWaves, kCgMaxBlocks);
-    switch (elems) {
-        case 1: launch_cg<1, K>(a, grid, stream); break;
-        case 2: launch_cg<2, K>(a, grid, stream); break;
-        case 3: launch_cg<3, K>(a, grid, stream); break;
-        default: launch_cg<4, K>(a, grid, stream); break;
-    }
+    dispatch_1_to_4(order, [&](auto elems) { launch_cg<elems(), K>(a, grid, stream); });
 }
 
 }  // namespace
@@ -388,14 +315,14 @@ void ials_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, i
                        c.g0.ptr, c.g0_dense.ptr, F, S);
     CU2REC_HIP(hipGetLastError());
     CgArgs a{side.indptr, side.indices, side.data, p, c.g0_dense.ptr, S, std::min(side.rows, max_rows), cg_steps, c.unsolved.ptr};
-    launch_cg_rows<AlsKind::Implicit>(a, (F + 63) / 64, stream);
+    launch_cg_rows<AlsKind::Implicit>(a, F, stream);
 }
 
 void als_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, int max_rows, int cg_steps, hipStream_t stream) {
     const int F = p.n_factors;
     if (F < 1 || F > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als_cg: n_factors above 252 is not supported");
     CgArgs a{side.indptr, side.indices, side.data, p, nullptr, 0, std::min(side.rows, max_rows), cg_steps, c.unsolved.ptr};
-    launch_cg_rows<AlsKind::Explicit>(a, (F + 1 + 63) / 64, stream);  // order f + 1 <= 253: E <= 4
+    launch_cg_rows<AlsKind::Explicit>(a, F + 1, stream);  // order f + 1 <= 253: E <= 4
 }
 
 }  // namespace cu2rec

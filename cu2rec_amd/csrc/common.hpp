@@ -26,6 +26,16 @@ inline void require(bool ok, const char *what) {
     if (!ok) fail(CU2REC_EINVAL, what);
 }
 
+// The argument checks of one entry point: need(ok, code, ": what") fails with fn + what, put together only when a check fails.
+struct Need {
+    const char *fn;
+    void operator()(bool ok, int code, const char *what) const {
+        if (ok) return;
+        const std::string name = fn;
+        fail(code, name + what);
+    }
+};
+
 // Runs `body`, mapping exceptions to status codes. Every extern "C" entry point goes through it.
 template <class F>
 int guarded(F &&body) noexcept {

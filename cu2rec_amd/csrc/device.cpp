@@ -507,65 +507,74 @@ AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream) {
     }
     return c.items;
 }
-}  // namespace
 
-// Argument checks first: nothing on the device or in the model is touched by a call that fails them.
-int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream, int cg_steps) {
-    const char *fn = cg_steps > 0 ? "cu2rec_model_als_cg" : "cu2rec_model_als";
-    auto need = [fn](bool ok, int code, const char *what) {  // the message is put together only when a check fails
-        if (!ok) fail(code, std::string(fn) + what);
-    };
-    need(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
-    const bool users = side == CU2REC_SIDE_USERS;
-    const float reg = users ? h.P_reg : h.Q_reg, reg_bias = users ? h.user_bias_reg : h.item_bias_reg;
-    need(std::isfinite(reg) && reg > 0.f, CU2REC_EINVAL, ": the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
-    need(std::isfinite(reg_bias) && reg_bias >= 0.f, CU2REC_EINVAL, ": the bias regulariser must be finite and >= 0");
-    need(train.rows <= rows && train.max_item < cols, CU2REC_EINVAL, ": ratings exceed the model's shape");
-    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
-    require_device();
-    check_faults();
-    finish_swap();
-    AlsSide &rows_of_side = als_side(train, users, stream);
-    AlsCache &c = *train.als;
-    const AlsProblem p = users ? AlsProblem{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, global_bias, reg, reg_bias}
-                               : AlsProblem{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, global_bias, reg, reg_bias};
-    const int unsolved = als_half_step(c, rows_of_side, p, users ? rows : cols, stream, cg_steps);
-    other_in_sync = false;  // Q moved on without the ping-pong pair
-    return unsolved;
+// One side of the model as a half-step sees it: the rows that move, and the frozen partner side.
+struct SideView {
+    float *own, *own_bias, *partner, *partner_bias;
+    int ld_own, ld_partner;
+};
+
+SideView side_view(DeviceModel &m, bool users) {
+    return users ? SideView{m.P.ptr, m.user_bias.ptr, m.Q.ptr, m.item_bias.ptr, m.ld, m.ldq}
+                 : SideView{m.Q.ptr, m.item_bias.ptr, m.P.ptr, m.user_bias.ptr, m.ldq, m.ld};
 }
 
-// Implicit feedback (include/cu2rec_amd.h: cu2rec_model_als_implicit).  The same order as als(): argument checks, then the device.
-int DeviceModel::ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream, int cg_steps) {
-    const std::string fn = cg_steps > 0 ? "cu2rec_model_als_implicit_cg" : "cu2rec_model_als_implicit";
-    require(side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS, (fn + ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS").c_str());
-    const bool users = side == CU2REC_SIDE_USERS;
-    const float reg = users ? h.P_reg : h.Q_reg;
-    require(std::isfinite(reg) && reg > 0.f, (fn + ": the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0").c_str());
-    require(std::isfinite(alpha) && alpha >= 0.f, (fn + ": alpha must be finite and >= 0").c_str());
-    require(train.rows <= rows && train.max_item < cols && train.cols <= cols, (fn + ": ratings exceed the model's shape").c_str());
-    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, fn + ": n_factors above 252 is not supported");
+// what every trainer's call does between its argument checks and its work
+void enter(DeviceModel &m) {
     require_device();
     check_faults();
-    finish_swap();
+    m.finish_swap();
+}
+
+bool is_side(int side) { return side == CU2REC_SIDE_USERS || side == CU2REC_SIDE_ITEMS; }
+bool finite_at_least(float v, float low) { return std::isfinite(v) && v >= low; }
+
+// One ALS half-step, explicit or implicit (include/cu2rec_amd.h: cu2rec_model_als, cu2rec_model_als_implicit and their _cg forms).
+// Argument checks first: nothing on the device or in the model is touched by a call that fails them.
+int als_half_step_of(DeviceModel &m, AlsKind kind, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side,
+                     hipStream_t stream, int cg_steps) {
+    const bool implicit = kind == AlsKind::Implicit;
+    const Need need{implicit ? (cg_steps > 0 ? "cu2rec_model_als_implicit_cg" : "cu2rec_model_als_implicit")
+                             : (cg_steps > 0 ? "cu2rec_model_als_cg" : "cu2rec_model_als")};
+    need(is_side(side), CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    const bool users = side == CU2REC_SIDE_USERS;
+    const float reg = users ? h.P_reg : h.Q_reg, reg_bias = implicit ? 0.f : (users ? h.user_bias_reg : h.item_bias_reg);
+    need(std::isfinite(reg) && reg > 0.f, CU2REC_EINVAL, ": the factor regulariser (P_reg for users, Q_reg for items) must be finite and > 0");
+    if (implicit) need(finite_at_least(alpha, 0.f), CU2REC_EINVAL, ": alpha must be finite and >= 0");
+    else need(finite_at_least(reg_bias, 0.f), CU2REC_EINVAL, ": the bias regulariser must be finite and >= 0");
+    need(train.rows <= m.rows && train.max_item < m.cols && (!implicit || train.cols <= m.cols), CU2REC_EINVAL,
+         ": ratings exceed the model's shape");
+    need(m.n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
+    enter(m);
     AlsSide &rows_of_side = als_side(train, users, stream);
-    AlsProblem p = users ? AlsProblem{Q.ptr, ldq, item_bias.ptr, P.ptr, ld, user_bias.ptr, n_factors, 0.f, reg, 0.f}
-                         : AlsProblem{P.ptr, ld, user_bias.ptr, Q.ptr, ldq, item_bias.ptr, n_factors, 0.f, reg, 0.f};
-    p.alpha = alpha;
-    p.x_rows = users ? train.cols : train.rows;  // every partner row inside the CSR counts
-    const int unsolved = ials_half_step(*train.als, rows_of_side, p, users ? rows : cols, stream, cg_steps);
-    other_in_sync = false;
+    const SideView v = side_view(m, users);
+    AlsProblem p{v.partner, v.ld_partner, v.partner_bias, v.own, v.ld_own, v.own_bias, m.n_factors, implicit ? 0.f : m.global_bias,
+                 reg, reg_bias};
+    if (implicit) {
+        p.alpha = alpha;
+        p.x_rows = users ? train.cols : train.rows;  // every partner row inside the CSR counts
+    }
+    const int unsolved = (implicit ? ials_half_step : als_half_step)(*train.als, rows_of_side, p, users ? m.rows : m.cols, stream, cg_steps);
+    m.other_in_sync = false;  // Q moved on without the ping-pong pair
     return unsolved;
+}
+}  // namespace
+
+int DeviceModel::als(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream, int cg_steps) {
+    return als_half_step_of(*this, AlsKind::Explicit, train, h, 0.f, side, stream, cg_steps);
+}
+
+int DeviceModel::ials(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream, int cg_steps) {
+    return als_half_step_of(*this, AlsKind::Implicit, train, h, alpha, side, stream, cg_steps);
 }
 
 double DeviceModel::implicit_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream) {
-    require(std::isfinite(h.P_reg) && h.P_reg >= 0.f && std::isfinite(h.Q_reg) && h.Q_reg >= 0.f,
-            "cu2rec_model_implicit_objective: the factor regularisers must be finite and >= 0");
-    require(std::isfinite(alpha) && alpha >= 0.f, "cu2rec_model_implicit_objective: alpha must be finite and >= 0");
-    require(train.rows <= rows && train.max_item < cols && train.cols <= cols, "cu2rec_model_implicit_objective: ratings exceed the model's shape");
-    if (n_factors > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_implicit_objective: n_factors above 252 is not supported");
-    require_device();
-    check_faults();
-    finish_swap();
+    const Need need{"cu2rec_model_implicit_objective"};
+    need(finite_at_least(h.P_reg, 0.f) && finite_at_least(h.Q_reg, 0.f), CU2REC_EINVAL, ": the factor regularisers must be finite and >= 0");
+    need(finite_at_least(alpha, 0.f), CU2REC_EINVAL, ": alpha must be finite and >= 0");
+    need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": ratings exceed the model's shape");
+    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
+    enter(*this);
     if (!train.als) train.als.reset(new AlsCache);
     const AlsObjectiveProblem o{train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz,
                                 P.ptr, ld, Q.ptr, ldq, n_factors, alpha, h.P_reg, h.Q_reg};
@@ -574,13 +583,11 @@ double DeviceModel::implicit_objective(const DeviceCsr &train, const cu2rec_hype
 
 // Logistic matrix factorization (include/cu2rec_amd.h: cu2rec_model_lmf).  The checks of ials(), in its order, before the device.
 void DeviceModel::lmf_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, const int *side) const {
-    auto need = [fn](bool ok, int code, const char *what) {
-        if (!ok) fail(code, std::string(fn) + what);
-    };
-    need(!side || *side == CU2REC_SIDE_USERS || *side == CU2REC_SIDE_ITEMS, CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    const Need need{fn};
+    need(!side || is_side(*side), CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
     for (float reg : {h.P_reg, h.Q_reg, h.user_bias_reg, h.item_bias_reg})
-        need(std::isfinite(reg) && reg >= 0.f, CU2REC_EINVAL, ": every regulariser must be finite and >= 0");
-    need(std::isfinite(alpha) && alpha >= 0.f, CU2REC_EINVAL, ": alpha must be finite and >= 0");
+        need(finite_at_least(reg, 0.f), CU2REC_EINVAL, ": every regulariser must be finite and >= 0");
+    need(finite_at_least(alpha, 0.f), CU2REC_EINVAL, ": alpha must be finite and >= 0");
     need(std::isfinite(h.learning_rate) && h.learning_rate > 0.f, CU2REC_EINVAL, ": learning_rate must be finite and > 0");
     need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": entries exceed the model's shape");
     need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
@@ -590,11 +597,10 @@ namespace {
 // the half-step's view of one side; the item side reads the item-major view cached on the CSR by the ALS calls
 LmfProblem lmf_problem(DeviceModel &m, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, bool users, hipStream_t stream) {
     const AlsSide &s = als_side(train, users, stream);
-    if (users)
-        return {s.indptr, s.indices, s.data, m.P.ptr, m.ld, m.user_bias.ptr, train.rows, m.Q.ptr, m.ldq, m.item_bias.ptr, train.cols,
-                m.n_factors, m.global_bias, alpha, h.P_reg, h.user_bias_reg, h.learning_rate};
-    return {s.indptr, s.indices, s.data, m.Q.ptr, m.ldq, m.item_bias.ptr, train.cols, m.P.ptr, m.ld, m.user_bias.ptr, train.rows,
-            m.n_factors, m.global_bias, alpha, h.Q_reg, h.item_bias_reg, h.learning_rate};
+    const SideView v = side_view(m, users);
+    return {s.indptr, s.indices, s.data, v.own, v.ld_own, v.own_bias, users ? train.rows : train.cols, v.partner, v.ld_partner,
+            v.partner_bias, users ? train.cols : train.rows, m.n_factors, m.global_bias, alpha, users ? h.P_reg : h.Q_reg,
+            users ? h.user_bias_reg : h.item_bias_reg, h.learning_rate};
 }
 
 void lmf_ensure_state(DeviceModel &m) {  // allocated zeroed by the first logistic call
@@ -609,9 +615,7 @@ void lmf_ensure_state(DeviceModel &m) {  // allocated zeroed by the first logist
 
 int DeviceModel::lmf(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, hipStream_t stream) {
     lmf_check("cu2rec_model_lmf", train, h, alpha, &side);
-    require_device();
-    check_faults();
-    finish_swap();
+    enter(*this);
     lmf_ensure_state(*this);
     const bool users = side == CU2REC_SIDE_USERS;
     const LmfProblem p = lmf_problem(*this, train, h, alpha, users, stream);
@@ -624,9 +628,7 @@ int DeviceModel::lmf(const DeviceCsr &train, const cu2rec_hyper &h, float alpha,
 void DeviceModel::lmf_gradient(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, int side, float *grad_out, float *bias_grad_out,
                                hipStream_t stream) {
     lmf_check("cu2rec_model_lmf_gradient", train, h, alpha, &side);
-    require_device();
-    check_faults();
-    finish_swap();
+    enter(*this);
     const LmfProblem p = lmf_problem(*this, train, h, alpha, side == CU2REC_SIDE_USERS, stream);
     if (p.n_own == 0) return;
     cu2rec::lmf_gradient(lmf_st, p, stream);
@@ -641,9 +643,7 @@ void DeviceModel::lmf_gradient(const DeviceCsr &train, const cu2rec_hyper &h, fl
 
 double DeviceModel::lmf_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream) {
     lmf_check("cu2rec_model_lmf_objective", train, h, alpha, nullptr);
-    require_device();
-    check_faults();
-    finish_swap();
+    enter(*this);
     const LmfProblem p = lmf_problem(*this, train, h, alpha, true, stream);
     const double dense = lmf_dense_objective(lmf_st, p, stream);
     double s[5];
@@ -966,40 +966,34 @@ int cu2rec_model_sgd(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hype
     });
 }
 
-int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *unsolved) {
+// the four ALS half-step entry points: the null check (and, cg: the step count's) under the entry's own name, then the half-step
+static int als_entry(const char *fn, AlsKind kind, cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha,
+                     int side, bool cg, int cg_steps, int *unsolved) {
     return guarded([&] {
-        require(m && train && hyper, "cu2rec_model_als: null argument");
-        const int n = m->impl.als(train->impl, *hyper, side, nullptr);
+        Need{fn}(m && train && hyper, CU2REC_EINVAL, ": null argument");
+        if (cg) require_cg_steps(fn, cg_steps);
+        const int n = kind == AlsKind::Implicit ? m->impl.ials(train->impl, *hyper, alpha, side, nullptr, cg ? cg_steps : 0)
+                                                : m->impl.als(train->impl, *hyper, side, nullptr, cg ? cg_steps : 0);
         if (unsolved) *unsolved = n;
     });
 }
 
+int cu2rec_model_als(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *unsolved) {
+    return als_entry("cu2rec_model_als", AlsKind::Explicit, m, train, hyper, 0.f, side, false, 0, unsolved);
+}
+
 int cu2rec_model_als_cg(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int cg_steps, int *unsolved) {
-    return guarded([&] {
-        require(m && train && hyper, "cu2rec_model_als_cg: null argument");
-        require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_model_als_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
-        const int n = m->impl.als(train->impl, *hyper, side, nullptr, cg_steps);
-        if (unsolved) *unsolved = n;
-    });
+    return als_entry("cu2rec_model_als_cg", AlsKind::Explicit, m, train, hyper, 0.f, side, true, cg_steps, unsolved);
 }
 
 int cu2rec_model_als_implicit(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
                               int *unsolved) {
-    return guarded([&] {
-        require(m && train && hyper, "cu2rec_model_als_implicit: null argument");
-        const int n = m->impl.ials(train->impl, *hyper, alpha, side, nullptr);
-        if (unsolved) *unsolved = n;
-    });
+    return als_entry("cu2rec_model_als_implicit", AlsKind::Implicit, m, train, hyper, alpha, side, false, 0, unsolved);
 }
 
 int cu2rec_model_als_implicit_cg(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, int side,
                                  int cg_steps, int *unsolved) {
-    return guarded([&] {
-        require(m && train && hyper, "cu2rec_model_als_implicit_cg: null argument");
-        require(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, "cu2rec_model_als_implicit_cg: cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
-        const int n = m->impl.ials(train->impl, *hyper, alpha, side, nullptr, cg_steps);
-        if (unsolved) *unsolved = n;
-    });
+    return als_entry("cu2rec_model_als_implicit_cg", AlsKind::Implicit, m, train, hyper, alpha, side, true, cg_steps, unsolved);
 }
 
 int cu2rec_model_implicit_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, float alpha, double *L) {

@@ -62,6 +62,11 @@ void loss(const RatingsRef &r, int nnz, const FactorsRef &m, float *errors_out, 
 
 void error_metrics(const float *errors, int n, void *workspace, float *mae, float *rmse, hipStream_t stream);
 
+// the step count of every conjugate-gradient entry point (cu2rec_model_als_cg, cu2rec_train_implicit_cg, ...), under the entry's name
+inline void require_cg_steps(const char *fn, int cg_steps) {
+    Need{fn}(cg_steps >= 1 && cg_steps <= CU2REC_ALS_CG_MAX_STEPS, CU2REC_EINVAL, ": cg_steps must be in [1, CU2REC_ALS_CG_MAX_STEPS]");
+}
+
 // Device CSR in the reference's layout (matrix.h:11-19): int32 indptr / indices, float32 data.
 struct DeviceCsr {
     DeviceCsr(int rows, int cols, int nnz, const int *h_indptr, const int *h_indices, const float *h_data);

@@ -20,7 +20,7 @@
 // double per lane, then per workgroup in thread order, the workgroups' partials added in block order on the host.
 //
 // SPARSE (lmf_sparse_kernel): one wavefront per own row gathers the row's entries in ascending stored order in the four groups of
-// 16 lanes x float4 of als_cg.hip's entry pass (column f a synthesised 1), accumulates w sigma(-s) [y | 1] per group, adds the four
+// 16 lanes x float4 of row_wave.hpp's ENTRY map (column f a synthesised 1), accumulates w sigma(-s) [y | 1] per group, adds the four
 // groups in group order and combines g = (sparse - dense) - reg x in place of the dense sums.
 //
 // STEP (lmf_step_kernel): one wavefront per row, element-wise float32: a' = a + g g, x' = x + (lr g) / sqrtf(a') where a' > 0.  A
@@ -35,6 +35,8 @@
 
 #include "kernels.hpp"
 #include "lmf.hpp"
+#include "objective_pass.hpp"
+#include "row_wave.hpp"
 #include "score_tile.hpp"
 
 namespace cu2rec {
@@ -52,12 +54,6 @@ __device__ __forceinline__ float lmf_sigmoid(float s) {
 }
 
 __device__ __forceinline__ double lmf_softplus(double s) { return fmax(s, 0.0) + log1p(exp(-fabs(s))); }
-
-// the wavefront's LDS traffic is its own: order it for the compiler and the memory model (als_cg.hip)
-__device__ __forceinline__ void lmf_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 // columns f .. 4 nslots - 1 of a staged [32][RS] tile become zeros (by the wavefront that staged it)
 __device__ __forceinline__ void zero_tail(float4 *tile, int RS, int nslots, int f, int lane) {
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(256) void lmf_dense_kernel(LmfDenseArgs a) {
     const float *yf = reinterpret_cast<const float *>(ytile);
     if (wave == 0) {
         stage_rows(xtile, a.X, a.ldx, own0, a.n_own, 0, a.nslots, RS, lane);
-        lmf_wave_sync();
+        wave_sync();
         zero_tail(xtile, RS, a.nslots, f, lane);
     }
     const bool own_ok = own0 + r < a.n_own;
@@ -115,11 +111,11 @@ __global__ __launch_bounds__(256) void lmf_dense_kernel(LmfDenseArgs a) {
         float pb[16];
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) pb[reg] = a.yb[min(part0 + acc_row(reg, h), a.n_partner - 1)];
-        lmf_wave_sync();  // the previous step's reads of this wavefront's tile are done
+        wave_sync();  // the previous step's reads of this wavefront's tile are done
         stage_rows(ytile, a.Y, a.ldy, part0, a.n_partner, 0, a.nslots, RS, lane);
-        lmf_wave_sync();
+        wave_sync();
         zero_tail(ytile, RS, a.nslots, f, lane);
-        lmf_wave_sync();
+        wave_sync();
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
@@ -183,23 +179,6 @@ struct LmfRowArgs {
     int *unchanged;
 };
 
-// columns c0 .. c0 + 3 of [y | 1 | 0 ...] for partner row idx: column F the synthesised 1, zeros after it, the padding floats never read
-__device__ __forceinline__ float4 lmf_load_y(const LmfProblem &p, int idx, int c0) {
-    const int F = p.n_factors;
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (c0 < F) {
-        v = *reinterpret_cast<const float4 *>(p.Y + static_cast<size_t>(idx) * p.ldy + c0);
-        if (c0 + 1 >= F) v.y = 0.f;
-        if (c0 + 2 >= F) v.z = 0.f;
-        if (c0 + 3 >= F) v.w = 0.f;
-    }
-    if (c0 == F) v.x = 1.f;
-    if (c0 + 1 == F) v.y = 1.f;
-    if (c0 + 2 == F) v.z = 1.f;
-    if (c0 + 3 == F) v.w = 1.f;
-    return v;
-}
-
 // E = ceil((f + 1) / 64) elements per lane: element i = lane + 64 k is factor i, element f the bias
 template <int E>
 __global__ __launch_bounds__(kRowThreads) void lmf_sparse_kernel(LmfRowArgs a) {
@@ -213,14 +192,14 @@ __global__ __launch_bounds__(kRowThreads) void lmf_sparse_kernel(LmfRowArgs a) {
         const int lo = p.indptr[row], hi = p.indptr[row + 1];
         const float *x = p.X + static_cast<size_t>(row) * p.ldx;
         float xr[E];
-        lmf_wave_sync();  // the previous row has read pv and part
+        wave_sync();  // the previous row has read pv and part
 #pragma unroll
         for (int k = 0; k < E; ++k) {
             const int c = lane + 64 * k;
             xr[k] = c < F ? x[c] : 0.f;
             pv[c] = xr[k];  // zero from F on: the synthesised 1 of column F adds an exact 0 to the dot product
         }
-        lmf_wave_sync();
+        wave_sync();
         const float base = p.global_bias + p.xb[row];
         float4 v[E], acc[E];
 #pragma unroll
@@ -237,40 +216,24 @@ __global__ __launch_bounds__(kRowThreads) void lmf_sparse_kernel(LmfRowArgs a) {
             const float b = p.yb[idx];
             float4 q[E];
 #pragma unroll
-            for (int k = 0; k < E; ++k) q[k] = lmf_load_y(p, idx, 4 * l16 + 64 * k);
-            float d = 0.f;
-#pragma unroll
-            for (int k = 0; k < E; ++k) {
-                d = fmaf(q[k].x, v[k].x, d);
-                d = fmaf(q[k].y, v[k].y, d);
-                d = fmaf(q[k].z, v[k].z, d);
-                d = fmaf(q[k].w, v[k].w, d);
-            }
-#pragma unroll
-            for (int m = 8; m > 0; m >>= 1) d = d + __shfl_xor(d, m, 16);
+            for (int k = 0; k < E; ++k) q[k] = load_partner4<true>(p.Y, p.ldy, F, idx, 4 * l16 + 64 * k);
+            const float d = group_dot4<E>(q, v);
             if (on) {
                 const float s = (base + b) + d;
                 const float c = w * lmf_sigmoid(-s);  // w (1 - sigma(s)), without the cancellation
 #pragma unroll
-                for (int k = 0; k < E; ++k) {
-                    acc[k].x = fmaf(c, q[k].x, acc[k].x);
-                    acc[k].y = fmaf(c, q[k].y, acc[k].y);
-                    acc[k].z = fmaf(c, q[k].z, acc[k].z);
-                    acc[k].w = fmaf(c, q[k].w, acc[k].w);
-                }
+                for (int k = 0; k < E; ++k) axpy4(c, q[k], acc[k]);
             }
         }
-#pragma unroll
-        for (int k = 0; k < E; ++k) *reinterpret_cast<float4 *>(part + g * FS + 4 * l16 + 64 * k) = acc[k];
-        lmf_wave_sync();
+        float t[E];
+        combine_groups<E>(acc, part, part + g * FS + 4 * l16, lane, t);
         float *gr = a.grad + static_cast<size_t>(row) * a.ldg;
 #pragma unroll
         for (int k = 0; k < E; ++k) {
             const int i = lane + 64 * k;
             if (i > F) continue;
-            const float t = ((part[i] + part[FS + i]) + part[2 * FS + i]) + part[3 * FS + i];
             const float xi = i < F ? xr[k] : p.xb[row];
-            gr[i] = (t - gr[i]) - (i < F ? p.reg : p.reg_bias) * xi;
+            gr[i] = (t[k] - gr[i]) - (i < F ? p.reg : p.reg_bias) * xi;
         }
     }
 }
@@ -314,22 +277,6 @@ __global__ __launch_bounds__(kRowThreads) void lmf_step_kernel(LmfRowArgs a) {
     }
 }
 
-constexpr int kObjThreads = 256, kObjGroup = 16, kObjMaxBlocks = 4096;
-
-// x . y over the first f floats of two rows, in double, by one 16-lane group; every lane returns the sum
-__device__ inline double lmf_group_dot(const float *x, const float *y, int f, int lane16) {
-    double d = 0.0;
-    for (int c0 = 4 * lane16; c0 < f; c0 += 4 * kObjGroup) {
-        const float4 a = *reinterpret_cast<const float4 *>(x + c0), b = *reinterpret_cast<const float4 *>(y + c0);
-        d += static_cast<double>(a.x) * static_cast<double>(b.x);
-        if (c0 + 1 < f) d += static_cast<double>(a.y) * static_cast<double>(b.y);
-        if (c0 + 2 < f) d += static_cast<double>(a.z) * static_cast<double>(b.z);
-        if (c0 + 3 < f) d += static_cast<double>(a.w) * static_cast<double>(b.w);
-    }
-    for (int m = kObjGroup / 2; m > 0; m >>= 1) d += __shfl_xor(d, m, kObjGroup);
-    return d;
-}
-
 // the entries' term and the four norms, a 16-lane group per entry / row, in double; partials[block][5]
 __global__ __launch_bounds__(kObjThreads) void lmf_objective_kernel(LmfProblem p, int nnz, double *__restrict__ partials) {
     __shared__ double red[5][kObjThreads];
@@ -337,21 +284,15 @@ __global__ __launch_bounds__(kObjThreads) void lmf_objective_kernel(LmfProblem p
     const int group = (blockIdx.x * kObjThreads + tid) / kObjGroup, groups = gridDim.x * (kObjThreads / kObjGroup);
     double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int k = group; k < nnz; k += groups) {
-        int lo = 0, hi = p.n_own;  // the last u with indptr[u] <= k
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (p.indptr[mid] <= k) lo = mid;
-            else hi = mid - 1;
-        }
-        const int i = p.indices[k];
-        const double dot = lmf_group_dot(p.X + static_cast<size_t>(lo) * p.ldx, p.Y + static_cast<size_t>(i) * p.ldy, p.n_factors, lane16);
-        const double sc = ((static_cast<double>(p.global_bias) + static_cast<double>(p.xb[lo])) + static_cast<double>(p.yb[i])) + dot;
+        const int u = row_of_entry(p.indptr, p.n_own, k), i = p.indices[k];
+        const double dot = group_dot(p.X + static_cast<size_t>(u) * p.ldx, p.Y + static_cast<size_t>(i) * p.ldy, p.n_factors, lane16);
+        const double sc = ((static_cast<double>(p.global_bias) + static_cast<double>(p.xb[u])) + static_cast<double>(p.yb[i])) + dot;
         const double w = static_cast<double>(p.alpha * p.data[k]);
         if (lane16 == 0) s[0] += w * (sc - lmf_softplus(sc));
     }
     for (int u = group; u < p.n_own; u += groups) {
         const float *x = p.X + static_cast<size_t>(u) * p.ldx;
-        const double n2 = lmf_group_dot(x, x, p.n_factors, lane16);
+        const double n2 = group_dot(x, x, p.n_factors, lane16);
         if (lane16 == 0) {
             s[1] += n2;
             s[2] += static_cast<double>(p.xb[u]) * static_cast<double>(p.xb[u]);
@@ -359,18 +300,13 @@ __global__ __launch_bounds__(kObjThreads) void lmf_objective_kernel(LmfProblem p
     }
     for (int i = group; i < p.n_partner; i += groups) {
         const float *y = p.Y + static_cast<size_t>(i) * p.ldy;
-        const double n2 = lmf_group_dot(y, y, p.n_factors, lane16);
+        const double n2 = group_dot(y, y, p.n_factors, lane16);
         if (lane16 == 0) {
             s[3] += n2;
             s[4] += static_cast<double>(p.yb[i]) * static_cast<double>(p.yb[i]);
         }
     }
-    for (int j = 0; j < 5; ++j) red[j][tid] = s[j];
-    for (int stride = kObjThreads / 2; stride > 0; stride >>= 1) {
-        __syncthreads();
-        if (tid < stride)
-            for (int j = 0; j < 5; ++j) red[j][tid] += red[j][tid + stride];
-    }
+    block_reduce(s, red);
     if (tid == 0)
         for (int j = 0; j < 5; ++j) partials[5 * blockIdx.x + j] = red[j][0];
 }
@@ -398,16 +334,6 @@ void launch_dense(const LmfDenseArgs &a, hipStream_t stream) {
 
 int row_grid(int rows) { return std::min((rows + kRowWaves - 1) / kRowWaves, kRowMaxBlocks); }
 
-template <class F>
-void dispatch_elems(int n_factors, F &&f) {  // E = ceil((f + 1) / 64): 1 .. 4 up to 252 factors
-    switch ((n_factors + 1 + 63) / 64) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        default: f(std::integral_constant<int, 4>{}); break;
-    }
-}
-
 }  // namespace
 
 void lmf_gradient(LmfState &st, const LmfProblem &p, hipStream_t stream) {
@@ -418,7 +344,7 @@ void lmf_gradient(LmfState &st, const LmfProblem &p, hipStream_t stream) {
     const LmfDenseArgs d = dense_args(st, p);
     dispatch_1_to_8(T, "cu2rec_model_lmf: n_factors above 252 is not supported", [&](auto tiles) { launch_dense<tiles(), false>(d, stream); });
     const LmfRowArgs a{p, st.grad.ptr, ldg, nullptr, nullptr, nullptr};
-    dispatch_elems(p.n_factors, [&](auto elems) {
+    dispatch_1_to_4(p.n_factors + 1, [&](auto elems) {
         hipLaunchKernelGGL((lmf_sparse_kernel<elems()>), dim3(row_grid(p.n_own)), dim3(kRowThreads), 0, stream, a);
     });
     CU2REC_HIP(hipGetLastError());
@@ -429,7 +355,7 @@ int lmf_step(LmfState &st, const LmfProblem &p, float *acc, float *acc_bias, hip
     if (!st.unchanged.ptr) st.unchanged.allocate(1);
     CU2REC_HIP(hipMemsetAsync(st.unchanged.ptr, 0, sizeof(int), stream));
     const LmfRowArgs a{p, st.grad.ptr, 32 * lmf_tiles(p.n_factors), acc, acc_bias, st.unchanged.ptr};
-    dispatch_elems(p.n_factors, [&](auto elems) {
+    dispatch_1_to_4(p.n_factors + 1, [&](auto elems) {
         hipLaunchKernelGGL((lmf_step_kernel<elems()>), dim3(row_grid(p.n_own)), dim3(kRowThreads), 0, stream, a);
     });
     CU2REC_HIP(hipGetLastError());
@@ -454,9 +380,7 @@ double lmf_dense_objective(LmfState &st, const LmfProblem &p, hipStream_t stream
 }
 
 void lmf_sparse_objective(LmfState &st, const LmfProblem &p, int nnz, double *out, hipStream_t stream) {
-    const size_t work = static_cast<size_t>(std::max(nnz, std::max(p.n_own, p.n_partner)));
-    const int per_block = (kObjThreads / kObjGroup) * 8;
-    const int blocks = static_cast<int>(std::min<size_t>(std::max<size_t>((work + per_block - 1) / per_block, 1), kObjMaxBlocks));
+    const int blocks = objective_blocks(static_cast<size_t>(std::max(nnz, std::max(p.n_own, p.n_partner))));
     if (st.partials.count < 5 * static_cast<size_t>(blocks)) st.partials.allocate(5 * static_cast<size_t>(blocks));
     hipLaunchKernelGGL(lmf_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, p, nnz, st.partials.ptr);
     CU2REC_HIP(hipGetLastError());

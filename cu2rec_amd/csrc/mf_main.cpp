@@ -45,6 +45,9 @@ namespace {
 
 bool g_mode_given = false;  // -m on the command line
 
+// what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf };
+
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
 int effective_mode(int mode, int n_factors) {
@@ -288,12 +291,11 @@ int main(int argc, char **argv) {
     int rank_k = 0;  // -k: 0 = no ranking line
     bool rank_given = false;
     float rank_threshold = -INFINITY;
-    bool implicit = false;  // -m ials: implicit-feedback ALS (cu2rec_train_implicit), not a cu2rec_sgd_mode
-    bool logistic = false;  // -m lmf: logistic matrix factorization (cu2rec_train_lmf)
+    Trainer trainer = Trainer::Sgd;
+    const char *trainer_name = "";  // -m's word, for a refusal
     float alpha = 40.f;     // -a: the weight per unit of r of -m ials (default 40) and -m lmf (default 1)
     bool alpha_given = false;
-    bool als_cg = false;    // -m alscg: explicit ALS by conjugate gradients (cu2rec_train_als_cg), -C steps or 3
-    bool cg_given = false;  // -C steps: -m ials by conjugate gradients (cu2rec_train_implicit_cg), or -m alscg's step count
+    bool cg_given = false;  // -C steps: -m ials by conjugate gradients (cu2rec_train_implicit_cg), or -m alscg's step count (default 3)
     long cg_steps = 0;
     int opt;
     while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:")) != -1) {
@@ -339,16 +341,18 @@ int main(int argc, char **argv) {
                 break;
             case 'm':
                 g_mode_given = true;
-                implicit = std::strcmp(optarg, "ials") == 0;
-                als_cg = std::strcmp(optarg, "alscg") == 0;
-                logistic = std::strcmp(optarg, "lmf") == 0;
-                mode = implicit || als_cg || logistic ? CU2REC_ALS
-                       : std::strcmp(optarg, "serial") == 0    ? CU2REC_SGD_SERIAL
-                       : std::strcmp(optarg, "ordered") == 0 ? CU2REC_SGD_ORDERED
-                       : std::strcmp(optarg, "pingpong") == 0 ? CU2REC_SGD_PINGPONG
+                trainer_name = optarg;
+                trainer = std::strcmp(optarg, "als") == 0     ? Trainer::Als
+                          : std::strcmp(optarg, "alscg") == 0 ? Trainer::AlsCg
+                          : std::strcmp(optarg, "ials") == 0  ? Trainer::Ials
+                          : std::strcmp(optarg, "lmf") == 0   ? Trainer::Lmf
+                                                              : Trainer::Sgd;
+                mode = trainer != Trainer::Sgd                  ? CU2REC_ALS
+                       : std::strcmp(optarg, "serial") == 0     ? CU2REC_SGD_SERIAL
+                       : std::strcmp(optarg, "ordered") == 0    ? CU2REC_SGD_ORDERED
+                       : std::strcmp(optarg, "pingpong") == 0   ? CU2REC_SGD_PINGPONG
                        : std::strcmp(optarg, "blocksolve") == 0 ? CU2REC_SGD_BLOCKSOLVE
-                       : std::strcmp(optarg, "als") == 0 ? CU2REC_ALS
-                                                             : CU2REC_SGD_HOGWILD;
+                                                                : CU2REC_SGD_HOGWILD;
                 break;
             default:
                 std::cout << "Unknown option.\n";  // mf.cu:27-29
@@ -371,23 +375,25 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -k is single-GPU only (not with -g)\n";
         return 1;
     }
-    if (cg_given && (!(implicit || als_cg) || cg_steps < 1 || cg_steps > CU2REC_ALS_CG_MAX_STEPS)) {  // before the GPU is touched
+    const bool takes_cg = trainer == Trainer::Ials || trainer == Trainer::AlsCg;
+    const bool takes_alpha = trainer == Trainer::Ials || trainer == Trainer::Lmf;
+    if (cg_given && (!takes_cg || cg_steps < 1 || cg_steps > CU2REC_ALS_CG_MAX_STEPS)) {  // before the GPU is touched
         std::cerr << "mf: -C needs -m ials or -m alscg and a step count between 1 and " << CU2REC_ALS_CG_MAX_STEPS << "\n" << usage;
         return 1;
     }
-    if (als_cg && !cg_given) cg_steps = 3;
-    if (logistic && gpus > 1) {  // before the GPU is touched
+    if (trainer == Trainer::AlsCg && !cg_given) cg_steps = 3;
+    if (trainer == Trainer::Lmf && gpus > 1) {  // before the GPU is touched
         std::cerr << "mf: -m lmf is single-GPU only (not with -g)\n" << usage;
         return 1;
     }
-    if (logistic && !alpha_given) alpha = 1.f;
-    if ((implicit || logistic) && !(std::isfinite(alpha) && alpha >= 0.f)) {
+    if (trainer == Trainer::Lmf && !alpha_given) alpha = 1.f;
+    if (takes_alpha && !(std::isfinite(alpha) && alpha >= 0.f)) {
         std::cerr << "mf: -a must be a finite number >= 0\n";
         return 1;
     }
     if (gpus > 1) {
-        if (mode == CU2REC_ALS) {
-            std::cerr << "mf: -m " << (implicit ? "ials" : als_cg ? "alscg" : "als") << " is single-GPU only (not with -g)\n";
+        if (trainer != Trainer::Sgd) {
+            std::cerr << "mf: -m " << trainer_name << " is single-GPU only (not with -g)\n";
             return 1;
         }
         if (mode == CU2REC_SGD_PINGPONG) {
@@ -417,15 +423,15 @@ int main(int argc, char **argv) {
         cu2rec::CsrHandle d_train(train), d_test(test);
         cu2rec::ModelHandle model(train.rows, train.cols, cfg.n_factors, train.global_bias);
         std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
-        if (logistic)
+        if (trainer == Trainer::Lmf)
             cu2rec::check(cu2rec_train_lmf(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
-        else if (implicit && cg_given)
+        else if (trainer == Trainer::Ials && cg_given)
             cu2rec::check(cu2rec_train_implicit_cg(d_train.h, &cfg, model.h, alpha, static_cast<int>(cg_steps), 1, nullptr, nullptr));
-        else if (implicit)  // the test file is read (and checked) as always, but only -k looks at it
+        else if (trainer == Trainer::Ials)  // the test file is read (and checked) as always, but only -k looks at it
             cu2rec::check(cu2rec_train_implicit(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
-        else if (als_cg)
+        else if (trainer == Trainer::AlsCg)
             cu2rec::check(cu2rec_train_als_cg(d_train.h, d_test.h, &cfg, model.h, static_cast<int>(cg_steps), 1, losses.data(), nullptr));
-        else
+        else  // an SGD mode, or Trainer::Als as CU2REC_ALS
             cu2rec::check(cu2rec_train(d_train.h, d_test.h, &cfg, model.h, mode, 1, losses.data(), nullptr));  // mf.cu:61
 
         std::vector<float> P(static_cast<size_t>(train.rows) * cfg.n_factors), Q(static_cast<size_t>(train.cols) * cfg.n_factors);

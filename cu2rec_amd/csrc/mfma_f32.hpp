@@ -10,5 +10,10 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // row of the 32x32 accumulator tile held in register `reg` of a lane of half h (column = lane & 31)
 __device__ __forceinline__ int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+// its inverse: the register and half that hold `row` of the tile (acc_row(reg, h) == row)
+__device__ __forceinline__ void acc_reg_of_row(int row, int &reg, int &h) {
+    h = (row >> 2) & 1;
+    reg = (row & 3) + 4 * (row >> 3);
+}
 
 }  // namespace cu2rec

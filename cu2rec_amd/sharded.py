@@ -9,7 +9,7 @@ import os
 import numpy as np
 
 from . import api
-from ._lib import CommInfo, Config, Hyper, TrainStats, check, lib
+from ._lib import CommInfo, Config, TrainStats, check, lib
 
 MERGES = {"mean": 0, "weighted": 1, "sum": 2, "adaptive": 3}
 
@@ -88,7 +88,7 @@ class ShardJob:
         check(lib().cu2rec_shard_job_create(comm._h, model._h, train._h, int(user_offset), C.byref(opt), C.byref(self._h)))
 
     def run(self, hyper, seed, iter0, n_iters, mode=api.SGD_HOGWILD, update_items=True):
-        h = hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
+        h = api._hyper(hyper)
         check(lib().cu2rec_shard_job_run(self._h, C.byref(h), int(seed), int(iter0), int(n_iters), api._mode(mode),
                                          1 if update_items else 0))
 
