@@ -154,7 +154,11 @@ __global__ __launch_bounds__(256, 4) void bs_gram_kernel(SgdArgs a, BsIteration 
     // only as many as an iteration is expected to fill needs a way to do the rest when an iteration has more: as a stride loop around
     // gram_block it cost this kernel 55 spilled registers, as an out-of-line function a scratch frame -- 92 instead of 79 us per
     // iteration on the ML-20M shape either way (round 6, profiles/r06_launch_bounds.txt).  Phase 3 and the walk, whose kernels have the
-    // registers to spare, do stride: bs_update_kernel, sgd_ordered_kernel.)
+    // registers to spare, do stride: bs_update_kernel, sgd_ordered_kernel.
+    // An EXACT grid needs no "rest": round 8 had the plan kernel write every iteration's block counts, copied them to pinned memory in
+    // front of the window's "ready" event and QUERIED that event (no wait) at launch -- about 600 workgroups instead of 2,277.  This
+    // kernel's average did not move, 18.54 against 18.51 / 18.62 us for the parent's two runs (the surplus workgroups are not on its
+    // critical path), the benchmark step by 0.7 us with repeats 1.0 us apart: removed by the round's rule, profiles/r08_phase1_ab.txt.)
     gram_block(a, it, g, bs_smem);
 }
 

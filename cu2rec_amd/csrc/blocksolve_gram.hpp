@@ -3,7 +3,9 @@
 // (odd row stride: a column read is conflict free), 16 rows per wavefront, all of a lane's loads in flight together.
 // v_mfma_f32_32x32x2_f32 wants A[i = l & 31][kk = l >> 5] and B[kk = l >> 5][j = l & 31]: lane (k = l & 31, h = l >> 5)
 // feeds half h of the columns of row k, so for the two diagonal tiles (B = A^T) the SAME register is both operands.
-// The three Gram tiles are three wavefronts' work (one matrix pipe each).  With N = lr L in tiles [[N00, 0], [N10, N11]]
+// The three Gram tiles are FOUR wavefronts' work (one matrix pipe each: the waves of a workgroup sit on SIMD 0-3 in order): wavefronts
+// 0-2 contract the leading three quarters of the K range of one tile each, wavefront 3 the last quarter of all three, and the partial
+// tiles are added through LDS (gram_split).  With N = lr L in tiles [[N00, 0], [N10, N11]]
 // (strictly lower triangular diagonal tiles):
 //     M = (I + N)^-1 = [[M11, 0], [M21, M22]],  M11 = (I + N00)^-1,  M22 = (I + N11)^-1,  M21 = -M22 N10 M11.
 // The two triangular inversions run side by side in the two lane halves of wavefront 0 (lane = column, forward
@@ -29,6 +31,15 @@ __host__ __device__ inline size_t gram_lds_bytes(int nslots, bool with_cross_blo
     const size_t cross = with_cross_blocks ? 2 * gram_tile_float4s(nslots) * sizeof(float4) : 0;
     return own > cross ? own : cross;
 }
+
+// The K split of the Gram products: of the S0 = ceil(nslots / 2) float4 slots of each lane half, wavefronts 0-2 take [0, gram_split(S0))
+// and wavefront 3 takes the rest, for all three tiles -- 3 Sa = 3 (S0 - Sa) + at most 3.  Whole slots only; up to S0 = 3 wavefront 3's
+// range is empty (n_factors <= 24).  f = 100: S0 = 13, 40 dependent MFMAs on each of wavefronts 0-2 and 36 on wavefront 3 instead of 52 on three.
+// Measured (ML-20M shape, profiles/r08_phase1_ab.txt): bs_gram_kernel 18.6 -> 17.4 us on average, 17.6 -> 16.0 in the median iteration,
+// -1.2 us per benchmark step.  One more barrier and one LDS round trip of three tiles pay for it.
+// Registers: the kernel sits exactly at its 128 VGPRs (__launch_bounds__(256, 4)), no scratch; the three accumulator tiles are live in
+// every wavefront across the products -- whatever is added to this kernel has to win registers back first.
+__host__ __device__ inline int gram_split(int S0) { return (3 * S0 + 3) >> 2; }
 
 // One block of phase 1 (the body of bs_gram_kernel): its rows -> LDS, the Gram tiles, (I + N)^-1, the record.  Workgroup uniform.
 __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &it, int g, float4 *bs_smem) {
@@ -78,17 +89,37 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
     }
     __syncthreads();
     const int k = lane & 31, h = lane >> 5;
-    f32x16 acc;
+    const int S0 = (nslots + 1) >> 1;  // slots per lane half
+    const int Sa = gram_split(S0);
+    f32x16 acc, acc1, acc2;  // (acc1, acc2: wavefront 3's second and third partial tile)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    if (wave < 3) {  // 0: G00 -> N00, 1: G11 -> N11, 2: G10 -> N10 (rows: links 32.., columns: links 0..31)
+    for (int i = 0; i < 16; ++i) acc[i] = acc1[i] = acc2[i] = 0.f;
+    if (wave < 3) {  // 0: G00 -> N00, 1: G11 -> N11, 2: G10 -> N10 (rows: links 32.., columns: links 0..31); slots [0, Sa) of each lane half
         // D[i][j] = (A row i) . (B row j) lands in lane j = l & 31 at the rows i = acc_row(reg, h) of its registers.  The lane's own
         // link is the tile's ROW here, the registers' index its columns -- for the diagonal tiles by symmetry, for N10 because
         // A = links 0..31 and B = links 32..63: every lane then holds 4 x 4 CONTIGUOUS columns of its row and writes them with four
         // 16-byte LDS stores (round 4; it was sixteen scattered 4-byte stores behind two table reads each: 3.3 us of phase 1)
-        const int S0 = (nslots + 1) >> 1;  // slots per lane half
         const float4 *ra = tile + (wave == 1 ? kH + k : k) * RS, *rb = tile + (wave == 0 ? k : kH + k) * RS;
-        for (int c = 0; c < S0; c += 2) {
+        for (int c = 0; c < Sa; c += 2) {
+            float4 va[2], vb[2];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int slot = h * S0 + c + i;
+                const bool ok = c + i < Sa && slot < nslots;
+                const float4 t0 = ra[min(slot, nslots - 1)], t1 = rb[min(slot, nslots - 1)];
+                va[i] = ok ? t0 : zero4();
+                vb[i] = ok ? t1 : zero4();
+            }
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const float pa[4] = {va[i].x, va[i].y, va[i].z, va[i].w}, pb[4] = {vb[i].x, vb[i].y, vb[i].z, vb[i].w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[e], pb[e], acc, 0, 0, 0);
+            }
+        }
+    } else {  // slots [Sa, S0) of each lane half, all three tiles: one read of the two rows feeds three independent accumulators
+        const float4 *ra = tile + k * RS, *rb = tile + (kH + k) * RS;
+        for (int c = Sa; c < S0; c += 2) {
             float4 va[2], vb[2];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -102,11 +133,27 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
             for (int i = 0; i < 2; ++i) {
                 const float pa[4] = {va[i].x, va[i].y, va[i].z, va[i].w}, pb[4] = {vb[i].x, vb[i].y, vb[i].z, vb[i].w};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[e], pb[e], acc, 0, 0, 0);
+                for (int e = 0; e < 4; ++e) {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[e], pa[e], acc, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(pb[e], pb[e], acc1, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(pa[e], pb[e], acc2, 0, 0, 0);
+                }
             }
         }
     }
     __syncthreads();  // every wavefront is through with the rows: the tiles take their place
+    if (wave == 3) {
+        // the partial tiles, each element where the lane of wavefronts 0-2 that owns it will write its N: that lane reads it back and
+        // nobody else does
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            float *dst = Ns + k * kMS + 4 * h + 8 * m;
+            *reinterpret_cast<f32x4 *>(dst) = f32x4{acc[4 * m], acc[4 * m + 1], acc[4 * m + 2], acc[4 * m + 3]};
+            *reinterpret_cast<f32x4 *>(dst + kH * kMS) = f32x4{acc1[4 * m], acc1[4 * m + 1], acc1[4 * m + 2], acc1[4 * m + 3]};
+            *reinterpret_cast<f32x4 *>(dst + 2 * kH * kMS) = f32x4{acc2[4 * m], acc2[4 * m + 1], acc2[4 * m + 2], acc2[4 * m + 3]};
+        }
+    }
+    __syncthreads();
     if (wave < 3) {
         // N[K][J] = lr (c^d + a^d G[K][J]), d = K - 1 - J (links of the block), for J < K < n_valid; the powers by v_exp_f32 from
         // log2 a, log2 c (they multiply lr-sized terms only: an ulp of the power is 1e-9 of an entry)
@@ -117,18 +164,24 @@ __device__ __forceinline__ void gram_block(const SgdArgs &a, const BsIteration &
         float *dst = Ns + (wave * kH + k) * kMS + 4 * h;
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
+            const f32x4 part = *reinterpret_cast<const f32x4 *>(dst + 8 * m);  // wavefront 3's share of the sum
             f32x4 out;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int d = K - 1 - (J0 + 8 * m + e);
                 const float fd = static_cast<float>(d);
-                const float v = lr * (__builtin_amdgcn_exp2f(fd * it.log2c) + __builtin_amdgcn_exp2f(fd * it.log2a) * acc[4 * m + e]);
+                const float v = lr * (__builtin_amdgcn_exp2f(fd * it.log2c) + __builtin_amdgcn_exp2f(fd * it.log2a) * (acc[4 * m + e] + part[e]));
                 out[e] = d >= 0 && row_ok ? v : 0.f;
             }
             *reinterpret_cast<f32x4 *>(dst + 8 * m) = out;
         }
     }
     __syncthreads();
+    // (Tried and removed: each diagonal tile inverted in 16 x 16 quarters, one unit-triangular quarter of 15 steps per wavefront, the
+    // quarters below the diagonal and M21 -- one quarter per wavefront -- on v_mfma_f32_16x16x4_f32, 16-byte stores.  128 VGPRs, no
+    // scratch, same results; two more barriers, and without the row prefetch below, which spilled 27 registers there.  bs_gram_kernel
+    // 17.42 -> 17.50 us on average on top of the four-wavefront products, 18.50 -> 18.42 alone: inside the run-to-run spread either way,
+    // the benchmark step unchanged.  profiles/r08_phase1_ab.txt; the code: profiles/r08_gram_quartered_inverse.patch.)
     if (wave == 0) {
     // M11 (lanes 0-31) and M22 (lanes 32-63): lane = column, m[kk] = M[kk][column]
     float m[kH];
