@@ -146,6 +146,12 @@ SIGNATURES = {
     "cu2rec_model_lmf_objective": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_float, _dp]),
     "cu2rec_model_lmf_state": (C.c_int, [_P, _P, _P, _P, _P]),
     "cu2rec_model_lmf_reset": (C.c_int, [_P]),
+    "cu2rec_model_bpr": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_uint64, C.c_int, C.c_int, _ip]),
+    "cu2rec_model_bpr_gradient": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_uint64, C.c_int, C.c_int, _P, _P]),
+    "cu2rec_model_bpr_objective": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_uint64, C.c_int, _dp, C.POINTER(C.c_longlong),
+                                             C.POINTER(C.c_longlong)]),
+    "cu2rec_csr_bpr_negatives": (C.c_int, [_P, C.c_uint64, C.c_int, _P]),
+    "cu2rec_train_bpr": (C.c_int, [_P, C.POINTER(Config), _P, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_train_lmf": (C.c_int, [_P, C.POINTER(Config), _P, C.c_float, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_train": (C.c_int, [_P, _P, C.POINTER(Config), _P, C.c_int, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_shard_plan": (C.c_int, [C.c_int, C.c_int, _P]),

@@ -42,16 +42,17 @@ def _hyper(hyper):
     return hyper if isinstance(hyper, Hyper) else Hyper(*[float(x) for x in hyper])
 
 
-def _half_steps(side, sweeps, call):
+def _half_steps(side, sweeps, call, numbered=False):
     """`sweeps` times over the half-steps of side "users", "items" or "both" (users, then items): call(side code, byref(count))
-    is one library call's status; returns the counts summed."""
+    is one library call's status -- numbered: call(side code, byref(count), k), k = 0 .. sweeps - 1 the sweep; returns the counts
+    summed."""
     if side not in ALS_SIDES:
         raise ValueError("side must be one of %s, not %r" % (sorted(ALS_SIDES), side))
     total = 0
-    for _ in range(int(sweeps)):
+    for k in range(int(sweeps)):
         for s in ALS_SIDES[side]:
             n = C.c_int()
-            check(call(s, C.byref(n)))
+            check(call(s, C.byref(n), k) if numbered else call(s, C.byref(n)))
             total += n.value
     return total
 
@@ -269,6 +270,13 @@ class DeviceCSR:
         check(lib().cu2rec_csr_device_ptrs(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def bpr_negatives(self, seed, sweep):
+        """The negative item Model.bpr() pairs with every stored entry in sweep `sweep` (cu2rec_csr_bpr_negatives) -> int32 (nnz,),
+        -1 where all eight draws were items the row stores."""
+        neg = np.empty(self.nnz, np.int32)
+        check(lib().cu2rec_csr_bpr_negatives(self._h, int(seed), int(sweep), _ptr(neg)))
+        return neg
+
     def blocksolve_items(self):
         """cu2rec_csr_blocksolve_items: how many items the block-solve mode solves block-wise here (0: it is the ordered walk)."""
         n = lib().cu2rec_csr_blocksolve_items(self._h)
@@ -378,6 +386,38 @@ class Model:
     def lmf_reset(self):
         """Zeroes the AdaGrad accumulators of lmf()."""
         check(lib().cu2rec_model_lmf_reset(self._h))
+
+    def bpr(self, train, hyper, seed=42, sweep0=0, side="both", sweeps=1):
+        """Bayesian Personalized Ranking half-steps (cu2rec_model_bpr; Rendle et al. 2009, deterministic and full batch): sweep
+        sweep0 + k pairs every stored entry (u, i) with one negative item j drawn from the counter-based sampler (seed; see
+        DeviceCSR.bpr_negatives), a half-step is the gradient of sum ln sigma((ib_i - ib_j) + p_u . (q_i - q_j)) minus the
+        regularisers over those triples, then lmf()'s AdaGrad step at hyper's learning rate.  Stored values are not read; user
+        biases never move.  side and sweeps as in als().  The AdaGrad accumulators are lmf()'s (lmf_state, lmf_reset): the model
+        has one set, reset it between the two trainers.
+        Returns the number of rows left unchanged (a non-finite gradient or step), summed over the half-steps."""
+        h = _hyper(hyper)
+        return _half_steps(side, sweeps, lambda s, n, k: lib().cu2rec_model_bpr(self._h, train._h, C.byref(h), int(seed), int(sweep0) + k, s, n),
+                           numbered=True)
+
+    def bpr_gradient(self, train, hyper, seed, sweep, side):
+        """The gradient bpr() would step along for side "users" or "items" in sweep `sweep` (cu2rec_model_bpr_gradient) ->
+        (grad, bias_grad) shaped as lmf_gradient()'s; the users' bias_grad is all zeros.  The model and the accumulators are
+        untouched."""
+        h = _hyper(hyper)
+        if side not in ("users", "items"):
+            raise ValueError("side must be 'users' or 'items', not %r" % (side,))
+        n = train.rows if side == "users" else train.cols
+        grad, bias = np.empty((n, self.n_factors), np.float32), np.empty(n, np.float32)
+        check(lib().cu2rec_model_bpr_gradient(self._h, train._h, C.byref(h), int(seed), int(sweep), ALS_SIDES[side][0], _ptr(grad), _ptr(bias)))
+        return grad, bias
+
+    def bpr_objective(self, train, hyper, seed, sweep):
+        """The objective bpr() climbs over sweep `sweep`'s triples, at the model's current values (cu2rec_model_bpr_objective) ->
+        (L, n_triples, n_ordered); n_ordered / n_triples is the sampled AUC."""
+        h = _hyper(hyper)
+        L, n, m = C.c_double(), C.c_longlong(), C.c_longlong()
+        check(lib().cu2rec_model_bpr_objective(self._h, train._h, C.byref(h), int(seed), int(sweep), C.byref(L), C.byref(n), C.byref(m)))
+        return L.value, n.value, m.value
 
     def loss(self, ratings):
         """calculate_loss_gpu + get_error_metrics_gpu (loss.cu:40-49,195-200) -> dict(mae, rmse, sum_abs, sum_sq)."""
@@ -496,7 +536,8 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     returned is the objective at the checked sweeps, float64, NaN elsewhere; solver="cg" runs the sweeps with cg_steps conjugate-gradient
     steps per row, cu2rec_train_implicit_cg; with mode "als" it is cu2rec_train_als_cg -- solver and cg_steps are read in these two modes
     only); "lmf" by logistic matrix factorization (cu2rec_train_lmf: like "ials", test_matrix may be None and the third element is the
-    log-posterior at the checked sweeps; cfg.learning_rate is AdaGrad's and does not decay).  alpha None is 40.0 for "ials" and 1.0 for
+    log-posterior at the checked sweeps; cfg.learning_rate is AdaGrad's and does not decay); "bpr" by Bayesian Personalized Ranking
+    (cu2rec_train_bpr: like "lmf", with cfg.seed drawing the negatives and no alpha).  alpha None is 40.0 for "ials" and 1.0 for
     "lmf", where the weight multiplies a log-odds gradient and 40 x a 5-star rating saturates it.
     train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
@@ -511,7 +552,10 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     gb = tr.host.global_bias if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
     stats = TrainStats()
-    if mode == "lmf":
+    if mode == "bpr":
+        losses = np.empty(max(cfg.total_iterations, 1), np.float64)
+        check(lib().cu2rec_train_bpr(tr._h, C.byref(cfg), model._h, 1 if verbose else 0, _ptr(losses), C.byref(stats)))
+    elif mode == "lmf":
         losses = np.empty(max(cfg.total_iterations, 1), np.float64)
         check(lib().cu2rec_train_lmf(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses), C.byref(stats)))
     elif mode == "ials":

@@ -517,12 +517,14 @@ void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, con
     c.t_indptr.allocate(static_cast<size_t>(cols) + 1);
     c.t_indices.allocate(std::max(nnz, 1));
     c.t_data.allocate(std::max(nnz, 1));
+    c.t_pos.allocate(std::max(nnz, 1));
     if (nnz == 0) {
         CU2REC_HIP(hipMemsetAsync(c.t_indptr.ptr, 0, (static_cast<size_t>(cols) + 1) * sizeof(int), stream));
         CU2REC_HIP(hipStreamSynchronize(stream));
         return;
     }
-    DeviceBuffer<int> row_of(nnz), pos(nnz), pos_sorted(nnz);
+    DeviceBuffer<int> row_of(nnz), pos(nnz);
+    int *pos_sorted = c.t_pos.ptr;  // kept: the user-major position of every item-major one
     DeviceBuffer<unsigned> items_sorted(nnz);
     const int threads = 256, blocks = static_cast<int>(std::min<size_t>((static_cast<size_t>(nnz) + threads - 1) / threads, 8192));
     hipLaunchKernelGGL(als_row_of_kernel, dim3(blocks), dim3(threads), 0, stream, indptr, rows, nnz, row_of.ptr, pos.ptr);
@@ -532,11 +534,11 @@ void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, con
     // LSD radix sort: a chain of stable counting sorts, so rating positions (users ascending) keep their order within an item
     size_t temp_bytes = 0;
     const unsigned *keys_in = reinterpret_cast<const unsigned *>(indices);
-    CU2REC_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted.ptr, nnz, 0u, bits, stream));
+    CU2REC_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted, nnz, 0u, bits, stream));
     DeviceBuffer<unsigned char> temp(temp_bytes + 16);
-    CU2REC_HIP(rocprim::radix_sort_pairs(temp.ptr, temp_bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted.ptr, nnz, 0u, bits, stream));
+    CU2REC_HIP(rocprim::radix_sort_pairs(temp.ptr, temp_bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted, nnz, 0u, bits, stream));
     const int tblocks = static_cast<int>(std::min<size_t>((static_cast<size_t>(std::max(nnz, cols + 1)) + threads - 1) / threads, 8192));
-    hipLaunchKernelGGL(als_transpose_kernel, dim3(tblocks), dim3(threads), 0, stream, items_sorted.ptr, pos_sorted.ptr, row_of.ptr,
+    hipLaunchKernelGGL(als_transpose_kernel, dim3(tblocks), dim3(threads), 0, stream, items_sorted.ptr, pos_sorted, row_of.ptr,
                        data, nnz, cols, c.t_indptr.ptr, c.t_indices.ptr, c.t_data.ptr);
     CU2REC_HIP(hipGetLastError());
     CU2REC_HIP(hipStreamSynchronize(stream));  // before the temporaries are freed

@@ -57,6 +57,7 @@ struct AlsCache {
     bool users_ready = false, items_ready = false;
     DeviceBuffer<int> t_indptr, t_indices;
     DeviceBuffer<float> t_data;
+    DeviceBuffer<int> t_pos;  // item-major position -> the entry's position in the user-major CSR (the sort's own values, kept)
     DeviceBuffer<float> workspace;  // the partial Grams of one batch of long rows, kAlsWorkspaceBytes at most
     DeviceBuffer<int> unsolved;
     // implicit feedback: X^T X of the partner side (and of the other side, for the objective) in the accumulator layout

@@ -652,6 +652,85 @@ double DeviceModel::lmf_objective(const DeviceCsr &train, const cu2rec_hyper &h,
                                    static_cast<double>(h.Q_reg) * s[3] + static_cast<double>(h.item_bias_reg) * s[4]);
 }
 
+// Bayesian Personalized Ranking (include/cu2rec_amd.h: cu2rec_model_bpr).  The logistic calls' checks with their codes, and the sweep.
+void DeviceModel::bpr_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, const int *side, long long sweep) const {
+    const Need need{fn};
+    need(!side || is_side(*side), CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    for (float reg : {h.P_reg, h.Q_reg, h.user_bias_reg, h.item_bias_reg})
+        need(finite_at_least(reg, 0.f), CU2REC_EINVAL, ": every regulariser must be finite and >= 0");
+    need(std::isfinite(h.learning_rate) && h.learning_rate > 0.f, CU2REC_EINVAL, ": learning_rate must be finite and > 0");
+    need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": entries exceed the model's shape");
+    need(sweep >= 0 && sweep < kBprMaxSweep, CU2REC_EINVAL, ": sweep must be in [0, 2^29)");
+    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
+}
+
+namespace {
+// the kernels' view; items: with the item-major view cached on the CSR by the ALS calls
+BprProblem bpr_problem(DeviceModel &m, const DeviceCsr &train, const cu2rec_hyper &h, bool items, hipStream_t stream) {
+    BprProblem p{train.indptr.ptr, train.indices.ptr, train.rows, train.cols, train.nnz, nullptr, nullptr, nullptr, m.P.ptr, m.ld,
+                 m.Q.ptr, m.ldq, m.item_bias.ptr, m.n_factors, h.P_reg, h.Q_reg, h.item_bias_reg};
+    if (items) {
+        const AlsSide &s = als_side(train, false, stream);
+        p.t_indptr = s.indptr;
+        p.t_indices = s.indices;
+        p.t_pos = train.als->t_pos.ptr;
+    }
+    if (!train.bpr) train.bpr.reset(new BprCache);
+    return p;
+}
+
+// st.grad = the gradient of `side` over (seed, sweep)'s triples, in lmf_step's layout
+void bpr_gradient_into(LmfState &st, const DeviceCsr &train, const BprProblem &p, uint64_t seed, int sweep, bool users, hipStream_t stream) {
+    const int ldg = 32 * lmf_tiles(p.n_factors);
+    const size_t need = static_cast<size_t>(std::max(users ? p.rows : p.cols, 1)) * ldg;
+    if (st.grad.count < need) st.grad.allocate(need);
+    bpr_negatives(*train.bpr, p, seed, sweep, stream);
+    (users ? bpr_user_gradient : bpr_item_gradient)(*train.bpr, p, st.grad.ptr, ldg, stream);
+}
+}  // namespace
+
+int DeviceModel::bpr(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, int side, hipStream_t stream) {
+    bpr_check("cu2rec_model_bpr", train, h, &side, sweep);
+    enter(*this);
+    lmf_ensure_state(*this);
+    const bool users = side == CU2REC_SIDE_USERS;
+    bpr_gradient_into(lmf_st, train, bpr_problem(*this, train, h, !users, stream), seed, sweep, users, stream);
+    const LmfProblem step = lmf_problem(*this, train, h, 0.f, users, stream);  // the rows that move, and the learning rate
+    const int unchanged = lmf_step(lmf_st, step, users ? lmf_st.aP.ptr : lmf_st.aQ.ptr, users ? lmf_st.a_ub.ptr : lmf_st.a_ib.ptr, stream);
+    other_in_sync = false;  // Q may have moved on without the ping-pong pair
+    return unchanged;
+}
+
+void DeviceModel::bpr_gradient(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, int side, float *grad_out,
+                               float *bias_grad_out, hipStream_t stream) {
+    bpr_check("cu2rec_model_bpr_gradient", train, h, &side, sweep);
+    enter(*this);
+    const bool users = side == CU2REC_SIDE_USERS;
+    const int n_own = users ? train.rows : train.cols;
+    if (n_own == 0) return;
+    bpr_gradient_into(lmf_st, train, bpr_problem(*this, train, h, !users, stream), seed, sweep, users, stream);
+    const size_t ldg = static_cast<size_t>(32) * lmf_tiles(n_factors) * sizeof(float);
+    CU2REC_HIP(hipStreamSynchronize(stream));
+    if (grad_out)
+        CU2REC_HIP(hipMemcpy2D(grad_out, static_cast<size_t>(n_factors) * sizeof(float), lmf_st.grad.ptr, ldg,
+                               static_cast<size_t>(n_factors) * sizeof(float), n_own, hipMemcpyDeviceToHost));
+    if (bias_grad_out)
+        CU2REC_HIP(hipMemcpy2D(bias_grad_out, sizeof(float), lmf_st.grad.ptr + n_factors, ldg, sizeof(float), n_own, hipMemcpyDeviceToHost));
+}
+
+double DeviceModel::bpr_objective(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, long long *n_triples,
+                                  long long *n_ordered, hipStream_t stream) {
+    bpr_check("cu2rec_model_bpr_objective", train, h, nullptr, sweep);
+    enter(*this);
+    const BprProblem p = bpr_problem(*this, train, h, false, stream);
+    bpr_negatives(*train.bpr, p, seed, sweep, stream);
+    double s[6];
+    cu2rec::bpr_objective(*train.bpr, p, s, stream);
+    if (n_triples) *n_triples = static_cast<long long>(s[4]);
+    if (n_ordered) *n_ordered = static_cast<long long>(s[5]);
+    return s[0] - 0.5 * (static_cast<double>(h.P_reg) * s[1] + static_cast<double>(h.Q_reg) * s[2] + static_cast<double>(h.item_bias_reg) * s[3]);
+}
+
 void DeviceModel::lmf_download_state(float *aP, float *aQ, float *a_ub, float *a_ib) {
     if (!lmf_st.aP.ptr) {
         if (aP) std::fill(aP, aP + static_cast<size_t>(rows) * n_factors, 0.f);
@@ -1023,6 +1102,46 @@ int cu2rec_model_lmf_objective(cu2rec_model *m, const cu2rec_csr *train, const c
     return guarded([&] {
         require(m && train && hyper && L, "cu2rec_model_lmf_objective: null argument");
         *L = m->impl.lmf_objective(train->impl, *hyper, alpha, nullptr);
+    });
+}
+
+int cu2rec_model_bpr(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, uint64_t seed, int sweep, int side,
+                     int *n_unchanged) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_bpr: null argument");
+        const int n = m->impl.bpr(train->impl, *hyper, seed, sweep, side, nullptr);
+        if (n_unchanged) *n_unchanged = n;
+    });
+}
+
+int cu2rec_model_bpr_gradient(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, uint64_t seed, int sweep, int side,
+                              float *grad_out, float *bias_grad_out) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_bpr_gradient: null argument");
+        m->impl.bpr_gradient(train->impl, *hyper, seed, sweep, side, grad_out, bias_grad_out, nullptr);
+    });
+}
+
+int cu2rec_model_bpr_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, uint64_t seed, int sweep, double *L,
+                               long long *n_triples, long long *n_ordered) {
+    return guarded([&] {
+        require(m && train && hyper && L, "cu2rec_model_bpr_objective: null argument");
+        *L = m->impl.bpr_objective(train->impl, *hyper, seed, sweep, n_triples, n_ordered, nullptr);
+    });
+}
+
+int cu2rec_csr_bpr_negatives(const cu2rec_csr *train, uint64_t seed, int sweep, int *neg_out) {
+    return guarded([&] {
+        require(train && neg_out, "cu2rec_csr_bpr_negatives: null argument");
+        Need{"cu2rec_csr_bpr_negatives"}(sweep >= 0 && sweep < kBprMaxSweep, CU2REC_EINVAL, ": sweep must be in [0, 2^29)");
+        const DeviceCsr &t = train->impl;
+        require_device();
+        if (!t.bpr) t.bpr.reset(new BprCache);
+        const BprProblem p{t.indptr.ptr, t.indices.ptr, t.rows, t.cols, t.nnz, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr,
+                           0, 0.f, 0.f, 0.f};
+        bpr_negatives(*t.bpr, p, seed, sweep, nullptr);
+        CU2REC_HIP(hipStreamSynchronize(nullptr));
+        if (t.nnz) t.bpr->neg.download(neg_out, t.nnz);
     });
 }
 

@@ -8,6 +8,7 @@
 #include <memory>
 
 #include "als.hpp"
+#include "bpr.hpp"
 #include "hip_check.hpp"
 #include "lmf.hpp"
 #include "ordered.hpp"
@@ -79,6 +80,7 @@ struct DeviceCsr {
     mutable std::unique_ptr<OrderedSchedule> schedule;  // created on first CU2REC_SGD_ORDERED use
     mutable DeviceBuffer<uint2> pairs;                   // sample array, created on first Hogwild use (SgdArgs::pairs)
     mutable std::unique_ptr<AlsCache> als;               // item-major view and row plans, created on first ALS use
+    mutable std::unique_ptr<BprCache> bpr;               // row-sorted items and the current sweep's negatives, created on first BPR use
 };
 
 // P, Q, biases on the device with padded rows (see include/cu2rec_amd.h "Device data layout").
@@ -112,6 +114,17 @@ struct DeviceModel {
     void lmf_reset();
     // the argument checks of the logistic calls (side may be null), before the device or the model is touched; fn names the caller
     void lmf_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, const int *side) const;
+    // one BPR half-step (bpr.hpp: the gradient over sweep `sweep`'s triples, then the logistic trainer's AdaGrad step on ITS
+    // accumulators); returns the rows left unchanged
+    int bpr(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, int side, hipStream_t stream);
+    // the same gradient to the host, as lmf_gradient; the model and the accumulators untouched
+    void bpr_gradient(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, int side, float *grad_out,
+                      float *bias_grad_out, hipStream_t stream);
+    // the BPR objective at the current model over sweep `sweep`'s triples, their number and the number with x_e > 0 (synchronises)
+    double bpr_objective(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, long long *n_triples,
+                         long long *n_ordered, hipStream_t stream);
+    // the argument checks of the BPR calls (side may be null), before the device or the model is touched; fn names the caller
+    void bpr_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, const int *side, long long sweep) const;
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
               hipStream_t stream) const;
     FactorsRef ref() const { return {P.ptr, ld, Q.ptr, ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors}; }

@@ -35,6 +35,7 @@
 
 #include "kernels.hpp"
 #include "lmf.hpp"
+#include "logistic.hpp"
 #include "objective_pass.hpp"
 #include "row_wave.hpp"
 #include "score_tile.hpp"
@@ -44,16 +45,6 @@ namespace cu2rec {
 namespace {
 
 constexpr int kLmfStep = 4 * kTile;  // partners scored per workgroup step
-constexpr int kRowThreads = 256, kRowWaves = kRowThreads / 64, kRowMaxBlocks = 8192;
-
-// never inf / inf: the exponential's argument is <= 0 on both branches.  NaN in, NaN out.
-__device__ __forceinline__ float lmf_sigmoid(float s) {
-    if (s >= 0.f) return 1.f / (1.f + expf(-s));
-    const float e = expf(s);
-    return e / (1.f + e);
-}
-
-__device__ __forceinline__ double lmf_softplus(double s) { return fmax(s, 0.0) + log1p(exp(-fabs(s))); }
 
 // columns f .. 4 nslots - 1 of a staged [32][RS] tile become zeros (by the wavefront that staged it)
 __device__ __forceinline__ void zero_tail(float4 *tile, int RS, int nslots, int f, int lane) {
@@ -331,8 +322,6 @@ void launch_dense(const LmfDenseArgs &a, hipStream_t stream) {
     hipLaunchKernelGGL((lmf_dense_kernel<T, Objective>), dim3((a.n_own + kTile - 1) / kTile), dim3(256), lds, stream, a);
     CU2REC_HIP(hipGetLastError());
 }
-
-int row_grid(int rows) { return std::min((rows + kRowWaves - 1) / kRowWaves, kRowMaxBlocks); }
 
 }  // namespace
 

@@ -2,7 +2,7 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
 //          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
@@ -16,6 +16,9 @@
 // `-m lmf` trains by logistic matrix factorization (cu2rec_train_lmf): total_iterations full-batch sweeps with AdaGrad at the config's
 // learning rate, -a alpha the weight per unit of r (default 1 here, not ials's 40); single GPU, no -C.  The AdaGrad accumulators
 // are not written out: a run started from the five files begins them at zero.
+// `-m bpr` trains by Bayesian Personalized Ranking (cu2rec_train_bpr): total_iterations deterministic full-batch sweeps over one
+// sampled negative per stored entry (the config's seed), AdaGrad at the config's learning rate; single GPU, no -a, no -C.  Like
+// `-m ials` and `-m lmf` it reads the test file only for -k.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -46,7 +49,7 @@ namespace {
 bool g_mode_given = false;  // -m on the command line
 
 // what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
-enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf };
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr };
 
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
@@ -279,7 +282,7 @@ int run_multi_gpu(int nranks, int mode, int sync_every, int merge, const std::st
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
                         "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
@@ -346,6 +349,7 @@ int main(int argc, char **argv) {
                           : std::strcmp(optarg, "alscg") == 0 ? Trainer::AlsCg
                           : std::strcmp(optarg, "ials") == 0  ? Trainer::Ials
                           : std::strcmp(optarg, "lmf") == 0   ? Trainer::Lmf
+                          : std::strcmp(optarg, "bpr") == 0   ? Trainer::Bpr
                                                               : Trainer::Sgd;
                 mode = trainer != Trainer::Sgd                  ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0     ? CU2REC_SGD_SERIAL
@@ -386,6 +390,10 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -m lmf is single-GPU only (not with -g)\n" << usage;
         return 1;
     }
+    if (trainer == Trainer::Bpr && (alpha_given || cg_given || gpus > 1)) {  // before the GPU is touched
+        std::cerr << "mf: -m bpr takes no -a and no -C, and is single-GPU only (not with -g)\n" << usage;
+        return 1;
+    }
     if (trainer == Trainer::Lmf && !alpha_given) alpha = 1.f;
     if (takes_alpha && !(std::isfinite(alpha) && alpha >= 0.f)) {
         std::cerr << "mf: -a must be a finite number >= 0\n";
@@ -423,7 +431,9 @@ int main(int argc, char **argv) {
         cu2rec::CsrHandle d_train(train), d_test(test);
         cu2rec::ModelHandle model(train.rows, train.cols, cfg.n_factors, train.global_bias);
         std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
-        if (trainer == Trainer::Lmf)
+        if (trainer == Trainer::Bpr)  // like -m ials: the test file is read, but only -k looks at it
+            cu2rec::check(cu2rec_train_bpr(d_train.h, &cfg, model.h, 1, nullptr, nullptr));
+        else if (trainer == Trainer::Lmf)
             cu2rec::check(cu2rec_train_lmf(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
         else if (trainer == Trainer::Ials && cg_given)
             cu2rec::check(cu2rec_train_implicit_cg(d_train.h, &cfg, model.h, alpha, static_cast<int>(cg_steps), 1, nullptr, nullptr));

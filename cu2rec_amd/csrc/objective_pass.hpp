@@ -1,5 +1,6 @@
-// The double-precision objective passes (als.hip: ials_objective_kernel; lmf.hip: lmf_objective_kernel): a 16-lane group per entry or
-// row, per-thread sums in double, one tree reduction per workgroup.  Every sum's order is a function of the grid alone.
+// The double-precision objective passes (als.hip: ials_objective_kernel; lmf.hip: lmf_objective_kernel; bpr.hip:
+// bpr_objective_kernel): a 16-lane group per entry or row, per-thread sums in double, one tree reduction per workgroup.  Every sum's
+// order is a function of the grid alone.
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,4 +1,5 @@
-// One wavefront per row: what the conjugate-gradient half-steps (als_cg.hip) and the logistic trainer's sparse pass (lmf.hip) share.
+// One wavefront per row: what the conjugate-gradient half-steps (als_cg.hip), the logistic trainer's sparse pass (lmf.hip) and the
+// pairwise-ranking trainer's gradient kernels (bpr.hip) share.
 //
 // Two lane <-> element maps of a row of up to 64 E floats.  OWNER: lane l holds elements l, l + 64, ... (E registers).  ENTRY: the
 // wavefront is four groups of 16 lanes, group g takes the row's entries e = g, g + 4, ... in ascending order, lane l16 of a group
@@ -9,9 +10,15 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <type_traits>
 
 namespace cu2rec {
+
+// the launch shape of the one-wavefront-per-row kernels of lmf.hip and bpr.hip: four rows per workgroup, the grid strides beyond
+// kRowMaxBlocks workgroups
+constexpr int kRowThreads = 256, kRowWaves = kRowThreads / 64, kRowMaxBlocks = 8192;
+inline int row_grid(int rows) { return std::min((rows + kRowWaves - 1) / kRowWaves, kRowMaxBlocks); }
 
 // the wavefront's LDS traffic is its own: order it for the compiler and the memory model, no instruction is needed beyond that
 __device__ __forceinline__ void wave_sync() {

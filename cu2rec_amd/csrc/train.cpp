@@ -11,14 +11,14 @@
 namespace cu2rec {
 
 namespace {
-// n sweeps of a full-batch trainer: the user half-step, then the item half-step unless the items are frozen.  half_step(side)
-// returns the rows it updated; so does this, summed
+// n sweeps of a full-batch trainer: the user half-step, then the item half-step unless the items are frozen.  half_step(side, k)
+// (k = 0 .. n - 1: the sweep) returns the rows it updated; so does this, summed
 template <class HalfStep>
 double sweeps(int n, bool items, HalfStep &&half_step) {
     double updated = 0.0;
     for (int k = 0; k < n; ++k) {
-        updated += half_step(CU2REC_SIDE_USERS);
-        if (items) updated += half_step(CU2REC_SIDE_ITEMS);
+        updated += half_step(CU2REC_SIDE_USERS, k);
+        if (items) updated += half_step(CU2REC_SIDE_ITEMS, k);
     }
     return updated;
 }
@@ -26,7 +26,8 @@ double sweeps(int n, bool items, HalfStep &&half_step) {
 // The trainers that watch an objective instead of a test set (cu2rec_train_implicit, cu2rec_train_lmf): the schedule of train()
 // with sweeps for the iterations and the objective for the loss.  There is no test set and the learning rate does not decay: the
 // schedule's own lines and its patience stay off; the objective's line (`label`) is printed here.
-// half_step(hyper, side, stream) returns the rows it updated, objective(hyper) the value at the current model.
+// half_step(hyper, side, stream, iteration) returns the rows it updated, objective(hyper, iteration) the value at the current model
+// (iteration: the sweep's number in cfg's count, the last one done for the objective).
 template <class HalfStep, class Objective>
 void train_by_objective(const char *label, cu2rec_config &cfg, bool verbose, double *objectives, cu2rec_train_stats *stats,
                         HalfStep &&half_step, Objective &&objective) {
@@ -35,18 +36,20 @@ void train_by_objective(const char *label, cu2rec_config &cfg, bool verbose, dou
     cu2rec_hyper hyper{};
     double updated = 0.0;
     int done = 0;
+    uint64_t last = 0;
     cu2rec_train_stats st{};
     train_schedule(
         cfg, false, false, 0.0, nullptr, &st, nullptr,
-        [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
+        [&](const cu2rec_hyper &h, uint64_t first, int n, hipStream_t s) {
             hyper = h;
-            updated += sweeps(n, cfg.is_train, [&](int side) { return half_step(h, side, s); });
+            updated += sweeps(n, cfg.is_train, [&](int side, int k) { return half_step(h, side, s, first + static_cast<uint64_t>(k)); });
             done += n;
+            last = first + static_cast<uint64_t>(n) - 1;
         },
         [&](bool on_train, float *mae, float *rmse) {
             *mae = *rmse = 0.f;  // no residual metrics in these models
             if (!on_train) return;
-            const double L = objective(hyper);
+            const double L = objective(hyper, last);
             if (verbose) std::printf("TRAIN: Iteration %d GPU %s objective: %f\n", done, label, L);
             if (objectives) objectives[done - 1] = L;
         },
@@ -74,7 +77,7 @@ void train(const DeviceCsr &train_csr, const DeviceCsr &test_csr, cu2rec_config 
         train_schedule(
             cfg, verbose, true, 0.0, losses, stats, stream,
             [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
-                solved += sweeps(n, cfg.is_train, [&](int side) {
+                solved += sweeps(n, cfg.is_train, [&](int side, int) {
                     const int unsolved = model.als(train_csr, h, side, s, cg_steps);
                     return (side == CU2REC_SIDE_USERS ? train_csr.als->users : train_csr.als->items).rows_with_ratings - unsolved;
                 });
@@ -108,11 +111,11 @@ void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel 
     require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_implicit: bad iteration counts");
     train_by_objective(
         "implicit", cfg, verbose, objectives, stats,
-        [&](const cu2rec_hyper &h, int side, hipStream_t s) {
+        [&](const cu2rec_hyper &h, int side, hipStream_t s, uint64_t) {
             const int unsolved = model.ials(train_csr, h, alpha, side, s, cg_steps);
             return (side == CU2REC_SIDE_USERS ? train_csr.als->users : train_csr.als->items).rows_with_ratings - unsolved;
         },
-        [&](const cu2rec_hyper &h) { return model.implicit_objective(train_csr, h, alpha, nullptr); });
+        [&](const cu2rec_hyper &h, uint64_t) { return model.implicit_objective(train_csr, h, alpha, nullptr); });
 }
 
 // Logistic matrix factorization (include/cu2rec_amd.h: cu2rec_train_lmf): full-batch logistic sweeps and the log-posterior.  The
@@ -126,10 +129,30 @@ void train_lmf(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &mode
     model.lmf_reset();
     train_by_objective(
         "logistic", cfg, verbose, objectives, stats,
-        [&](const cu2rec_hyper &h, int side, hipStream_t s) {
+        [&](const cu2rec_hyper &h, int side, hipStream_t s, uint64_t) {
             return (side == CU2REC_SIDE_USERS ? train_csr.rows : train_csr.cols) - model.lmf(train_csr, h, alpha, side, s);
         },
-        [&](const cu2rec_hyper &h) { return model.lmf_objective(train_csr, h, alpha, nullptr); });
+        [&](const cu2rec_hyper &h, uint64_t) { return model.lmf_objective(train_csr, h, alpha, nullptr); });
+}
+
+// Bayesian Personalized Ranking (include/cu2rec_amd.h: cu2rec_train_bpr): sweep t is iteration t of cfg's count, its negatives drawn
+// with cfg.seed; the objective at a check is over the triples of the sweep just done.  The accumulators are the logistic trainer's.
+void train_bpr(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &model, bool verbose, double *objectives,
+               cu2rec_train_stats *stats) {
+    require(cfg.n_factors == model.n_factors, "cu2rec_train_bpr: cfg.n_factors differs from the model's");
+    require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_bpr: bad iteration counts");
+    const cu2rec_hyper hyper{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
+    require(cfg.cur_iterations >= 0, "cu2rec_train_bpr: bad iteration counts");
+    model.bpr_check("cu2rec_train_bpr", train_csr, hyper, nullptr,
+                    static_cast<long long>(cfg.cur_iterations) + std::max(cfg.total_iterations, 1) - 1);  // the last sweep's number
+    model.lmf_reset();
+    const uint64_t seed = static_cast<uint64_t>(static_cast<uint32_t>(cfg.seed));
+    train_by_objective(
+        "BPR", cfg, verbose, objectives, stats,
+        [&](const cu2rec_hyper &h, int side, hipStream_t s, uint64_t t) {
+            return (side == CU2REC_SIDE_USERS ? train_csr.rows : train_csr.cols) - model.bpr(train_csr, h, seed, static_cast<int>(t), side, s);
+        },
+        [&](const cu2rec_hyper &h, uint64_t t) { return model.bpr_objective(train_csr, h, seed, static_cast<int>(t), nullptr, nullptr, nullptr); });
 }
 
 }  // namespace cu2rec
@@ -140,6 +163,15 @@ extern "C" int cu2rec_train_lmf(const cu2rec_csr *train, cu2rec_config *cfg, cu2
     return guarded([&] {
         require(train && cfg && model, "cu2rec_train_lmf: null argument");
         cu2rec::train_lmf(unwrap(train), *cfg, unwrap(model), alpha, verbose != 0, objectives, stats);
+    });
+}
+
+extern "C" int cu2rec_train_bpr(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, int verbose, double *objectives,
+                                cu2rec_train_stats *stats) {
+    using namespace cu2rec;
+    return guarded([&] {
+        require(train && cfg && model, "cu2rec_train_bpr: null argument");
+        cu2rec::train_bpr(unwrap(train), *cfg, unwrap(model), verbose != 0, objectives, stats);
     });
 }
 

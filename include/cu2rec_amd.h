@@ -594,6 +594,53 @@ int cu2rec_model_lmf_state(cu2rec_model *m, float *aP, float *aQ, float *a_ub, f
 int cu2rec_model_lmf_reset(cu2rec_model *m);
 
 /* ------------------------------------------------------------------------------------------
+ * Implicit feedback: Bayesian Personalized Ranking (Rendle, Freudenthaler, Gantner, Schmidt-Thieme: BPR: Bayesian Personalized
+ * Ranking from Implicit Feedback, 2009) in a deterministic, full-batch form.  U = train rows, I = train cols; entry e = (u, i) is
+ * the k-th stored entry of row u; stored values are not read; repeated pairs count separately.
+ * Negatives.  For sweep t and entry (u, k), up to 8 attempts a = 0 .. 7 draw
+ *   j = cu2rec_sampler_index(seed, u, ((uint64_t)(t * 8 + a) << 32) | k, 0, I)
+ * and the first j that row u does not store is the entry's negative j_e; if all eight are stored items the entry has no triple in
+ * this sweep (j_e = -1) and contributes nothing anywhere.  The draw depends on seed, u, k, t, I and the row's own set of items only.
+ * Rows may be unsorted and hold repeats: the membership test is exact (a binary search of a row-sorted copy of the indices, cached
+ * on the cu2rec_csr by the first BPR call, as the ALS calls cache the item-major view).  Both half-steps of a sweep use the same
+ * negatives.  With x_e = (item_bias[i] - item_bias[j_e]) + p_u . (q_i - q_j) -- the user bias and the global bias cancel -- the
+ * quantity to be MAXIMISED is
+ *   L = sum_triples ln sigma(x_e) - 1/2 P_reg sum_(u < U) |p_u|^2 - 1/2 Q_reg sum_(i < I) |q_i|^2 - 1/2 item_bias_reg sum_(i < I) ib_i^2
+ * (plain regularisers, as in cu2rec_model_als_implicit, not n * reg; user_bias_reg is checked and otherwise unused).
+ * CU2REC_SIDE_USERS: for every u < U,  g_u = sum_(triples of u) sigma(-x_e) (q_i - q_j) - P_reg p_u;  the user bias' gradient is a
+ * zero, and the step below leaves user_bias and its accumulator bit for bit as they were.
+ * CU2REC_SIDE_ITEMS: for every i < I, with c_e = sigma(-x_e) at the current values,
+ *   g_i  = sum_(e: item(e) = i) c_e p_u - sum_(e: j_e = i) c_e p_u - Q_reg q_i
+ *   gb_i = sum_(e: item(e) = i) c_e     - sum_(e: j_e = i) c_e     - item_bias_reg ib_i
+ * the positives first, in ascending position of the item-major view, then the negatives in ascending e (each dealt to four partial
+ * sums by position, added in order); an item that is never a positive and never a negative gets -reg x.
+ * Either side then takes cu2rec_model_lmf's AdaGrad step with its unchanged-row rule (any non-finite gradient value, new value or
+ * new accumulator of a row -- a user's bias counts as its row's -- leaves the row's bits and is counted in *n_unchanged, may be
+ * NULL) ON THE SAME ACCUMULATORS: the model has one set, which cu2rec_model_lmf_state / cu2rec_model_lmf_reset expose and both
+ * trainers move; reset them between the two.  Model rows past the CSR and the frozen side keep their bits.
+ * No float atomics, every sum's order is a function of positions alone: bit-identical run to run, and a user's gradient and
+ * negatives in a CSR where every other row is empty equal those among the others.
+ * CU2REC_EINVAL, all checked before the device or the model is touched: a null m / train / hyper, a bad side, any of the four
+ * regularisers not finite or < 0, learning_rate not finite or <= 0, a CSR whose rows or cols exceed the model's, sweep outside
+ * [0, 2^29).  n_factors > CU2REC_ALS_MAX_FACTORS: CU2REC_EUNSUPPORTED.  A CSR with cols == 0 or nnz == 0 is a valid problem
+ * without triples.  Single GPU.
+ * ---------------------------------------------------------------------------------------- */
+int cu2rec_model_bpr(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, uint64_t seed, int sweep, int side,
+                     int *n_unchanged);
+/* The gradient cu2rec_model_bpr would step along, to the host, shaped as cu2rec_model_lmf_gradient's (either may be NULL).  The
+ * model and the accumulators are untouched. */
+int cu2rec_model_bpr_gradient(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, uint64_t seed, int sweep, int side,
+                              float *grad_out, float *bias_grad_out);
+/* *L = the objective above at the model's current values over sweep `sweep`'s triples: ln sigma(x_e) = -softplus(-x_e) from scores
+ * in double, every sum in double with the workgroups' partial sums added in order.  *n_triples = the number of triples and
+ * *n_ordered = the number with x_e > 0 (either may be NULL): n_ordered / n_triples is the sampled AUC.  The same checks (no side),
+ * and L not NULL.  Reads the model only. */
+int cu2rec_model_bpr_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, uint64_t seed, int sweep, double *L,
+                               long long *n_triples, long long *n_ordered);
+/* neg_out[e] (host, nnz ints) = j_e of sweep `sweep`, or -1.  CU2REC_EINVAL: a null argument, sweep outside [0, 2^29). */
+int cu2rec_csr_bpr_negatives(const cu2rec_csr *train, uint64_t seed, int sweep, int *neg_out);
+
+/* ------------------------------------------------------------------------------------------
  * train() -- replaces both overloads of train (training.h:12-15, training.cu:21-217):
  * total_iterations iterations; loss on train and test when i == 0, (i+1) % check_error == 0
  * or last (training.cu:118) printed as "TRAIN: Iteration %d GPU MAE: %f RMSE: %f" / "TEST: ..."
@@ -639,6 +686,14 @@ int cu2rec_train_implicit_cg(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec
  * stored in objectives[i] (may be NULL; NaN elsewhere).  stats->updates = rows stepped (rows left unchanged are not counted).
  * cu2rec_model_lmf's checks with its codes, before the device or the model is touched. */
 int cu2rec_train_lmf(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose, double *objectives,
+                     cu2rec_train_stats *stats);
+/* BPR training: the accumulators (the logistic trainer's) are reset, then total_iterations sweeps of cu2rec_model_bpr -- the users,
+ * then the items when cfg->is_train -- with seed cfg->seed; sweep t is iteration t of cfg's count (cfg->cur_iterations + the
+ * iterations done), so the last one must be below 2^29.  The objective over the triples of the sweep just done is evaluated at
+ * cu2rec_train_implicit's cadence, printed as "TRAIN: Iteration %d GPU BPR objective: %f" when `verbose`, and stored in
+ * objectives[i] (may be NULL; NaN elsewhere).  No decay.  stats->updates = rows stepped.  cu2rec_model_bpr's checks with its codes,
+ * before the device or the model is touched. */
+int cu2rec_train_bpr(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, int verbose, double *objectives,
                      cu2rec_train_stats *stats);
 
 /* ------------------------------------------------------------------------------------------
