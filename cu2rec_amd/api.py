@@ -357,15 +357,19 @@ class Model:
         h = _hyper(hyper)
         return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_lmf(self._h, train._h, C.byref(h), float(alpha), s, n))
 
+    def _gradient_out(self, train, side):
+        """What lmf_gradient() and bpr_gradient() hand to the library for side "users" or "items" -> (its constant, grad, bias_grad)."""
+        if side not in ("users", "items"):
+            raise ValueError("side must be 'users' or 'items', not %r" % (side,))
+        n = train.rows if side == "users" else train.cols
+        return ALS_SIDES[side][0], np.empty((n, self.n_factors), np.float32), np.empty(n, np.float32)
+
     def lmf_gradient(self, train, hyper, alpha, side):
         """The gradient lmf() would step along for side "users" or "items" (cu2rec_model_lmf_gradient) -> (grad, bias_grad),
         float32 of shapes (n, n_factors) and (n,), n = train's rows or cols.  The model and the accumulators are untouched."""
         h = _hyper(hyper)
-        if side not in ("users", "items"):
-            raise ValueError("side must be 'users' or 'items', not %r" % (side,))
-        n = train.rows if side == "users" else train.cols
-        grad, bias = np.empty((n, self.n_factors), np.float32), np.empty(n, np.float32)
-        check(lib().cu2rec_model_lmf_gradient(self._h, train._h, C.byref(h), float(alpha), ALS_SIDES[side][0], _ptr(grad), _ptr(bias)))
+        s, grad, bias = self._gradient_out(train, side)
+        check(lib().cu2rec_model_lmf_gradient(self._h, train._h, C.byref(h), float(alpha), s, _ptr(grad), _ptr(bias)))
         return grad, bias
 
     def lmf_objective(self, train, hyper, alpha):
@@ -404,11 +408,8 @@ class Model:
         (grad, bias_grad) shaped as lmf_gradient()'s; the users' bias_grad is all zeros.  The model and the accumulators are
         untouched."""
         h = _hyper(hyper)
-        if side not in ("users", "items"):
-            raise ValueError("side must be 'users' or 'items', not %r" % (side,))
-        n = train.rows if side == "users" else train.cols
-        grad, bias = np.empty((n, self.n_factors), np.float32), np.empty(n, np.float32)
-        check(lib().cu2rec_model_bpr_gradient(self._h, train._h, C.byref(h), int(seed), int(sweep), ALS_SIDES[side][0], _ptr(grad), _ptr(bias)))
+        s, grad, bias = self._gradient_out(train, side)
+        check(lib().cu2rec_model_bpr_gradient(self._h, train._h, C.byref(h), int(seed), int(sweep), s, _ptr(grad), _ptr(bias)))
         return grad, bias
 
     def bpr_objective(self, train, hyper, seed, sweep):
@@ -552,14 +553,13 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     gb = tr.host.global_bias if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
     stats = TrainStats()
-    if mode == "bpr":
+    if mode in ("bpr", "lmf", "ials"):  # the objective-driven modes
         losses = np.empty(max(cfg.total_iterations, 1), np.float64)
+    if mode == "bpr":
         check(lib().cu2rec_train_bpr(tr._h, C.byref(cfg), model._h, 1 if verbose else 0, _ptr(losses), C.byref(stats)))
     elif mode == "lmf":
-        losses = np.empty(max(cfg.total_iterations, 1), np.float64)
         check(lib().cu2rec_train_lmf(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses), C.byref(stats)))
     elif mode == "ials":
-        losses = np.empty(max(cfg.total_iterations, 1), np.float64)
         if solver == "cg":
             check(lib().cu2rec_train_implicit_cg(tr._h, C.byref(cfg), model._h, float(alpha), int(cg_steps), 1 if verbose else 0,
                                                  _ptr(losses), C.byref(stats)))

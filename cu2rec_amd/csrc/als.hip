@@ -35,6 +35,7 @@
 #include "als.hpp"
 #include "kernels.hpp"
 #include "objective_pass.hpp"
+#include "rocprim_temp.hpp"
 #include "score_tile.hpp"
 
 namespace cu2rec {
@@ -499,15 +500,8 @@ __global__ void als_transpose_kernel(const unsigned *__restrict__ sorted_items, 
         t_indices[p] = row_of[k];
         t_data[p] = data[k];
     }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += stride) {  // first position of item i
-        int lo = 0, hi = nnz;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (sorted_items[mid] < static_cast<unsigned>(i)) lo = mid + 1;
-            else hi = mid;
-        }
-        t_indptr[i] = lo;
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += stride)  // first position of item i
+        t_indptr[i] = first_at_least(sorted_items, 0, nnz, static_cast<unsigned>(i));
 }
 
 }  // namespace
@@ -532,11 +526,11 @@ void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, con
     unsigned bits = 1;
     while (bits < 31 && (1u << bits) < static_cast<unsigned>(cols)) ++bits;
     // LSD radix sort: a chain of stable counting sorts, so rating positions (users ascending) keep their order within an item
-    size_t temp_bytes = 0;
     const unsigned *keys_in = reinterpret_cast<const unsigned *>(indices);
-    CU2REC_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted, nnz, 0u, bits, stream));
-    DeviceBuffer<unsigned char> temp(temp_bytes + 16);
-    CU2REC_HIP(rocprim::radix_sort_pairs(temp.ptr, temp_bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted, nnz, 0u, bits, stream));
+    DeviceBuffer<unsigned char> temp;
+    with_rocprim_temp(temp, [&](void *t, size_t &bytes) {
+        return rocprim::radix_sort_pairs(t, bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted, nnz, 0u, bits, stream);
+    });
     const int tblocks = static_cast<int>(std::min<size_t>((static_cast<size_t>(std::max(nnz, cols + 1)) + threads - 1) / threads, 8192));
     hipLaunchKernelGGL(als_transpose_kernel, dim3(tblocks), dim3(threads), 0, stream, items_sorted.ptr, pos_sorted, row_of.ptr,
                        data, nnz, cols, c.t_indptr.ptr, c.t_indices.ptr, c.t_data.ptr);

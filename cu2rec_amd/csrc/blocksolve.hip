@@ -218,7 +218,7 @@ void launch_solve_sw(const SgdArgs &a, const BsIteration &it, hipStream_t stream
 //      FIRST on one stream, satisfied by a signal kernel queued behind it on the other, bounded by 10 ms -- both directions.  Streams
 //      that share a hardware queue (GPU_MAX_HW_QUEUES=1), a tool that serialises dispatches, a tenant holding the CUs: the waiter times
 //      out, and the process uses events for good;
-//   4. a join that gives up mid-run (check_faults, device.cpp) switches the device to events for every later call, and says so in its
+//   4. a join that gives up mid-run (check_faults, device_runtime.cpp) switches the device to events for every later call, and says so in its
 //      error.  A wait inside a phase-2 workgroup that gives up (la_wait*: status 2, not 1) leaves the topology as it is.
 namespace {
 __global__ void bs_probe_wait_kernel(const unsigned *word, unsigned *result, unsigned long long ticks) {

@@ -39,7 +39,7 @@ enum { kSyC0 = 0, kSyC1 = 1, kSyE = 2, kSyG = 3, kSyLdP = 4, kSyLdR = 8, kSyR = 
 
 // Waits until reached() says the counters are there; bounded: gives up after 2 s (or as soon as another wait of the workgroup has) and sets
 // the workgroup's abort flag and the status word to 2 -- a wait inside one workgroup: the fork / join topology had no part in it
-// (check_faults, device.cpp).  The store is unconditional (a load in front of it costs the loader's hot loop its wait-count schedule): a
+// (check_faults, device_runtime.cpp).  The store is unconditional (a load in front of it costs the loader's hot loop its wait-count schedule): a
 // join that gave up earlier in the same call (1) is then reported as this wait.
 template <class Reached>
 __device__ __forceinline__ void la_wait_until(unsigned *sy, const BsIteration &it, Reached reached) {

@@ -19,11 +19,11 @@
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
-#include <vector>
 
 #include "bpr.hpp"
 #include "logistic.hpp"
 #include "objective_pass.hpp"
+#include "rocprim_temp.hpp"
 #include "row_wave.hpp"
 #include "sampler.hpp"
 
@@ -49,12 +49,7 @@ __global__ __launch_bounds__(kEntryThreads) void bpr_negatives_kernel(const int 
         for (uint32_t a = 0; a < static_cast<uint32_t>(kBprAttempts); ++a) {
             const uint64_t iteration = (static_cast<uint64_t>(sweep * kBprAttempts + a) << 32) | k;
             const int cand = sampler_index(seed, static_cast<uint64_t>(u), iteration, 0, cols);
-            int l = lo, h = hi;  // the first position of the row's ascending items that holds cand or more
-            while (l < h) {
-                const int mid = (l + h) >> 1;
-                if (sorted[mid] < cand) l = mid + 1;
-                else h = mid;
-            }
+            const int l = first_at_least(sorted, lo, hi, cand);  // in the row's ascending items
             if (l == hi || sorted[l] != cand) {
                 j = cand;
                 break;
@@ -69,18 +64,11 @@ __global__ __launch_bounds__(kEntryThreads) void bpr_iota_kernel(int *__restrict
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += gridDim.x * blockDim.x) iota[e] = e;
 }
 
-// n_indptr[i] = the first position of key_sorted that holds i or more, i = 0 .. cols (als_transpose_kernel's search)
+// n_indptr[i] = the first position of key_sorted that holds i or more, i = 0 .. cols
 __global__ __launch_bounds__(kEntryThreads) void bpr_indptr_kernel(const unsigned *__restrict__ key_sorted, int nnz, int cols,
                                                                    int *__restrict__ n_indptr) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += gridDim.x * blockDim.x) {
-        int lo = 0, hi = nnz;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (key_sorted[mid] < static_cast<unsigned>(i)) lo = mid + 1;
-            else hi = mid;
-        }
-        n_indptr[i] = lo;
-    }
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += gridDim.x * blockDim.x)
+        n_indptr[i] = first_at_least(key_sorted, 0, nnz, static_cast<unsigned>(i));
 }
 
 struct BprRowArgs {
@@ -246,10 +234,6 @@ unsigned key_bits(int top) {  // bits that hold every key in [0, top]
     return bits;
 }
 
-void ensure_temp(BprCache &c, size_t bytes) {
-    if (c.sort_temp.count < bytes + 16) c.sort_temp.allocate(bytes + 16);
-}
-
 // once per CSR: every row's items ascending (a segmented radix sort) and the buffers of its size
 void build(BprCache &c, const BprProblem &p, hipStream_t stream) {
     if (c.built) return;
@@ -267,12 +251,10 @@ void build(BprCache &c, const BprProblem &p, hipStream_t stream) {
         const unsigned bits = key_bits(std::max(p.cols - 1, 1));
         const unsigned *keys = reinterpret_cast<const unsigned *>(p.indices);
         unsigned *out = reinterpret_cast<unsigned *>(c.sorted.ptr);
-        size_t bytes = 0;
-        CU2REC_HIP(rocprim::segmented_radix_sort_keys(nullptr, bytes, keys, out, static_cast<unsigned>(p.nnz), static_cast<unsigned>(p.rows),
-                                                      p.indptr, p.indptr + 1, 0u, bits, stream));
-        ensure_temp(c, bytes);
-        CU2REC_HIP(rocprim::segmented_radix_sort_keys(c.sort_temp.ptr, bytes, keys, out, static_cast<unsigned>(p.nnz),
-                                                      static_cast<unsigned>(p.rows), p.indptr, p.indptr + 1, 0u, bits, stream));
+        with_rocprim_temp(c.sort_temp, [&](void *temp, size_t &bytes) {
+            return rocprim::segmented_radix_sort_keys(temp, bytes, keys, out, static_cast<unsigned>(p.nnz), static_cast<unsigned>(p.rows),
+                                                      p.indptr, p.indptr + 1, 0u, bits, stream);
+        });
         hipLaunchKernelGGL(bpr_iota_kernel, dim3(entry_grid(p.nnz)), dim3(kEntryThreads), 0, stream, c.iota.ptr, p.nnz);
         CU2REC_HIP(hipGetLastError());
     }
@@ -284,12 +266,10 @@ void regroup(BprCache &c, const BprProblem &p, hipStream_t stream) {
     if (c.grouped) return;
     if (p.nnz > 0) {
         const unsigned bits = key_bits(p.cols);  // -1 sorts as `cols`
-        size_t bytes = 0;
-        CU2REC_HIP(rocprim::radix_sort_pairs(nullptr, bytes, c.neg_key.ptr, c.key_sorted.ptr, c.iota.ptr, c.neg_e.ptr,
-                                             static_cast<size_t>(p.nnz), 0u, bits, stream));
-        ensure_temp(c, bytes);
-        CU2REC_HIP(rocprim::radix_sort_pairs(c.sort_temp.ptr, bytes, c.neg_key.ptr, c.key_sorted.ptr, c.iota.ptr, c.neg_e.ptr,
-                                             static_cast<size_t>(p.nnz), 0u, bits, stream));
+        with_rocprim_temp(c.sort_temp, [&](void *temp, size_t &bytes) {
+            return rocprim::radix_sort_pairs(temp, bytes, c.neg_key.ptr, c.key_sorted.ptr, c.iota.ptr, c.neg_e.ptr,
+                                             static_cast<size_t>(p.nnz), 0u, bits, stream);
+        });
     }
     hipLaunchKernelGGL(bpr_indptr_kernel, dim3(entry_grid(static_cast<size_t>(p.cols) + 1)), dim3(kEntryThreads), 0, stream,
                        c.key_sorted.ptr, p.nnz, p.cols, c.n_indptr.ptr);
@@ -339,17 +319,12 @@ void bpr_item_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, h
     CU2REC_HIP(hipGetLastError());
 }
 
-void bpr_objective(BprCache &c, const BprProblem &p, double *out, hipStream_t stream) {
+void bpr_objective(BprCache &c, const BprProblem &p, double (&out)[6], hipStream_t stream) {
     const int blocks = objective_blocks(static_cast<size_t>(std::max(p.nnz, std::max(p.rows, p.cols))));
     if (c.partials.count < 6 * static_cast<size_t>(blocks)) c.partials.allocate(6 * static_cast<size_t>(blocks));
     hipLaunchKernelGGL(bpr_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, p, c.neg.ptr, c.row_of.ptr, c.partials.ptr);
     CU2REC_HIP(hipGetLastError());
-    std::vector<double> part(6 * static_cast<size_t>(blocks));
-    CU2REC_HIP(hipMemcpyAsync(part.data(), c.partials.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    CU2REC_HIP(hipStreamSynchronize(stream));
-    for (int j = 0; j < 6; ++j) out[j] = 0.0;
-    for (int b = 0; b < blocks; ++b)  // block order
-        for (int j = 0; j < 6; ++j) out[j] += part[6 * b + j];
+    sum_block_partials(c.partials, blocks, out, stream);
 }
 
 }  // namespace cu2rec

@@ -54,6 +54,6 @@ void bpr_user_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, h
 void bpr_item_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, hipStream_t stream);
 // out[6] = {sum over triples of ln sigma(x_e), sum |p_u|^2, sum |q_i|^2, sum ib_i^2, triples, triples with x_e > 0}, in double
 // (synchronises).  Needs bpr_negatives
-void bpr_objective(BprCache &c, const BprProblem &p, double *out, hipStream_t stream);
+void bpr_objective(BprCache &c, const BprProblem &p, double (&out)[6], hipStream_t stream);
 
 }  // namespace cu2rec

@@ -6,6 +6,8 @@
 #include <cstdint>
 
 #include <memory>
+#include <optional>
+#include <utility>
 
 #include "als.hpp"
 #include "bpr.hpp"
@@ -18,7 +20,7 @@ struct cu2rec_model;
 
 namespace cu2rec {
 
-// The ratings and the model as the hot path passes them on: plain views, nothing owned.  The extern "C" wrappers (device.cpp) pack
+// The ratings and the model as the hot path passes them on: plain views, nothing owned.  The extern "C" wrappers (device_raw.cpp) pack
 // their loose parameters into these; an owned object hands out its own (DeviceCsr::ref, DeviceModel::ref).
 struct RatingsRef {
     const int *indptr, *indices;
@@ -35,6 +37,10 @@ struct FactorsRef {
     float global_bias;
     int n_factors;
 };
+
+// What a persistent or concurrent launch could not finish is reported at the next entry point, once: the words are cleared so that
+// the process can go on.  (device_runtime.cpp, beside device_runtime() of hip_check.hpp)
+void check_faults();
 
 // fills the launch argument block after validating shapes / alignment (shared by all SGD modes)
 SgdArgs make_sgd_args(const RatingsRef &r, const FactorsRef &m, int n_cols, const cu2rec_hyper &hyper, uint64_t seed,
@@ -112,8 +118,10 @@ struct DeviceModel {
     double lmf_objective(const DeviceCsr &train, const cu2rec_hyper &h, float alpha, hipStream_t stream);
     void lmf_download_state(float *aP, float *aQ, float *a_ub, float *a_ib);  // zeros before the first logistic call
     void lmf_reset();
-    // the argument checks of the logistic calls (side may be null), before the device or the model is touched; fn names the caller
-    void lmf_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, const int *side) const;
+    // the argument checks of the logistic and the BPR calls, before the device or the model is touched; fn names the caller.
+    // alpha (the logistic calls'), side and sweep (the BPR calls') are checked where given
+    void logistic_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, std::optional<float> alpha, std::optional<int> side,
+                        std::optional<long long> sweep) const;
     // one BPR half-step (bpr.hpp: the gradient over sweep `sweep`'s triples, then the logistic trainer's AdaGrad step on ITS
     // accumulators); returns the rows left unchanged
     int bpr(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, int side, hipStream_t stream);
@@ -123,8 +131,10 @@ struct DeviceModel {
     // the BPR objective at the current model over sweep `sweep`'s triples, their number and the number with x_e > 0 (synchronises)
     double bpr_objective(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, long long *n_triples,
                          long long *n_ordered, hipStream_t stream);
-    // the argument checks of the BPR calls (side may be null), before the device or the model is touched; fn names the caller
-    void bpr_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, const int *side, long long sweep) const;
+    // what the logistic and the BPR calls end in: lmf_st.grad's first n_own rows to the host (synchronises); the AdaGrad step from
+    // lmf_st.grad on the accumulators of p's side, which returns the rows left unchanged
+    void download_gradient(int n_own, float *grad_out, float *bias_grad_out, hipStream_t stream);
+    int adagrad_half_step(const LmfProblem &p, bool users, hipStream_t stream);
     void loss(const DeviceCsr &ratings, double *sum_abs, double *sum_sq, float *mae, float *rmse,
               hipStream_t stream) const;
     FactorsRef ref() const { return {P.ptr, ld, Q.ptr, ldq, user_bias.ptr, item_bias.ptr, global_bias, n_factors}; }
@@ -143,9 +153,29 @@ struct DeviceModel {
     float global_bias;
 };
 
+// padded device rows (stride ld) -> dense host rows (stride f)
+void download_padded(const DeviceBuffer<float> &src, float *host, int rows, int f, int ld);
+
 DeviceCsr &unwrap(cu2rec_csr *m);
 const DeviceCsr &unwrap(const cu2rec_csr *m);
 DeviceModel &unwrap(cu2rec_model *m);
 const DeviceModel &unwrap(const cu2rec_model *m);
 
 }  // namespace cu2rec
+
+// the C ABI's opaque handles
+struct cu2rec_schedule {
+    cu2rec::OrderedSchedule impl;
+    template <class... A>
+    explicit cu2rec_schedule(A &&...a) : impl(std::forward<A>(a)...) {}
+};
+struct cu2rec_csr {
+    cu2rec::DeviceCsr impl;
+    template <class... A>
+    explicit cu2rec_csr(A &&...a) : impl(std::forward<A>(a)...) {}
+};
+struct cu2rec_model {
+    cu2rec::DeviceModel impl;
+    template <class... A>
+    explicit cu2rec_model(A &&...a) : impl(std::forward<A>(a)...) {}
+};

@@ -46,7 +46,7 @@ inline void ensure_max_dynamic_lds(const void *kernel, int bytes = 160 * 1024) {
     done.insert({dev, kernel});
 }
 
-// What the launch paths keep per device (device.cpp), created on first use and never freed.  Bounded device-side waits that give
+// What the launch paths keep per device (device_runtime.cpp), created on first use and never freed.  Bounded device-side waits that give
 // up set a status word; the host copy is refreshed behind the launches (resident.hip: every resident launch; blocksolve.hip: the
 // end of every block-solve call) and check_faults() reports and clears it at the next entry point.
 struct DeviceRuntime {

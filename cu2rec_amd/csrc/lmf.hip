@@ -31,7 +31,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <vector>
 
 #include "kernels.hpp"
 #include "lmf.hpp"
@@ -360,25 +359,17 @@ double lmf_dense_objective(LmfState &st, const LmfProblem &p, hipStream_t stream
     if (st.partials.count < static_cast<size_t>(blocks)) st.partials.allocate(blocks);
     const LmfDenseArgs d = dense_args(st, p);
     launch_dense<1, true>(d, stream);  // no second product: nothing depends on T
-    std::vector<double> part(blocks);
-    CU2REC_HIP(hipMemcpyAsync(part.data(), st.partials.ptr, blocks * sizeof(double), hipMemcpyDeviceToHost, stream));
-    CU2REC_HIP(hipStreamSynchronize(stream));
-    double s = 0.0;
-    for (double v : part) s += v;  // block order
-    return s;
+    double s[1];
+    sum_block_partials(st.partials, blocks, s, stream);
+    return s[0];
 }
 
-void lmf_sparse_objective(LmfState &st, const LmfProblem &p, int nnz, double *out, hipStream_t stream) {
+void lmf_sparse_objective(LmfState &st, const LmfProblem &p, int nnz, double (&out)[5], hipStream_t stream) {
     const int blocks = objective_blocks(static_cast<size_t>(std::max(nnz, std::max(p.n_own, p.n_partner))));
     if (st.partials.count < 5 * static_cast<size_t>(blocks)) st.partials.allocate(5 * static_cast<size_t>(blocks));
     hipLaunchKernelGGL(lmf_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, p, nnz, st.partials.ptr);
     CU2REC_HIP(hipGetLastError());
-    std::vector<double> part(5 * static_cast<size_t>(blocks));
-    CU2REC_HIP(hipMemcpyAsync(part.data(), st.partials.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    CU2REC_HIP(hipStreamSynchronize(stream));
-    for (int j = 0; j < 5; ++j) out[j] = 0.0;
-    for (int b = 0; b < blocks; ++b)
-        for (int j = 0; j < 5; ++j) out[j] += part[5 * b + j];
+    sum_block_partials(st.partials, blocks, out, stream);
 }
 
 }  // namespace cu2rec

@@ -45,6 +45,6 @@ int lmf_step(LmfState &st, const LmfProblem &p, float *a, float *ab, hipStream_t
 double lmf_dense_objective(LmfState &st, const LmfProblem &p, hipStream_t stream);
 // out[5] = {sum over entries of w (s - softplus(s)), sum |x|^2, sum xb^2, sum |y|^2, sum yb^2}, in double; p is the user side's
 // view (synchronises)
-void lmf_sparse_objective(LmfState &st, const LmfProblem &p, int nnz, double *out, hipStream_t stream);
+void lmf_sparse_objective(LmfState &st, const LmfProblem &p, int nnz, double (&out)[5], hipStream_t stream);
 
 }  // namespace cu2rec

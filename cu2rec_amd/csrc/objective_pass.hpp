@@ -7,6 +7,9 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <vector>
+
+#include "hip_check.hpp"
 
 namespace cu2rec {
 
@@ -43,6 +46,17 @@ __device__ inline int row_of_entry(const int *indptr, int rows, int k) {
     return lo;
 }
 
+// the first position in sorted[lo, hi) (ascending) that holds key or more; hi where none does
+template <class T>
+__device__ inline int first_at_least(const T *sorted, int lo, int hi, T key) {
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (sorted[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // the workgroup's N sums, a fixed tree over its kObjThreads threads: red[j][0] holds sum j, for thread 0 to read
 template <int N>
 __device__ inline void block_reduce(const double (&s)[N], double (&red)[N][kObjThreads]) {
@@ -53,6 +67,17 @@ __device__ inline void block_reduce(const double (&s)[N], double (&red)[N][kObjT
         if (tid < stride)
             for (int j = 0; j < N; ++j) red[j][tid] += red[j][tid + stride];
     }
+}
+
+// partials[block][N], as thread 0 of every workgroup left them, added on the host in block order (synchronises)
+template <int N>
+void sum_block_partials(DeviceBuffer<double> &partials, int blocks, double (&out)[N], hipStream_t stream) {
+    std::vector<double> part(N * static_cast<size_t>(blocks));
+    CU2REC_HIP(hipMemcpyAsync(part.data(), partials.ptr, part.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    CU2REC_HIP(hipStreamSynchronize(stream));
+    for (int j = 0; j < N; ++j) out[j] = 0.0;
+    for (int b = 0; b < blocks; ++b)
+        for (int j = 0; j < N; ++j) out[j] += part[N * b + j];
 }
 
 }  // namespace cu2rec

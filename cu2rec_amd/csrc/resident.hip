@@ -35,7 +35,7 @@
 // write-backs per XCD queue behind each other.)  The barrier is split in two halves; the next iteration's sample
 // gathers and the acquire's L1 invalidate sit between them.  Every spin is bounded (wall clock): a grid that is
 // not co-resident ends with the status word set instead of hanging, and the host reports it
-// (check_faults, device.cpp).  Residency comes from the grid size alone: at most one workgroup per CU.
+// (check_faults, device_runtime.cpp).  Residency comes from the grid size alone: at most one workgroup per CU.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

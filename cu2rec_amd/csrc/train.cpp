@@ -125,7 +125,7 @@ void train_lmf(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &mode
     require(cfg.n_factors == model.n_factors, "cu2rec_train_lmf: cfg.n_factors differs from the model's");
     require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_lmf: bad iteration counts");
     const cu2rec_hyper hyper{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
-    model.lmf_check("cu2rec_train_lmf", train_csr, hyper, alpha, nullptr);
+    model.logistic_check("cu2rec_train_lmf", train_csr, hyper, alpha, {}, {});
     model.lmf_reset();
     train_by_objective(
         "logistic", cfg, verbose, objectives, stats,
@@ -143,8 +143,8 @@ void train_bpr(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &mode
     require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_bpr: bad iteration counts");
     const cu2rec_hyper hyper{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
     require(cfg.cur_iterations >= 0, "cu2rec_train_bpr: bad iteration counts");
-    model.bpr_check("cu2rec_train_bpr", train_csr, hyper, nullptr,
-                    static_cast<long long>(cfg.cur_iterations) + std::max(cfg.total_iterations, 1) - 1);  // the last sweep's number
+    model.logistic_check("cu2rec_train_bpr", train_csr, hyper, {}, {},
+                         static_cast<long long>(cfg.cur_iterations) + std::max(cfg.total_iterations, 1) - 1);  // the last sweep's number
     model.lmf_reset();
     const uint64_t seed = static_cast<uint64_t>(static_cast<uint32_t>(cfg.seed));
     train_by_objective(

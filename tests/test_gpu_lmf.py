@@ -242,6 +242,42 @@ def test_argument_checks_leave_everything_alone():
         model.lmf(d, case.hyper, side="rows")
 
 
+def test_of_two_failed_argument_checks_the_earlier_one_is_reported():
+    """The logistic calls check side, the regularisers, alpha, the learning rate, the shape and n_factors, in this order.  For every
+    two neighbours a call that fails both: the earlier one's status and text under the entry point's own name (the texts as the
+    library had them before the BPR calls shared the check), the model and the accumulators bit-unchanged.  A 3 x 4 CSR at f = 4;
+    the shape fails on a model of two users, n_factors on one of 253 factors."""
+    SIDE, REG, ALPHA, LR, SHAPE = (": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS", ": every regulariser must be finite and >= 0",
+                                   ": alpha must be finite and >= 0", ": learning_rate must be finite and > 0",
+                                   ": entries exceed the model's shape")
+    d = cu.DeviceCSR(api.HostCSR(np.array([0, 2, 2, 3]), np.array([0, 3, 1], np.int32), np.array([1.0, 2.0, 1.0], np.float32), 3, 4, 0.0))
+    L = lib()
+    good = (0.05, 0.1, 0.2, 0.3, 0.4)
+    model, two_users, two_users_253 = cu.Model(3, 4, 4, 0.0), cu.Model(2, 4, 4, 0.0), cu.Model(2, 4, 253, 0.0)
+    assert model.lmf(d, good, 1.0, "both") == 0  # accumulators that are not zeros
+    before = {m: (m.download(), m.lmf_state()) for m in (model, two_users, two_users_253)}
+
+    def refused(m, hyper, alpha, side, text):
+        h, out = cu.Hyper(*hyper), C.c_double()
+        cfg = api.default_config(total_iterations=1, n_factors=m.n_factors, learning_rate=hyper[0], P_reg=hyper[1], Q_reg=hyper[2],
+                                 user_bias_reg=hyper[3], item_bias_reg=hyper[4])
+        calls = [("cu2rec_model_lmf", lambda: L.cu2rec_model_lmf(m._h, d._h, C.byref(h), alpha, side, None)),
+                 ("cu2rec_model_lmf_gradient", lambda: L.cu2rec_model_lmf_gradient(m._h, d._h, C.byref(h), alpha, side, None, None))]
+        if side in (0, 1):  # the calls without a side
+            calls += [("cu2rec_model_lmf_objective", lambda: L.cu2rec_model_lmf_objective(m._h, d._h, C.byref(h), alpha, C.byref(out))),
+                      ("cu2rec_train_lmf", lambda: L.cu2rec_train_lmf(d._h, C.byref(cfg), m._h, alpha, 0, None, None))]
+        for fn, call in calls:
+            assert call() == EINVAL, fn
+            assert L.cu2rec_last_error().decode() == fn + text
+            assert _same_state(m.download(), before[m][0]) and _same_state(m.lmf_state(), before[m][1]), fn
+
+    refused(model, (0.05, 0.1, -0.2, 0.3, 0.4), 1.0, 2, SIDE)       # side, regularisers
+    refused(model, (0.05, 0.1, 0.2, np.nan, 0.4), -1.0, 0, REG)     # regularisers, alpha
+    refused(model, (0.0, 0.1, 0.2, 0.3, 0.4), np.inf, 1, ALPHA)     # alpha, learning rate
+    refused(two_users, (-0.05, 0.1, 0.2, 0.3, 0.4), 1.0, 0, LR)     # learning rate, shape
+    refused(two_users_253, good, 1.0, 1, SHAPE)                     # shape, n_factors
+
+
 # ---------------------------------------------------------------------------------------------------- sweeps on the fixture
 
 _RUN = {}
