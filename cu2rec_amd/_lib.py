@@ -171,6 +171,14 @@ SIGNATURES = {
     "cu2rec_train_sharded": (C.c_int, [_P, _P, C.POINTER(Config), C.c_int, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_csr_slice": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, _ip, _ip]),
     "cu2rec_item_update_rates": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "cu2rec_knn_create": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_int, C.POINTER(_P)]),
+    "cu2rec_knn_destroy": (None, [_P]),
+    "cu2rec_knn_info": (C.c_int, [_P, _ip, _ip, _ip]),
+    "cu2rec_knn_slice_items": (C.c_int, []),
+    "cu2rec_csr_knn_weights": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, _P]),
+    "cu2rec_knn_neighbors": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "cu2rec_knn_recommend": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "cu2rec_knn_rank_metrics": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.POINTER(RankMetrics), _P]),
 }
 
 _lib = None

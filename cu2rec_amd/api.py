@@ -23,6 +23,9 @@ SIDES = {"users": SIDE_USERS, "items": SIDE_ITEMS}
 METRICS = {"dot": SIM_DOT, "cosine": SIM_COSINE}
 MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "pingpong": SGD_PINGPONG,
          "blocksolve": SGD_BLOCKSOLVE, "als": ALS}
+KNN_COUNT, KNN_COSINE, KNN_TFIDF, KNN_BM25 = 0, 1, 2, 3
+KNN_WEIGHTINGS = {"count": KNN_COUNT, "cosine": KNN_COSINE, "tfidf": KNN_TFIDF, "bm25": KNN_BM25}
+KNN_WORKSPACE_BYTES = 64 << 20  # CU2REC_KNN_WORKSPACE_BYTES: the bound of the product's workspace per batch of queries
 ALS_SIDES = {"users": (SIDE_USERS,), "items": (SIDE_ITEMS,), "both": (SIDE_USERS, SIDE_ITEMS)}
 IALS_SOLVERS = ("cholesky", "cg")  # Model.als / Model.ials / train(mode="als" | "ials"): the exact solver, or conjugate-gradient steps per row
 ALS_CG_MAX_STEPS = 256             # CU2REC_ALS_CG_MAX_STEPS
@@ -277,6 +280,14 @@ class DeviceCSR:
         check(lib().cu2rec_csr_bpr_negatives(self._h, int(seed), int(sweep), _ptr(neg)))
         return neg
 
+    def knn_weights(self, weighting, k1=100.0, b=0.8):
+        """The weight ItemKNN gives every stored entry (cu2rec_csr_knn_weights) -> float32 (nnz,), in the CSR's own entry order.
+        weighting: "count", "cosine", "tfidf" or "bm25" (k1 and b are bm25's)."""
+        weighting = _choice(KNN_WEIGHTINGS, weighting, "weighting")
+        w = np.empty(self.nnz, np.float32)
+        check(lib().cu2rec_csr_knn_weights(self._h, weighting, float(k1), float(b), _ptr(w)))
+        return w
+
     def blocksolve_items(self):
         """cu2rec_csr_blocksolve_items: how many items the block-solve mode solves block-wise here (0: it is the ordered walk)."""
         n = lib().cu2rec_csr_blocksolve_items(self._h)
@@ -515,6 +526,64 @@ class Model:
         if self._h:
             lib().cu2rec_model_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ItemKNN:
+    """Item-based nearest-neighbour recommender (cu2rec_knn_*; include/cu2rec_amd.h): every stored entry of `train` is weighted
+    ("count", "cosine", "tfidf" or "bm25", the last with k1 and b), the similarity of two items is the sum of the weight products over
+    the users that store both, and every item keeps its `neighbours` best touched neighbours (1 .. 256).  No factors, no learning
+    rate, no seed; results are bit-identical run to run.  Rows may be unsorted; a row that stores a column twice is refused."""
+
+    def __init__(self, train, weighting="cosine", neighbours=20, k1=100.0, b=0.8):
+        self._h = None
+        code = _choice(KNN_WEIGHTINGS, weighting, "weighting")
+        self.weighting, self.items, self.neighbours = weighting, train.cols, int(neighbours)
+        h = C.c_void_p()
+        check(lib().cu2rec_knn_create(train._h, code, float(k1), float(b), int(neighbours), C.byref(h)))
+        self._h = h
+
+    def neighbors(self, ids=None, k=None):
+        """The k best neighbours of each listed item (cu2rec_knn_neighbors) -> (ids, sims), each (n, k); topk's order, ties and
+        -1 / NaN padding.  ids: item ids (duplicates allowed), or None for every item; k: at most `neighbours` (None: all)."""
+        k = self.neighbours if k is None else int(k)
+        q = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n = self.items if q is None else len(q)
+        out, sims = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_knn_neighbors(self._h, _ptr(q), int(n), k, _ptr(out), _ptr(sims)))
+        return out, sims
+
+    def recommend(self, history, exclude, k, users=None):
+        """The k best items for each listed row of `history` (cu2rec_knn_recommend) -> (items, scores), each (n, k): the row's raw
+        values pushed through the truncated neighbour lists, the candidates being the items some history item lists, outside row
+        u of `exclude` (DeviceCSR or None).  users: row ids of history (duplicates allowed), or None for every row.  1 <= k <= 256."""
+        k = int(k)
+        q = None if users is None else np.ascontiguousarray(users, dtype=np.int32).reshape(-1)
+        n = history.rows if q is None else len(q)
+        items, scores = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_knn_recommend(self._h, history._h, exclude._h if exclude is not None else None, _ptr(q), int(n), k,
+                                         _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def rank_metrics(self, history, test, k, exclude=None, threshold=None, per_user=False):
+        """Model.rank_metrics' figures over recommend()'s lists of every row of `history` (cu2rec_knn_rank_metrics)."""
+        out = RankMetrics()
+        per = np.empty((history.rows, 5), np.float64) if per_user else None
+        thr = -np.inf if threshold is None else float(threshold)
+        check(lib().cu2rec_knn_rank_metrics(self._h, history._h, exclude._h if exclude is not None else None, test._h, int(k), thr,
+                                            C.byref(out), _ptr(per)))
+        res = {name: getattr(out, name) for name, _ in RankMetrics._fields_}
+        return (res, per) if per_user else res
+
+    def close(self):
+        if self._h:
+            lib().cu2rec_knn_destroy(self._h)
+            self._h = None
 
     def __del__(self):
         try:

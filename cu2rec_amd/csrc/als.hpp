@@ -54,7 +54,8 @@ struct AlsSide {
 // time it is needed (a stable radix sort by item of the rating positions: users stay in ascending order within an item).
 struct AlsCache {
     AlsSide users, items;
-    bool users_ready = false, items_ready = false;
+    bool users_ready = false, items_ready = false;  // the side is planned (als_plan_side)
+    bool items_built = false;                        // the item-major view exists (ItemKNN reads it without a plan)
     DeviceBuffer<int> t_indptr, t_indices;
     DeviceBuffer<float> t_data;
     DeviceBuffer<int> t_pos;  // item-major position -> the entry's position in the user-major CSR (the sort's own values, kept)

@@ -76,4 +76,14 @@ struct ModelHandle {
     ~ModelHandle() { cu2rec_model_destroy(h); }
 };
 
+struct KnnHandle {
+    cu2rec_knn *h = nullptr;
+    KnnHandle(const CsrHandle &train, int weighting, float k1, float b, int neighbours) {
+        check(cu2rec_knn_create(train.h, weighting, k1, b, neighbours, &h));
+    }
+    KnnHandle(const KnnHandle &) = delete;
+    KnnHandle &operator=(const KnnHandle &) = delete;
+    ~KnnHandle() { cu2rec_knn_destroy(h); }
+};
+
 }  // namespace cu2rec

@@ -12,6 +12,7 @@
 #include "als.hpp"
 #include "bpr.hpp"
 #include "hip_check.hpp"
+#include "knn.hpp"
 #include "lmf.hpp"
 #include "ordered.hpp"
 
@@ -87,7 +88,15 @@ struct DeviceCsr {
     mutable DeviceBuffer<uint2> pairs;                   // sample array, created on first Hogwild use (SgdArgs::pairs)
     mutable std::unique_ptr<AlsCache> als;               // item-major view and row plans, created on first ALS use
     mutable std::unique_ptr<BprCache> bpr;               // row-sorted items and the current sweep's negatives, created on first BPR use
+    mutable std::unique_ptr<KnnRows> knn_rows;           // row-sorted (column, value) pairs, created on first ItemKNN use
 };
+
+// The rows one ALS half-step solves, as it reads them: the CSR itself for the users, its item-major view for the items -- built on
+// the device, and either side planned, the first time it is asked for (device_trainers.cpp).
+AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream);
+// The item-major view alone (c.items' indptr / indices / data and c.t_pos), built the first time it is asked for and shared with
+// als_side; the ALS row plan is left to the first ALS call.  What the ItemKNN build reads (knn.hip).
+AlsCache &item_major_view(const DeviceCsr &train, hipStream_t stream);
 
 // P, Q, biases on the device with padded rows (see include/cu2rec_amd.h "Device data layout").
 struct DeviceModel {

@@ -8,9 +8,23 @@
 
 namespace cu2rec {
 
-namespace {
-// The rows one ALS half-step solves, as it reads them: the CSR itself for the users, its item-major view for the items -- built on
-// the device, and either side planned, the first time it is asked for.
+// device.hpp: the item-major view alone, built on the device once per rating matrix; nothing is planned
+AlsCache &item_major_view(const DeviceCsr &train, hipStream_t stream) {
+    if (!train.als) train.als.reset(new AlsCache);
+    AlsCache &c = *train.als;
+    if (!c.items_built) {
+        als_build_transpose(c, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz, stream);
+        c.items.indptr = c.t_indptr.ptr;
+        c.items.indices = c.t_indices.ptr;
+        c.items.data = c.t_data.ptr;
+        c.items.rows = train.cols;
+        c.items.nnz = train.nnz;
+        c.items_built = true;
+    }
+    return c;
+}
+
+// device.hpp: the rows one ALS half-step solves, as it reads them
 AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream) {
     if (!train.als) train.als.reset(new AlsCache);
     AlsCache &c = *train.als;
@@ -26,19 +40,15 @@ AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream) {
         }
         return c.users;
     }
-    if (!c.items_ready) {  // the item-major view, built on the device once per rating matrix
-        als_build_transpose(c, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz, stream);
-        c.items.indptr = c.t_indptr.ptr;
-        c.items.indices = c.t_indices.ptr;
-        c.items.data = c.t_data.ptr;
-        c.items.rows = train.cols;
-        c.items.nnz = train.nnz;
+    if (!c.items_ready) {
+        item_major_view(train, stream);
         als_plan_side(c.items, stream);
         c.items_ready = true;
     }
     return c.items;
 }
 
+namespace {
 // One side of the model as a half-step sees it: the rows that move, and the frozen partner side.
 struct SideView {
     float *own, *own_bias, *partner, *partner_bias;

@@ -2,8 +2,8 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
-//          [-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
+//          [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
 // for bit).  `-m hogwild` opts into sgd.cu's own racy semantics (fastest, 1e-3 away from the sequential result while
@@ -19,6 +19,11 @@
 // `-m bpr` trains by Bayesian Personalized Ranking (cu2rec_train_bpr): total_iterations deterministic full-batch sweeps over one
 // sampled negative per stored entry (the config's seed), AdaGrad at the config's learning rate; single GPU, no -a, no -C.  Like
 // `-m ials` and `-m lmf` it reads the test file only for -k.
+// `-m knn` trains nothing: it builds the item-neighbourhood recommender (cu2rec_knn_create) on the training file -- -W the weighting
+// (default cosine; bm25 with k1 = 100, b = 0.8), -N the neighbours kept per item (default 20, at most 256) -- writes every item's list to
+// <base>_knn_ids.csv and <base>_knn_sims.csv (items x N, -1 / nan padding) where the five files would go, and prints -k's ranking line
+// with the training rows as history and exclusion (cu2rec_knn_rank_metrics).  -k is required; no config is read, so -c is refused, as
+// are -a, -C, -g, -s and -w.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -49,7 +54,7 @@ namespace {
 bool g_mode_given = false;  // -m on the command line
 
 // what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
-enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr };
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn };
 
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
@@ -279,11 +284,52 @@ int run_multi_gpu(int nranks, int mode, int sync_every, int merge, const std::st
     return rc;
 }
 
+// the directory and the base name the output files of a training file go by (mf.cu:65-87)
+void output_place(const std::string &train_path, std::string &parent_dir, std::string &base) {
+    parent_dir = ".";
+    std::string filename = train_path;
+    const size_t slash = train_path.find_last_of('/');
+    if (slash != std::string::npos) {
+        parent_dir = train_path.substr(0, slash);
+        filename = train_path.substr(slash + 1);
+    }
+    base = filename.substr(0, filename.find_last_of('.'));
+}
+
+void print_rank_line(const cu2rec_rank_metrics &rm, int K) {
+    std::printf("TEST: Precision@%d: %f Recall@%d: %f NDCG@%d: %f MAP@%d: %f HitRate@%d: %f Users: %d Skipped: %d\n", K, rm.precision, K,
+                rm.recall, K, rm.ndcg, K, rm.map, K, rm.hit_rate, rm.users_evaluated, rm.users_skipped);
+}
+
+// bin/mf -m knn: the neighbour lists of the training file to <base>_knn_ids.csv / <base>_knn_sims.csv, then -k's ranking line
+int run_knn(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::string &train_path, int weighting, int neighbours, int rank_k,
+            float rank_threshold) {
+    if (test.rows > train.rows || test.cols > train.cols)
+        throw std::runtime_error("the test file names users / items the training file does not have");
+    if (train.cols > (1 << 24)) throw std::runtime_error("-m knn writes item ids through the float writer: more than 2^24 items");
+    test.cols = train.cols;  // the recommender's lists and the test rows name one catalogue
+    cu2rec::CsrHandle d_train(train), d_test(test);
+    cu2rec::KnnHandle knn(d_train, weighting, 100.f, 0.8f, neighbours);
+    const size_t total = static_cast<size_t>(train.cols) * neighbours;
+    std::vector<int> ids(total);
+    std::vector<float> sims(total), ids_f(total);
+    cu2rec::check(cu2rec_knn_neighbors(knn.h, nullptr, train.cols, neighbours, ids.data(), sims.data()));
+    for (size_t t = 0; t < total; ++t) ids_f[t] = static_cast<float>(ids[t]);
+    std::string parent_dir, base;
+    output_place(train_path, parent_dir, base);
+    cu2rec::check(cu2rec_write_csv((parent_dir + "/" + base + "_knn_ids.csv").c_str(), ids_f.data(), train.cols, neighbours));
+    cu2rec::check(cu2rec_write_csv((parent_dir + "/" + base + "_knn_sims.csv").c_str(), sims.data(), train.cols, neighbours));
+    cu2rec_rank_metrics rm;
+    cu2rec::check(cu2rec_knn_rank_metrics(knn.h, d_train.h, d_train.h, d_test.h, rank_k, rank_threshold, &rm, nullptr));
+    print_rank_line(rm, rank_k);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every] "
-                        "[-w adaptive|mean|weighted|sum] [-k K [-t T]] train.csv test.csv\n";
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn] [-a alpha] [-C cg_steps] [-g gpus] "
+                        "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
         return -1;
@@ -300,8 +346,12 @@ int main(int argc, char **argv) {
     bool alpha_given = false;
     bool cg_given = false;  // -C steps: -m ials by conjugate gradients (cu2rec_train_implicit_cg), or -m alscg's step count (default 3)
     long cg_steps = 0;
+    bool sync_given = false, merge_given = false;  // -s / -w: read by -g's ranks only; -m knn refuses them
+    bool weighting_given = false, neighbours_given = false;  // -W / -N: -m knn's weighting (-1: not one of the four) and list length
+    int weighting = CU2REC_KNN_COSINE;
+    long neighbours = 20;
     int opt;
-    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:W:N:")) != -1) {
         switch (opt) {
             case 'a': {
                 char *end = nullptr;
@@ -315,6 +365,21 @@ int main(int argc, char **argv) {
                 cg_given = true;
                 cg_steps = std::strtol(optarg, &end, 10);
                 if (end == optarg || *end != '\0') cg_steps = 0;  // not a number: refused below
+                break;
+            }
+            case 'W':
+                weighting_given = true;
+                weighting = std::strcmp(optarg, "count") == 0    ? CU2REC_KNN_COUNT
+                            : std::strcmp(optarg, "cosine") == 0 ? CU2REC_KNN_COSINE
+                            : std::strcmp(optarg, "tfidf") == 0  ? CU2REC_KNN_TFIDF
+                            : std::strcmp(optarg, "bm25") == 0   ? CU2REC_KNN_BM25
+                                                                 : -1;  // refused below
+                break;
+            case 'N': {
+                char *end = nullptr;
+                neighbours_given = true;
+                neighbours = std::strtol(optarg, &end, 10);
+                if (end == optarg || *end != '\0') neighbours = 0;  // not a number: refused below
                 break;
             }
             case 'k':
@@ -331,9 +396,11 @@ int main(int argc, char **argv) {
                 gpus = std::atoi(optarg);
                 break;
             case 's':
+                sync_given = true;
                 sync_every = std::atoi(optarg);
                 break;
             case 'w':
+                merge_given = true;
                 merge = std::strcmp(optarg, "mean") == 0       ? CU2REC_MERGE_MEAN
                         : std::strcmp(optarg, "sum") == 0      ? CU2REC_MERGE_SUM
                         : std::strcmp(optarg, "adaptive") == 0 ? CU2REC_MERGE_ADAPTIVE
@@ -350,6 +417,7 @@ int main(int argc, char **argv) {
                           : std::strcmp(optarg, "ials") == 0  ? Trainer::Ials
                           : std::strcmp(optarg, "lmf") == 0   ? Trainer::Lmf
                           : std::strcmp(optarg, "bpr") == 0   ? Trainer::Bpr
+                          : std::strcmp(optarg, "knn") == 0   ? Trainer::Knn
                                                               : Trainer::Sgd;
                 mode = trainer != Trainer::Sgd                  ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0     ? CU2REC_SGD_SERIAL
@@ -375,6 +443,11 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -t must be a number\n";
         return 1;
     }
+    if (trainer == Trainer::Knn &&
+        (!rank_given || alpha_given || cg_given || gpus > 1 || !config_path.empty() || sync_given || merge_given)) {  // before the GPU is touched
+        std::cerr << "mf: -m knn needs -k, reads no config (no -c), takes no -a and no -C, and is single-GPU only (no -g, -s, -w)\n" << usage;
+        return 1;
+    }
     if (rank_given && gpus > 1) {
         std::cerr << "mf: -k is single-GPU only (not with -g)\n";
         return 1;
@@ -392,6 +465,12 @@ int main(int argc, char **argv) {
     }
     if (trainer == Trainer::Bpr && (alpha_given || cg_given || gpus > 1)) {  // before the GPU is touched
         std::cerr << "mf: -m bpr takes no -a and no -C, and is single-GPU only (not with -g)\n" << usage;
+        return 1;
+    }
+    if ((weighting_given || neighbours_given) &&
+        (trainer != Trainer::Knn || weighting < 0 || neighbours < 1 || neighbours > CU2REC_KNN_MAX_NEIGHBOURS)) {
+        std::cerr << "mf: -W and -N need -m knn, a weighting of count, cosine, tfidf or bm25, and between 1 and " << CU2REC_KNN_MAX_NEIGHBOURS
+                  << " neighbours\n" << usage;
         return 1;
     }
     if (trainer == Trainer::Lmf && !alpha_given) alpha = 1.f;
@@ -421,6 +500,7 @@ int main(int argc, char **argv) {
         const std::string test_path = argv[optind++];
         const cu2rec::HostCsr test = cu2rec::load_ratings(test_path);    // mf.cu:47-51
         if (train.nnz == 0) throw std::runtime_error("no ratings read from " + train_path);
+        if (trainer == Trainer::Knn) return run_knn(train, test, train_path, weighting, static_cast<int>(neighbours), rank_k, rank_threshold);
 
         cu2rec_config cfg;  // mf.cu:54-57
         cu2rec::check(cu2rec_config_default(&cfg));
@@ -449,13 +529,8 @@ int main(int argc, char **argv) {
         cu2rec::check(cu2rec_model_download(model.h, P.data(), Q.data(), user_bias.data(), item_bias.data()));
 
         // mf.cu:65-87: outputs go next to the training file, named <base>_f<F>_<component>.csv
-        std::string parent_dir = ".", filename = train_path;
-        const size_t slash = train_path.find_last_of('/');
-        if (slash != std::string::npos) {
-            parent_dir = train_path.substr(0, slash);
-            filename = train_path.substr(slash + 1);
-        }
-        const std::string base = filename.substr(0, filename.find_last_of('.'));
+        std::string parent_dir, base;
+        output_place(train_path, parent_dir, base);
         const float gb = train.global_bias;
         const int f = cfg.n_factors;
         cu2rec::check(cu2rec_write_component(parent_dir.c_str(), base.c_str(), "p", P.data(), train.rows, f, f));
@@ -466,9 +541,7 @@ int main(int argc, char **argv) {
         if (rank_given) {  // the trained model ranks every user's unrated items against the test file
             cu2rec_rank_metrics rm;
             cu2rec::check(cu2rec_model_rank_metrics(model.h, d_train.h, d_test.h, rank_k, rank_threshold, &rm, nullptr));
-            const int K = rank_k;
-            std::printf("TEST: Precision@%d: %f Recall@%d: %f NDCG@%d: %f MAP@%d: %f HitRate@%d: %f Users: %d Skipped: %d\n", K,
-                        rm.precision, K, rm.recall, K, rm.ndcg, K, rm.map, K, rm.hit_rate, rm.users_evaluated, rm.users_skipped);
+            print_rank_line(rm, rank_k);
         }
     } catch (const std::exception &e) {
         std::cerr << "mf: " << e.what() << "\n";

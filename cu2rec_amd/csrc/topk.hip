@@ -5,7 +5,7 @@
 // 32 x 32 blocks exactly as scores_kernel does (score_tile.hpp: same staging chunks, same MFMA order, same bias sums), and
 // each score goes straight into selection -- nothing of size users x items is ever written.
 //
-// Selection ("Fused top-k"): every score becomes a 64-bit key whose unsigned order is recommend's order -- the
+// Selection ("Fused top-k"; the keys and the wavefront sort are select.hpp's, shared with knn.hip): every score becomes a 64-bit key whose unsigned order is recommend's order -- the
 // high word is rocPRIM's radix code of the float (descending sort; +0.0 and -0.0 one key), the low word the item index
 // reversed, so equal scores rank by ascending item.  A user keeps a running threshold (its k-th best key so far, in LDS)
 // and a candidate buffer of S = 256 or 512 keys (k <= 128 / k <= 256) in global workspace; a score that is not excluded, not
@@ -27,11 +27,14 @@
 #include <algorithm>
 #include <cmath>
 #include <limits>
+#include <optional>
 #include <vector>
 
 #include "device.hpp"
 #include "hip_check.hpp"
+#include "rank_stage.hpp"
 #include "score_tile.hpp"
+#include "select.hpp"
 
 namespace cu2rec {
 
@@ -41,68 +44,6 @@ constexpr int kTopkMaxK = 256;
 constexpr int kStep = 4 * kTile;                        // items scored per workgroup step
 constexpr size_t kWorkspaceBudget = size_t(256) << 20;  // per batch of users
 constexpr unsigned kEncNegInf = 0x007FFFFFu;            // radix code of -inf: never listed (recommend's mask value)
-
-// rocPRIM's float radix code (radix_key_codec, with the descending sort's -0.0 == +0.0) in the high word; the low word is
-// (0x7FFFFFFF - item) << 1, so a larger key is a better (score, smaller item) pair, and bit 0 keeps the sign of a zero score
-// so that the listed score is the computed float bit for bit.  Key 0 is never a candidate: it marks an empty slot.
-__device__ __forceinline__ unsigned long long topk_key(float s, int item) {
-    unsigned b = __float_as_uint(s);
-    const unsigned negzero = b == 0x80000000u;
-    if (negzero) b = 0u;
-    const unsigned enc = b ^ ((b & 0x80000000u) ? 0xFFFFFFFFu : 0x80000000u);
-    return (static_cast<unsigned long long>(enc) << 32) | (static_cast<unsigned>(0x7FFFFFFF - item) << 1) | negzero;
-}
-
-__device__ __forceinline__ void topk_decode(unsigned long long key, int &item, float &score) {
-    if (key == 0ull) {
-        item = -1;
-        score = __builtin_nanf("");
-        return;
-    }
-    const unsigned enc = static_cast<unsigned>(key >> 32);
-    const unsigned b = (key & 1ull) ? 0x80000000u : enc ^ ((enc & 0x80000000u) ? 0x80000000u : 0xFFFFFFFFu);
-    item = 0x7FFFFFFF - static_cast<int>((static_cast<unsigned>(key) >> 1) & 0x7FFFFFFFu);
-    score = __uint_as_float(b);
-}
-
-// Bitonic sort, descending, of the wavefront's 64 E keys; element e of lane l is key e * 64 + l.  Strides below 64 pair lanes
-// (shuffles), larger ones pair registers of one lane.  Every index is a compile-time constant after unrolling.
-template <int E>
-__device__ __forceinline__ void wave_sort_desc(unsigned long long (&v)[E], int lane) {
-#pragma unroll
-    for (int size = 2; size <= 64 * E; size <<= 1) {
-#pragma unroll
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            if (stride >= 64) {
-                const int es = stride >> 6;
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    if (e & es) continue;
-                    const bool desc = ((e * 64 + lane) & size) == 0;  // this block ends up descending: the lower slot takes the max
-                    const unsigned long long a = v[e], b = v[e | es];
-                    const bool swap = desc ? a < b : a > b;
-                    v[e] = swap ? b : a;
-                    v[e | es] = swap ? a : b;
-                }
-            } else {
-#pragma unroll
-                for (int e = 0; e < E; ++e) {
-                    const unsigned long long o = __shfl_xor(v[e], stride);
-                    const bool lower = (lane & stride) == 0, desc = ((e * 64 + lane) & size) == 0;
-                    v[e] = lower == desc ? max(v[e], o) : min(v[e], o);
-                }
-            }
-        }
-    }
-}
-
-// loads the count keys of a candidate buffer (the rest as empty), sorts them best first
-template <int E>
-__device__ __forceinline__ void load_sorted(unsigned long long (&v)[E], const unsigned long long *buf, int count, int lane) {
-#pragma unroll
-    for (int e = 0; e < E; ++e) v[e] = e * 64 + lane < count ? buf[e * 64 + lane] : 0ull;
-    wave_sort_desc<E>(v, lane);
-}
 
 // What a selection ranks (include/cu2rec_amd.h): the query rows X and the candidate rows Y of the score tile, and the score
 //   kUserItems   X = P, Y = Q                  ((gb + ub[query]) + ib[cand]) + x . y            cu2rec_model_topk
@@ -548,40 +489,56 @@ void model_rank_metrics(const DeviceModel &m, const DeviceCsr *exclude, const De
     require(!std::isnan(threshold), "cu2rec_model_rank_metrics: threshold is NaN");
     require(test->rows <= m.rows, "cu2rec_model_rank_metrics: the test set has rows past the model's rows");
     check_exclude(exclude, m.rows, m.cols, "cu2rec_model_rank_metrics: exclusions exceed the model's shape");
-    const double nan = std::numeric_limits<double>::quiet_NaN();
-    *out = cu2rec_rank_metrics{k, 0, m.rows, nan, nan, nan, nan, nan};
+    *out = empty_rank_metrics(k, m.rows);
     if (m.rows == 0) return;
     require(m.cols > 0, "cu2rec_model_rank_metrics: no items");
     require_device();
     hipStream_t stream = nullptr;
     const int n = test->rows;  // rows past the test set's last row have no relevant items
-    DeviceBuffer<double> d_per(static_cast<size_t>(m.rows) * 5), d_sum(6);
+    std::vector<int> ids(n);
+    for (int i = 0; i < n; ++i) ids[i] = i;
+    DeviceBuffer<int> d_ids(n);
+    std::optional<TopkRunner> run;
+    if (n > 0) {
+        d_ids.upload(ids.data(), n);
+        run.emplace(user_items(m), k, n, exclude && exclude->nnz > 0, RankStage::bytes_per_row(m.cols));
+    }
+    RankStage stage(m.rows, m.cols, n > 0 ? run->batch : 1, stream);
+    for (int p0 = 0; p0 < n; p0 += run->batch) {  // stream order keeps the workspace of one batch until the next needs it
+        const int b = std::min(run->batch, n - p0);
+        run->run(exclude, d_ids.ptr + p0, b, stream);
+        stage.add(*test, threshold, run->items.ptr, k, p0, b);
+    }
+    stage.finish(k, out, per_user);
+}
+
+cu2rec_rank_metrics empty_rank_metrics(int k, int rows) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    return cu2rec_rank_metrics{k, 0, rows, nan, nan, nan, nan, nan};
+}
+
+RankStage::RankStage(int rows_, int cols_, int batch, hipStream_t stream_)
+    : rows(rows_), cols(cols_), words((cols_ + 31) / 32), stream(stream_), d_per(static_cast<size_t>(rows_) * 5), d_sum(6),
+      rel(static_cast<size_t>(batch) * ((cols_ + 31) / 32)), n_rel(batch) {
     hipLaunchKernelGGL(fill_nan_kernel, dim3(std::min<size_t>((d_per.count + 255) / 256, 4096)), dim3(256), 0, stream, d_per.ptr,
                        d_per.count);
     CU2REC_HIP(hipGetLastError());
-    if (n > 0) {
-        const int words = (m.cols + 31) / 32;
-        std::vector<int> ids(n);
-        for (int i = 0; i < n; ++i) ids[i] = i;
-        DeviceBuffer<int> d_ids(n);
-        d_ids.upload(ids.data(), n);
-        TopkRunner run(user_items(m), k, n, exclude && exclude->nnz > 0, static_cast<size_t>(words) * 4 + sizeof(int));
-        DeviceBuffer<unsigned> rel(static_cast<size_t>(run.batch) * words);
-        DeviceBuffer<int> n_rel(run.batch);
-        const bool all = std::isinf(threshold) && threshold < 0;
-        for (int p0 = 0; p0 < n; p0 += run.batch) {  // stream order keeps the workspace of one batch until the next needs it
-            const int b = std::min(run.batch, n - p0);
-            run.run(exclude, d_ids.ptr + p0, b, stream);
-            CU2REC_HIP(hipMemsetAsync(rel.ptr, 0, static_cast<size_t>(b) * words * sizeof(unsigned), stream));
-            CU2REC_HIP(hipMemsetAsync(n_rel.ptr, 0, static_cast<size_t>(b) * sizeof(int), stream));
-            hipLaunchKernelGGL(relevant_kernel, dim3(std::min(b, 4096)), dim3(256), 0, stream, test->indptr.ptr, test->indices.ptr,
-                               test->data.ptr, p0, b, m.cols, all, threshold, words, rel.ptr, n_rel.ptr);
-            hipLaunchKernelGGL(rank_metrics_kernel, dim3((b + 255) / 256), dim3(256), 0, stream, run.items.ptr, k, rel.ptr, words,
-                               n_rel.ptr, p0, b, d_per.ptr);
-            CU2REC_HIP(hipGetLastError());
-        }
-    }
-    hipLaunchKernelGGL(rank_sum_kernel, dim3(1), dim3(256), 0, stream, d_per.ptr, m.rows, d_sum.ptr);
+}
+
+void RankStage::add(const DeviceCsr &test, float threshold, const int *items, int k, int p0, int b) {
+    const bool all = std::isinf(threshold) && threshold < 0;
+    CU2REC_HIP(hipMemsetAsync(rel.ptr, 0, static_cast<size_t>(b) * words * sizeof(unsigned), stream));
+    CU2REC_HIP(hipMemsetAsync(n_rel.ptr, 0, static_cast<size_t>(b) * sizeof(int), stream));
+    hipLaunchKernelGGL(relevant_kernel, dim3(std::min(b, 4096)), dim3(256), 0, stream, test.indptr.ptr, test.indices.ptr,
+                       test.data.ptr, p0, b, cols, all, threshold, words, rel.ptr, n_rel.ptr);
+    hipLaunchKernelGGL(rank_metrics_kernel, dim3((b + 255) / 256), dim3(256), 0, stream, items, k, rel.ptr, words, n_rel.ptr, p0, b,
+                       d_per.ptr);
+    CU2REC_HIP(hipGetLastError());
+}
+
+void RankStage::finish(int k, cu2rec_rank_metrics *out, double *per_user) {
+    *out = empty_rank_metrics(k, rows);
+    hipLaunchKernelGGL(rank_sum_kernel, dim3(1), dim3(256), 0, stream, d_per.ptr, rows, d_sum.ptr);
     CU2REC_HIP(hipGetLastError());
     double sums[6];
     CU2REC_HIP(hipMemcpyAsync(sums, d_sum.ptr, sizeof(sums), hipMemcpyDeviceToHost, stream));
@@ -589,7 +546,7 @@ void model_rank_metrics(const DeviceModel &m, const DeviceCsr *exclude, const De
     CU2REC_HIP(hipStreamSynchronize(stream));
     const int evaluated = static_cast<int>(sums[5]);
     out->users_evaluated = evaluated;
-    out->users_skipped = m.rows - evaluated;
+    out->users_skipped = rows - evaluated;
     if (evaluated > 0) {
         out->precision = sums[0] / evaluated;
         out->recall = sums[1] / evaluated;

@@ -784,6 +784,55 @@ int cu2rec_shard_job_exchange_stats(cu2rec_shard_job *job, int *timed, double *s
 int cu2rec_train_sharded(cu2rec_shard_job *job, const cu2rec_csr *test, cu2rec_config *cfg, int mode, int verbose,
                          float *losses, cu2rec_train_stats *stats);
 
+/* ------------------------------------------------------------------------------------------
+ * Item-based nearest-neighbour recommendation (ItemKNN): no factors, no learning rate, no seed.  `train` is the user x item CSR
+ * with I columns, n_u the number of entries user u stores.  Every stored entry gets a weight w_ui:
+ *   CU2REC_KNN_COUNT   w = r
+ *   CU2REC_KNN_COSINE  w = r / sqrt(sum_v r_vi^2)
+ *   CU2REC_KNN_TFIDF   w = t / sqrt(sum_v t_vi^2), t_ui = sqrt(r_ui) idf_u, idf_u = ln(I) - ln(1 + n_u)
+ *   CU2REC_KNN_BM25    w = r (k1 + 1) / (k1 len_i + r) idf_u, len_i = (1 - b) + b c_i / mean(c), c_i = sum_v r_vi, the mean over
+ *                      all I columns (a zero denominator gives w = 0)
+ * evaluated in double (the per-user and per-column sums in a fixed order, k1 and b as the floats given) and rounded to float once;
+ * a column whose norm is 0 gets weights 0.  The similarity of two items is S_ij = sum_u w_ui w_uj over the users that store both;
+ * item i keeps its N best neighbours among the TOUCHED candidates j != i (at least one user stores both i and j), whatever their
+ * value.  A recommendation for a history row h (raw stored values r) scores score_j = sum_{i in h} r_i S_N[i, j] over the
+ * truncated lists; candidates are the touched j (some history item lists j) outside the `exclude` row.
+ *
+ * Every score is the fold acc = fmaf(alpha, v, acc) from +0.0f in a fixed order -- the users of column i in ascending order for
+ * S_ij, the history row's items in ascending id order for score_j -- with no float atomics: results are bit-identical run to
+ * run, and a query alone gives what it gives among others.  Order, ties (ascending id) and the -1 / NaN padding of every list
+ * are cu2rec_model_topk's; unlike there, a touched candidate is listed even when its value is -inf or NaN.
+ *
+ * Rows of every CSR may be unsorted (the library works on its own row-sorted copy, made on first use and kept with the
+ * cu2rec_csr); a train or history row that stores the same column twice is CU2REC_EINVAL.  Null arguments, a weighting outside
+ * the four, a non-finite or negative k1, b outside [0, 1], neighbours or k outside [1, 256], an id out of range, a history,
+ * exclude or test CSR whose column count differs from the model's: CU2REC_EINVAL, checked before the device is touched where the
+ * arguments alone show it.
+ *
+ * The product runs one wavefront per (query, slice of cu2rec_knn_slice_items() consecutive candidate ids), in batches of queries
+ * whose workspace ((slices + 1) * k * 8 bytes per query) fits CU2REC_KNN_WORKSPACE_BYTES. */
+enum { CU2REC_KNN_COUNT = 0, CU2REC_KNN_COSINE = 1, CU2REC_KNN_TFIDF = 2, CU2REC_KNN_BM25 = 3 };
+enum { CU2REC_KNN_MAX_NEIGHBOURS = 256, CU2REC_KNN_WORKSPACE_BYTES = 64 << 20 };
+typedef struct cu2rec_knn cu2rec_knn;
+/* builds the model: weights, the N best neighbours of every item, and their id-sorted copy for cu2rec_knn_recommend */
+int cu2rec_knn_create(const cu2rec_csr *train, int weighting, float k1, float b, int neighbours, cu2rec_knn **out);
+void cu2rec_knn_destroy(cu2rec_knn *knn);
+int cu2rec_knn_info(const cu2rec_knn *knn, int *items, int *neighbours, int *weighting); /* pointers may be NULL */
+/* candidate ids per wavefront slice (a constant of the build; needs no device) */
+int cu2rec_knn_slice_items(void);
+/* w_ui of every stored entry, in the CSR's own entry order -> out_nnz (host, nnz floats) */
+int cu2rec_csr_knn_weights(const cu2rec_csr *csr, int weighting, float k1, float b, float *out_nnz);
+/* the k <= neighbours best neighbours of each listed item (ids: host, duplicates allowed; NULL: every item) -> host, n x k */
+int cu2rec_knn_neighbors(const cu2rec_knn *knn, const int *ids, int n, int k, int *out_ids, float *out_sims);
+/* the k best candidates of each listed history row (users: host row ids of `history`, duplicates allowed; NULL: every row; row u
+ * of `exclude` -- may be NULL, rows past its last exclude nothing -- is not listed for row u) -> host, n x k */
+int cu2rec_knn_recommend(const cu2rec_knn *knn, const cu2rec_csr *history, const cu2rec_csr *exclude, const int *users, int n,
+                         int k, int *out_items, float *out_scores);
+/* cu2rec_model_rank_metrics' definitions over cu2rec_knn_recommend's lists of every history row (the rows the means are taken
+ * over; test rows past them: CU2REC_EINVAL).  per_user: host, history rows x 5, may be NULL. */
+int cu2rec_knn_rank_metrics(const cu2rec_knn *knn, const cu2rec_csr *history, const cu2rec_csr *exclude, const cu2rec_csr *test,
+                            int k, float threshold, cu2rec_rank_metrics *out, double *per_user);
+
 #ifdef __cplusplus
 }
 #endif
