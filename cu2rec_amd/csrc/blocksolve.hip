@@ -77,29 +77,17 @@ __global__ void bs_tables_kernel(SgdHyper h, float *__restrict__ t) {
     t[kTabCpow + k] = static_cast<float>(ck);
 }
 
-__device__ __forceinline__ int lower_bound_key(const uint32_t *__restrict__ keys, int n, uint32_t target) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < target) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // ---- plan: one workgroup per iteration of the batch --------------------------------------------------------------
-__global__ __launch_bounds__(256) void bs_plan_kernel(const uint32_t *__restrict__ keys, int n_active, int n_hot,
-                                                      int item_bits, int max_blocks, const int *__restrict__ item_of_rank,
-                                                      int *__restrict__ chain_begin, BsChainDesc *__restrict__ chains,
-                                                      BsBlockDesc *__restrict__ blocks, int *__restrict__ walk_begin, size_t stride) {
+// chain_ranges: the window's table of where the chains begin (chain_ranges_kernel, ordered.hip, queued in front of this kernel on the
+// same stream): iteration b's chain of rank r is [cb[r], cb[r + 1]) with cb = chain_ranges + b * range_stride, range_stride > n_hot
+__global__ __launch_bounds__(256) void bs_plan_kernel(const int *__restrict__ chain_ranges, int range_stride, int n_hot, int max_blocks,
+                                                      const int *__restrict__ item_of_rank, BsChainDesc *__restrict__ chains,
+                                                      BsBlockDesc *__restrict__ blocks) {
     __shared__ int s_part[256];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const uint32_t *kb = keys + static_cast<size_t>(b) * stride;  // iteration b's share of the sorted keys
-    int *cb = chain_begin + static_cast<size_t>(b) * (n_hot + 1);
+    const int *cb = chain_ranges + static_cast<size_t>(b) * range_stride;
     BsChainDesc *cd = chains + static_cast<size_t>(b) * max(n_hot, 1);
     BsBlockDesc *bd = blocks + static_cast<size_t>(b) * max_blocks;
-    for (int r = tid; r <= n_hot; r += 256) cb[r] = lower_bound_key(kb, n_active, static_cast<uint32_t>(r));
-    __syncthreads();
-    if (tid == 0) walk_begin[b] = cb[n_hot];
     // blocks per chain -> exclusive prefix; thread t owns the chains [t * per, (t + 1) * per)
     const int per = (n_hot + 255) / 256;
     const int r0 = min(tid * per, n_hot), r1 = min(r0 + per, n_hot);
@@ -425,9 +413,8 @@ int blocksolve_hot_items(const std::vector<double> &rate, int n_active, int rank
     return std::min(n, rank_limit);
 }
 
-BlockSolve::BlockSolve(int n_hot_, const std::vector<double> &rate, double hot_rate, int n_active_, int item_bits_, int max_batch_,
-                       const int *item_of_rank_)
-    : n_hot(n_hot_), n_active(n_active_), item_bits(item_bits_), max_batch(max_batch_), item_of_rank(item_of_rank_) {
+BlockSolve::BlockSolve(int n_hot_, const std::vector<double> &rate, double hot_rate, int n_active_, int max_batch_, const int *item_of_rank_)
+    : n_hot(n_hot_), n_active(n_active_), max_batch(max_batch_), item_of_rank(item_of_rank_) {
     max_blocks = n_active / kBsLinks + n_hot + 1;
     // Blocks of 64 links an iteration's hot chains are expected to fill, as a bound that holds in all but astronomically rare iterations
     // (the hot links' count: mean hot_rate, variance at most the mean; one partial block per chain): what phase 3 is launched with.  Its
@@ -446,8 +433,6 @@ BlockSolve::BlockSolve(int n_hot_, const std::vector<double> &rate, double hot_r
     }
     if (la_ranks > 0) la_cap = std::min(max_blocks, static_cast<int>(la_blocks * 1.25) + 4 * la_ranks + 8);
     for (int slot = 0; slot < 2; ++slot) {
-        chain_begin[slot].allocate(static_cast<size_t>(max_batch) * (n_hot + 1));
-        walk_begin[slot].allocate(max_batch);
         chains[slot].allocate(static_cast<size_t>(max_batch) * n_hot);
         blocks[slot].allocate(static_cast<size_t>(max_batch) * max_blocks);
     }
@@ -469,9 +454,9 @@ BlockSolve::~BlockSolve() {  // (the schedule has waited for its last call's end
         if (e) (void)hipEventDestroy(e);
 }
 
-void BlockSolve::plan(int slot, const uint32_t *sk, int nb, size_t stride, hipStream_t sched) {
-    hipLaunchKernelGGL(bs_plan_kernel, dim3(nb), dim3(256), 0, sched, sk, n_active, n_hot, item_bits, max_blocks, item_of_rank,
-                       chain_begin[slot].ptr, chains[slot].ptr, blocks[slot].ptr, walk_begin[slot].ptr, stride);
+void BlockSolve::plan(int slot, const int *chain_ranges, int range_stride, int nb, hipStream_t sched) {
+    hipLaunchKernelGGL(bs_plan_kernel, dim3(nb), dim3(256), 0, sched, chain_ranges, range_stride, n_hot, max_blocks, item_of_rank,
+                       chains[slot].ptr, blocks[slot].ptr);
 }
 
 void BlockSolve::begin(const SgdArgs &a, hipStream_t stream) {
@@ -508,7 +493,6 @@ void BlockSolve::begin(const SgdArgs &a, hipStream_t stream) {
     it = BsIteration{};
     it.n_active = n_active;
     it.n_hot = n_hot;
-    it.item_mask = (1u << item_bits) - 1u;
     it.item_of_rank = item_of_rank;
     it.tables = tables.ptr;
     it.log2a = static_cast<float>(std::log2(1.0 - static_cast<double>(a.h.lr) * static_cast<double>(a.h.q_reg)));
@@ -550,7 +534,6 @@ void BlockSolve::iteration(const SgdArgs &a, int slot, int b, const uint32_t *ke
     it.vals = vals;
     it.chains = chains[slot].ptr + static_cast<size_t>(b) * n_hot;
     it.blocks = blocks[slot].ptr + static_cast<size_t>(b) * max_blocks;
-    it.walk_begin = walk_begin[slot].ptr + b;
     it.side_target = device_join ? side_seq_host + 1 : 0;
     if (upd_pending) CU2REC_HIP(hipStreamWaitEvent(stream, ev_upd, 0));  // (events) join: rows the next phase 1 reads
     launch_gram(a, it, stream, device_join ? nullptr : ev_gram);

@@ -43,10 +43,8 @@ struct BsIteration {
     const uint64_t *vals;     // [n_active] user << 32 | rating bits
     int n_active;
     int n_hot;                // popularity ranks [0, n_hot) are solved block-wise, the others walked link by link
-    uint32_t item_mask;
     const BsChainDesc *chains;  // [n_hot]
     const BsBlockDesc *blocks;  // [max_blocks]
-    const int *walk_begin;      // [1] sorted position where the walked chains start
     const int *item_of_rank;
     const float *tables;      // [kBsTableFloats]
     float log2a, log2c;       // log2(1 - lr * Q_reg), log2(1 - lr * item_bias_reg)
@@ -92,14 +90,14 @@ int blocksolve_hot_items(const std::vector<double> &rate, int n_active, int rank
 // three phases, the plan of every scheduled iteration, the side stream the other items' chains run on, and the launch sequence.
 class BlockSolve {
 public:
-    // ranks [0, n_hot) are solved block-wise; hot_rate = rate[0] + ... + rate[n_hot - 1]; keys carry the rank in item_bits bits
-    BlockSolve(int n_hot, const std::vector<double> &rate, double hot_rate, int n_active, int item_bits, int max_batch,
-               const int *item_of_rank);
+    // ranks [0, n_hot) are solved block-wise; hot_rate = rate[0] + ... + rate[n_hot - 1]
+    BlockSolve(int n_hot, const std::vector<double> &rate, double hot_rate, int n_active, int max_batch, const int *item_of_rank);
     ~BlockSolve();
     BlockSolve(const BlockSolve &) = delete;
     BlockSolve &operator=(const BlockSolve &) = delete;
-    // schedule slot `slot` now holds nb sorted iterations (their keys `sk`, `stride` apart): queues their chain and block tables on `sched`
-    void plan(int slot, const uint32_t *sk, int nb, size_t stride, hipStream_t sched);
+    // schedule slot `slot` now holds nb sorted iterations: queues their chain and block tables on `sched`, behind the kernel that fills
+    // chain_ranges -- [nb][range_stride], range_stride > n_hot: where the chain of every rank r <= n_hot begins (OrderedSchedule::chain_ranges)
+    void plan(int slot, const int *chain_ranges, int range_stride, int nb, hipStream_t sched);
     // A call's start: decay tables, scratch, the side stream (behind everything queued on `stream` so far) and the fork / join topology.
     void begin(const SgdArgs &a, hipStream_t stream);
     // One iteration (a.iter0): the plan of iteration `b` of slot `slot`, its sorted keys and values.  `side` launches the other items'
@@ -113,14 +111,13 @@ public:
     const int n_hot;
 
 private:
-    int n_active, item_bits, max_batch;
+    int n_active, max_batch;
     const int *item_of_rank;
     int max_blocks;     // blocks of 64 links (kBsLinks) per iteration, upper bound
     int launch_blocks;  // workgroups phase 3 is launched with (BsIteration::launch_blocks)
     int la_ranks = 0;   // ranks [0, la_ranks): phase 2 in the look-ahead form; their blocks lie below la_cap
     int la_cap = 0;
     // per schedule slot, per iteration: the plan (bs_plan_kernel)
-    DeviceBuffer<int> chain_begin[2], walk_begin[2];
     DeviceBuffer<BsChainDesc> chains[2];
     DeviceBuffer<BsBlockDesc> blocks[2];
     DeviceBuffer<float> tables, Mbuf, ebuf, qstart, Nbuf;  // Nbuf: [la_cap][kBsCrossFloats] the cross blocks of the look-ahead chains

@@ -26,8 +26,8 @@ struct OrderedSchedule {
 
     int n_rows, n_cols, nnz;
     int n_active = 0;   // users with at least one rating = updates per iteration
-    int item_bits = 0;  // key = iteration_in_batch << item_bits | popularity_rank(item)
-    int max_batch = 1;  // iterations scheduled (sampled + sorted) per pass
+    int item_bits = 0;  // a sorted key is the item's popularity rank, below 1 << item_bits; users without ratings carry that one bit instead
+    int max_batch = 1;  // iterations per window (sampled + sorted in one pass)
     DeviceBuffer<int> item_rank, item_of_rank;
     // Two schedule slots: the sample stream is value independent, so batch j + 1 is sampled and sorted on a stream of
     // its own while batch j's iterations run.  Per slot: the radix sort's two key / value buffers.
@@ -61,8 +61,9 @@ struct OrderedSchedule {
     std::unique_ptr<BlockSolve> bs;
     int blocksolve_items() const { return bs ? bs->n_hot : 0; }
     int n_duo_bs = 0;  // block-solve mode: ranks [bs->n_hot, n_duo_bs) run in the two-wave form beside the block solves
-    // per schedule slot: [iteration of the batch][rank 0 .. n_range_ranks] first sorted position of the chains of the most
-    // popular items (chain_ranges_kernel, behind the sort): the two-wave blocks read their chain's range instead of searching
+    // per schedule slot: [iteration of the window][rank 0 .. n_range_ranks] first sorted position of the chains of the most
+    // popular items (chain_ranges_kernel, behind the sort).  The ONE table of where chains begin: the two-wave blocks, the walk's
+    // sweeper and the block-solve plan (BlockSolve::plan) read it
     DeviceBuffer<int> chain_ranges[2];
     int n_range_ranks = 0;
     // rank_rate_prefix[r] = expected updates per iteration of the r most popular items together (host; [n_cols + 1]): what the walk
@@ -74,6 +75,14 @@ struct OrderedSchedule {
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     ~OrderedSchedule();
+    // CONSTRUCTOR ONLY (it allocates and fills what the constructor's other steps size their buffers by): the one-off host pass over
+    // the CSR that sets n_active, item_rank / item_of_rank and rank_rate_prefix; returns the rates by rank
+    std::vector<double> rank_items(const int *d_indptr, const int *d_indices);
+    // the pieces of run(): which slot's window holds iteration `it` of this (seed, user offset, indptr, mode), or -1; queueing a
+    // window into a slot on `sched`; starting over in slot 0 when no window holds what the call needs
+    int slot_holding(const SgdArgs &a, uint64_t it, bool blocksolve) const;
+    void schedule_window(const SgdArgs &a, int slot, uint64_t first_iter, int nb, bool blocksolve);
+    void restart(const SgdArgs &a, uint64_t first_iter, int nb, bool blocksolve, hipStream_t stream);
 };
 
 }  // namespace cu2rec
