@@ -26,16 +26,12 @@
 // short rows go to als_cg.hip's explicit instantiation, which needs no G0 at all.
 #include <hip/hip_runtime.h>
 
-#include <cstring>  // (rocPRIM's headers call memset without including it)
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <string>
 
 #include "als.hpp"
 #include "kernels.hpp"
 #include "objective_pass.hpp"
-#include "rocprim_temp.hpp"
 #include "score_tile.hpp"
 
 namespace cu2rec {
@@ -482,61 +478,7 @@ __global__ __launch_bounds__(kObjThreads) void ials_objective_reduce_kernel(cons
         for (int j = 0; j < 4; ++j) out[j] = red[j][0];
 }
 
-// ---- the item-major view -------------------------------------------------------------------------------------------------
-__global__ void als_row_of_kernel(const int *__restrict__ indptr, int rows, int nnz, int *__restrict__ row_of,
-                                  int *__restrict__ pos) {
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += gridDim.x * blockDim.x) {
-        row_of[k] = row_of_entry(indptr, rows, k);
-        pos[k] = k;
-    }
-}
-
-__global__ void als_transpose_kernel(const unsigned *__restrict__ sorted_items, const int *__restrict__ sorted_pos,
-                                     const int *__restrict__ row_of, const float *__restrict__ data, int nnz, int cols,
-                                     int *__restrict__ t_indptr, int *__restrict__ t_indices, float *__restrict__ t_data) {
-    const int stride = gridDim.x * blockDim.x;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < nnz; p += stride) {
-        const int k = sorted_pos[p];
-        t_indices[p] = row_of[k];
-        t_data[p] = data[k];
-    }
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += stride)  // first position of item i
-        t_indptr[i] = first_at_least(sorted_items, 0, nnz, static_cast<unsigned>(i));
-}
-
 }  // namespace
-
-void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, const float *data, int rows, int cols, int nnz,
-                         hipStream_t stream) {
-    c.t_indptr.allocate(static_cast<size_t>(cols) + 1);
-    c.t_indices.allocate(std::max(nnz, 1));
-    c.t_data.allocate(std::max(nnz, 1));
-    c.t_pos.allocate(std::max(nnz, 1));
-    if (nnz == 0) {
-        CU2REC_HIP(hipMemsetAsync(c.t_indptr.ptr, 0, (static_cast<size_t>(cols) + 1) * sizeof(int), stream));
-        CU2REC_HIP(hipStreamSynchronize(stream));
-        return;
-    }
-    DeviceBuffer<int> row_of(nnz), pos(nnz);
-    int *pos_sorted = c.t_pos.ptr;  // kept: the user-major position of every item-major one
-    DeviceBuffer<unsigned> items_sorted(nnz);
-    const int threads = 256, blocks = static_cast<int>(std::min<size_t>((static_cast<size_t>(nnz) + threads - 1) / threads, 8192));
-    hipLaunchKernelGGL(als_row_of_kernel, dim3(blocks), dim3(threads), 0, stream, indptr, rows, nnz, row_of.ptr, pos.ptr);
-    CU2REC_HIP(hipGetLastError());
-    unsigned bits = 1;
-    while (bits < 31 && (1u << bits) < static_cast<unsigned>(cols)) ++bits;
-    // LSD radix sort: a chain of stable counting sorts, so rating positions (users ascending) keep their order within an item
-    const unsigned *keys_in = reinterpret_cast<const unsigned *>(indices);
-    DeviceBuffer<unsigned char> temp;
-    with_rocprim_temp(temp, [&](void *t, size_t &bytes) {
-        return rocprim::radix_sort_pairs(t, bytes, keys_in, items_sorted.ptr, pos.ptr, pos_sorted, nnz, 0u, bits, stream);
-    });
-    const int tblocks = static_cast<int>(std::min<size_t>((static_cast<size_t>(std::max(nnz, cols + 1)) + threads - 1) / threads, 8192));
-    hipLaunchKernelGGL(als_transpose_kernel, dim3(tblocks), dim3(threads), 0, stream, items_sorted.ptr, pos_sorted, row_of.ptr,
-                       data, nnz, cols, c.t_indptr.ptr, c.t_indices.ptr, c.t_data.ptr);
-    CU2REC_HIP(hipGetLastError());
-    CU2REC_HIP(hipStreamSynchronize(stream));  // before the temporaries are freed
-}
 
 void als_plan_side(AlsSide &side, hipStream_t stream) {
     std::vector<int> indptr(static_cast<size_t>(side.rows) + 1);
@@ -546,11 +488,9 @@ void als_plan_side(AlsSide &side, hipStream_t stream) {
     side.long_rows.clear();
     side.long_first_chunk.assign(1, 0);
     side.rows_with_ratings = 0;
-    side.max_len = 0;
     for (int r = 0; r < side.rows; ++r) {
         const int n = indptr[r + 1] - indptr[r];
         side.rows_with_ratings += n > 0;
-        side.max_len = std::max(side.max_len, n);
         if (n <= kAlsChunk) continue;
         const int len = als_chunk_len(n);
         for (int b = indptr[r]; b < indptr[r + 1]; b += len) {
@@ -568,6 +508,7 @@ void als_plan_side(AlsSide &side, hipStream_t stream) {
     put(side.d_long_first_chunk, side.long_first_chunk);
     put(side.d_chunk_lo, lo);
     put(side.d_chunk_hi, hi);
+    side.planned = true;
 }
 
 int als_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows, hipStream_t stream, int cg_steps) {

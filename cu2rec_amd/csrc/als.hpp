@@ -39,26 +39,21 @@ __host__ __device__ inline int als_chunk_len(int n) {  // ratings per chunk (the
     return (per + kAlsStep - 1) / kAlsStep * kAlsStep;
 }
 
-// One side's CSR as the half-step reads it, plus the host list of its long rows (cut into chunks).
+// One side's rows as the half-step reads them -- the CSR itself for the users, its item-major view (csr_views.hpp) for the items --
+// plus the row plan: the host list of the side's long rows, cut into chunks.
 struct AlsSide {
     const int *indptr = nullptr, *indices = nullptr;
     const float *data = nullptr;
-    int rows = 0, nnz = 0;
+    int rows = 0;
+    bool planned = false;  // als_plan_side has filled what follows
     int rows_with_ratings = 0;
-    int max_len = 0;
     std::vector<int> long_rows, long_first_chunk;  // long_first_chunk[r + 1] - long_first_chunk[r]: chunks of long row r
     DeviceBuffer<int> d_long_rows, d_long_first_chunk, d_chunk_lo, d_chunk_hi;
 };
 
-// Cached on a cu2rec_csr: the user side reads the CSR itself; the item side reads its transpose, built on the device the first
-// time it is needed (a stable radix sort by item of the rating positions: users stay in ascending order within an item).
+// Cached on a cu2rec_csr: what is ALS's own, the two row plans and the half-steps' workspaces.
 struct AlsCache {
     AlsSide users, items;
-    bool users_ready = false, items_ready = false;  // the side is planned (als_plan_side)
-    bool items_built = false;                        // the item-major view exists (ItemKNN reads it without a plan)
-    DeviceBuffer<int> t_indptr, t_indices;
-    DeviceBuffer<float> t_data;
-    DeviceBuffer<int> t_pos;  // item-major position -> the entry's position in the user-major CSR (the sort's own values, kept)
     DeviceBuffer<float> workspace;  // the partial Grams of one batch of long rows, kAlsWorkspaceBytes at most
     DeviceBuffer<int> unsolved;
     // implicit feedback: X^T X of the partner side (and of the other side, for the objective) in the accumulator layout
@@ -100,10 +95,7 @@ __host__ __device__ inline int tri(int i) { return i * (i + 1) / 2; }  // tile p
 // 32-column tiles of the implicit half-step's staged operands: f factor columns and the right-hand side's weight
 inline int ials_tiles(int n_factors) { return (n_factors + 1 + 31) / 32; }
 
-// builds the transpose of (indptr, indices, data) [rows x cols] into the cache's t_* buffers
-void als_build_transpose(AlsCache &c, const int *indptr, const int *indices, const float *data, int rows, int cols, int nnz,
-                         hipStream_t stream);
-// fills side.long_rows / chunk lists from the device indptr (once per side)
+// fills side.long_rows / chunk lists from the device indptr of a side whose pointers and shape are set (once per side)
 void als_plan_side(AlsSide &side, hipStream_t stream);
 // one half-step over every row of `side` (rows < max_rows); returns the number of rows left unchanged by a failed pivot
 // cg_steps > 0 (cu2rec_model_als_cg): the rows of 1 .. kAlsChunk ratings take cg_steps conjugate-gradient steps from their current

@@ -5,22 +5,20 @@
 //   g_i  = sum_(e: item(e) = i) c_e p_u - sum_(e: j_e = i) c_e p_u - Q_reg q_i,   gb_i = sum_pos c_e - sum_neg c_e - item_bias_reg ib_i
 //
 // NEGATIVES (bpr_negatives_kernel): one thread per entry draws up to kBprAttempts items from sampler.hpp and takes the first that a
-// binary search does not find in the row's ascending copy of its items.
+// binary search does not find in the row's ascending items (csr_views.hpp: the row-sorted view).
 // USERS (bpr_user_kernel): one wavefront per user on row_wave.hpp's ENTRY map, exactly lmf_sparse_kernel's walk: group g takes the
 // row's entries g, g + 4, ... in ascending order, gathers q_i and q_j, forms the difference once, dots it with the staged p_u, and
 // adds c_e times it to the group's sums; the four groups are added in group order.  The CoefOnly instantiation stores c_e instead.
 // REGROUPING: a stable radix sort of the entries by j_e (-1 as `cols`, past the end) and the first position of every item in it.
-// ITEMS (bpr_item_kernel): one wavefront per item on the same map: its positives in ascending item-major position (the view of
-// als.hip, whose kept sort values name each one's entry), then its negatives in ascending entry, gathering [p_u | 1] and c_e.
+// ITEMS (bpr_item_kernel): one wavefront per item on the same map: its positives in ascending item-major position (the CSR's
+// item-major view, whose kept sort values name each one's entry), then its negatives in ascending entry, gathering [p_u | 1] and c_e.
 // Every sum's order is a function of positions alone: no float atomics, bit-identical run to run.
 #include <hip/hip_runtime.h>
-
-#include <cstring>  // (rocPRIM's headers call memset without including it)
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 
 #include "bpr.hpp"
+#include "device.hpp"
 #include "logistic.hpp"
 #include "objective_pass.hpp"
 #include "rocprim_temp.hpp"
@@ -31,18 +29,12 @@ namespace cu2rec {
 
 namespace {
 
-constexpr int kEntryThreads = 256, kEntryMaxBlocks = 8192;
-
-int entry_grid(size_t n) { return static_cast<int>(std::min<size_t>((n + kEntryThreads - 1) / kEntryThreads, kEntryMaxBlocks)); }
-
-// have_row_of: row_of is read; otherwise it is written (the first call on a CSR)
-__global__ __launch_bounds__(kEntryThreads) void bpr_negatives_kernel(const int *__restrict__ indptr, const int *__restrict__ sorted,
-                                                                      int rows, int cols, int nnz, uint64_t seed, uint32_t sweep,
-                                                                      bool have_row_of, int *__restrict__ row_of,
-                                                                      int *__restrict__ neg, unsigned *__restrict__ neg_key) {
+__global__ __launch_bounds__(kElementThreads) void bpr_negatives_kernel(const int *__restrict__ indptr, const int *__restrict__ sorted,
+                                                                        const int *__restrict__ row_of, int cols, int nnz, uint64_t seed,
+                                                                        uint32_t sweep, int *__restrict__ neg,
+                                                                        unsigned *__restrict__ neg_key) {
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += gridDim.x * blockDim.x) {
-        const int u = have_row_of ? row_of[e] : row_of_entry(indptr, rows, e);
-        if (!have_row_of) row_of[e] = u;
+        const int u = row_of[e];
         const int lo = indptr[u], hi = indptr[u + 1];
         const uint32_t k = static_cast<uint32_t>(e - lo);
         int j = -1;
@@ -58,17 +50,6 @@ __global__ __launch_bounds__(kEntryThreads) void bpr_negatives_kernel(const int 
         neg[e] = j;
         neg_key[e] = j < 0 ? static_cast<unsigned>(cols) : static_cast<unsigned>(j);
     }
-}
-
-__global__ __launch_bounds__(kEntryThreads) void bpr_iota_kernel(int *__restrict__ iota, int nnz) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nnz; e += gridDim.x * blockDim.x) iota[e] = e;
-}
-
-// n_indptr[i] = the first position of key_sorted that holds i or more, i = 0 .. cols
-__global__ __launch_bounds__(kEntryThreads) void bpr_indptr_kernel(const unsigned *__restrict__ key_sorted, int nnz, int cols,
-                                                                   int *__restrict__ n_indptr) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i <= cols; i += gridDim.x * blockDim.x)
-        n_indptr[i] = first_at_least(key_sorted, 0, nnz, static_cast<unsigned>(i));
 }
 
 struct BprRowArgs {
@@ -228,18 +209,10 @@ __global__ __launch_bounds__(kObjThreads) void bpr_objective_kernel(BprProblem p
         for (int j = 0; j < 6; ++j) partials[6 * blockIdx.x + j] = red[j][0];
 }
 
-unsigned key_bits(int top) {  // bits that hold every key in [0, top]
-    unsigned bits = 1;
-    while (bits < 32 && (1ull << bits) <= static_cast<unsigned long long>(top)) ++bits;
-    return bits;
-}
-
-// once per CSR: every row's items ascending (a segmented radix sort) and the buffers of its size
-void build(BprCache &c, const BprProblem &p, hipStream_t stream) {
-    if (c.built) return;
+// once per CSR: the buffers of its size
+void allocate(BprCache &c, const BprProblem &p, hipStream_t stream) {
+    if (c.allocated) return;
     const size_t n = static_cast<size_t>(std::max(p.nnz, 1));
-    c.sorted.allocate(n);
-    c.row_of.allocate(n);
     c.iota.allocate(n);
     c.neg.allocate(n);
     c.neg_key.allocate(n);
@@ -247,50 +220,34 @@ void build(BprCache &c, const BprProblem &p, hipStream_t stream) {
     c.neg_e.allocate(n);
     c.coef.allocate(n);
     c.n_indptr.allocate(static_cast<size_t>(p.cols) + 1);
-    if (p.nnz > 0) {
-        const unsigned bits = key_bits(std::max(p.cols - 1, 1));
-        const unsigned *keys = reinterpret_cast<const unsigned *>(p.indices);
-        unsigned *out = reinterpret_cast<unsigned *>(c.sorted.ptr);
-        with_rocprim_temp(c.sort_temp, [&](void *temp, size_t &bytes) {
-            return rocprim::segmented_radix_sort_keys(temp, bytes, keys, out, static_cast<unsigned>(p.nnz), static_cast<unsigned>(p.rows),
-                                                      p.indptr, p.indptr + 1, 0u, bits, stream);
-        });
-        hipLaunchKernelGGL(bpr_iota_kernel, dim3(entry_grid(p.nnz)), dim3(kEntryThreads), 0, stream, c.iota.ptr, p.nnz);
-        CU2REC_HIP(hipGetLastError());
-    }
-    c.built = true;
+    fill_iota(c.iota.ptr, p.nnz, stream);
+    c.allocated = true;
 }
 
 // once per (seed, sweep): the entries by ascending (j_e, e) and every item's first position among them
 void regroup(BprCache &c, const BprProblem &p, hipStream_t stream) {
     if (c.grouped) return;
-    if (p.nnz > 0) {
-        const unsigned bits = key_bits(p.cols);  // -1 sorts as `cols`
-        with_rocprim_temp(c.sort_temp, [&](void *temp, size_t &bytes) {
-            return rocprim::radix_sort_pairs(temp, bytes, c.neg_key.ptr, c.key_sorted.ptr, c.iota.ptr, c.neg_e.ptr,
-                                             static_cast<size_t>(p.nnz), 0u, bits, stream);
-        });
-    }
-    hipLaunchKernelGGL(bpr_indptr_kernel, dim3(entry_grid(static_cast<size_t>(p.cols) + 1)), dim3(kEntryThreads), 0, stream,
-                       c.key_sorted.ptr, p.nnz, p.cols, c.n_indptr.ptr);
-    CU2REC_HIP(hipGetLastError());
+    sort_pairs_into_groups(c.sort_temp, c.neg_key.ptr, c.key_sorted.ptr, c.iota.ptr, c.neg_e.ptr, p.nnz, key_bits(p.cols) /* -1 sorts as `cols` */,
+                           p.cols, c.n_indptr.ptr, stream);
     c.grouped = true;
 }
 
-BprRowArgs row_args(BprCache &c, const BprProblem &p, float *grad, int ldg) {
-    return {p, c.neg.ptr, c.row_of.ptr, c.neg_e.ptr, c.n_indptr.ptr, c.coef.ptr, grad, ldg};
+BprRowArgs row_args(const DeviceCsr &train, const BprProblem &p, float *grad, int ldg, hipStream_t stream) {
+    const BprCache &c = train.bpr;
+    return {p, c.neg.ptr, row_of_view(train, stream), c.neg_e.ptr, c.n_indptr.ptr, c.coef.ptr, grad, ldg};
 }
 
 }  // namespace
 
-void bpr_negatives(BprCache &c, const BprProblem &p, uint64_t seed, int sweep, hipStream_t stream) {
-    build(c, p, stream);
+void bpr_negatives(const DeviceCsr &train, const BprProblem &p, uint64_t seed, int sweep, hipStream_t stream) {
+    BprCache &c = train.bpr;
+    allocate(c, p, stream);
     if (c.have_neg && c.seed == seed && c.sweep == sweep) return;
-    const bool have_row_of = c.have_neg;  // any earlier call wrote it
     c.have_neg = c.grouped = false;
+    const int *row_of = row_of_view(train, stream), *sorted = row_sorted_view(train, false, stream).idx.ptr;
     if (p.nnz > 0) {
-        hipLaunchKernelGGL(bpr_negatives_kernel, dim3(entry_grid(p.nnz)), dim3(kEntryThreads), 0, stream, p.indptr, c.sorted.ptr, p.rows,
-                           p.cols, p.nnz, seed, static_cast<uint32_t>(sweep), have_row_of, c.row_of.ptr, c.neg.ptr, c.neg_key.ptr);
+        hipLaunchKernelGGL(bpr_negatives_kernel, dim3(element_grid(p.nnz)), dim3(kElementThreads), 0, stream, p.indptr, sorted, row_of, p.cols,
+                           p.nnz, seed, static_cast<uint32_t>(sweep), c.neg.ptr, c.neg_key.ptr);
         CU2REC_HIP(hipGetLastError());
     }
     c.seed = seed;
@@ -298,19 +255,19 @@ void bpr_negatives(BprCache &c, const BprProblem &p, uint64_t seed, int sweep, h
     c.have_neg = true;
 }
 
-void bpr_user_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, hipStream_t stream) {
+void bpr_user_gradient(const DeviceCsr &train, const BprProblem &p, float *grad, int ldg, hipStream_t stream) {
     if (p.rows <= 0) return;
-    const BprRowArgs a = row_args(c, p, grad, ldg);
+    const BprRowArgs a = row_args(train, p, grad, ldg, stream);
     dispatch_1_to_4(p.n_factors + 1, [&](auto elems) {
         hipLaunchKernelGGL((bpr_user_kernel<elems(), false>), dim3(row_grid(p.rows)), dim3(kRowThreads), 0, stream, a);
     });
     CU2REC_HIP(hipGetLastError());
 }
 
-void bpr_item_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, hipStream_t stream) {
+void bpr_item_gradient(const DeviceCsr &train, const BprProblem &p, float *grad, int ldg, hipStream_t stream) {
     if (p.cols <= 0) return;
-    regroup(c, p, stream);
-    const BprRowArgs a = row_args(c, p, grad, ldg);
+    regroup(train.bpr, p, stream);
+    const BprRowArgs a = row_args(train, p, grad, ldg, stream);
     dispatch_1_to_4(p.n_factors + 1, [&](auto elems) {
         if (p.rows > 0 && p.nnz > 0)
             hipLaunchKernelGGL((bpr_user_kernel<elems(), true>), dim3(row_grid(p.rows)), dim3(kRowThreads), 0, stream, a);
@@ -319,10 +276,11 @@ void bpr_item_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, h
     CU2REC_HIP(hipGetLastError());
 }
 
-void bpr_objective(BprCache &c, const BprProblem &p, double (&out)[6], hipStream_t stream) {
+void bpr_objective(const DeviceCsr &train, const BprProblem &p, double (&out)[6], hipStream_t stream) {
+    BprCache &c = train.bpr;
     const int blocks = objective_blocks(static_cast<size_t>(std::max(p.nnz, std::max(p.rows, p.cols))));
     if (c.partials.count < 6 * static_cast<size_t>(blocks)) c.partials.allocate(6 * static_cast<size_t>(blocks));
-    hipLaunchKernelGGL(bpr_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, p, c.neg.ptr, c.row_of.ptr, c.partials.ptr);
+    hipLaunchKernelGGL(bpr_objective_kernel, dim3(blocks), dim3(kObjThreads), 0, stream, p, c.neg.ptr, row_of_view(train, stream), c.partials.ptr);
     CU2REC_HIP(hipGetLastError());
     sum_block_partials(c.partials, blocks, out, stream);
 }

@@ -14,10 +14,13 @@ namespace cu2rec {
 constexpr int kBprAttempts = 8;          // draws per entry and sweep before the entry goes without a triple
 constexpr int kBprMaxSweep = 1 << 29;    // sweep * kBprAttempts + attempt fills the high word of the sampler's iteration
 
-// Cached on a cu2rec_csr.  Built once: `sorted` (the CSR's indices, every row ascending -- the membership test's haystack) and
-// `row_of`.  Per (seed, sweep): the negatives, and for the item half-step their regrouping by item and the entries' coefficients.
+struct DeviceCsr;
+
+// Cached on a cu2rec_csr, per (seed, sweep): the negatives, and for the item half-step their regrouping by item and the entries'
+// coefficients.  The rows' ascending items (the membership test's haystack), the row of every entry and the item-major view are the
+// CSR's own views (csr_views.hpp).
 struct BprCache {
-    DeviceBuffer<int> sorted, row_of, iota;
+    DeviceBuffer<int> iota;           // [nnz]: the entries in CSR order, the regrouping sort's values
     DeviceBuffer<int> neg;            // [nnz]: j_e, or -1 where all attempts were stored items
     DeviceBuffer<unsigned> neg_key;   // [nnz]: j_e, or cols for -1 (sorts past the end)
     DeviceBuffer<unsigned> key_sorted;
@@ -26,12 +29,12 @@ struct BprCache {
     DeviceBuffer<float> coef;         // [nnz]: sigma(-x_e) at the current model
     DeviceBuffer<unsigned char> sort_temp;
     DeviceBuffer<double> partials;
-    bool built = false, have_neg = false, grouped = false;
+    bool allocated = false, have_neg = false, grouped = false;
     uint64_t seed = 0;
     int sweep = -1;
 };
 
-// The model and the CSR as the kernels read them.  t_*: the item-major view of als.hip (the item half-step only).
+// The model and the CSR as the kernels read them.  t_*: the CSR's item-major view (the item half-step only).
 struct BprProblem {
     const int *indptr, *indices;
     int rows, cols, nnz;
@@ -45,15 +48,15 @@ struct BprProblem {
     float P_reg, Q_reg, item_bias_reg;
 };
 
-// c.neg (and c.neg_key) for (seed, sweep); a repeated call for the same pair is free
-void bpr_negatives(BprCache &c, const BprProblem &p, uint64_t seed, int sweep, hipStream_t stream);
+// train.bpr.neg (and neg_key) for (seed, sweep); a repeated call for the same pair is free
+void bpr_negatives(const DeviceCsr &train, const BprProblem &p, uint64_t seed, int sweep, hipStream_t stream);
 // grad[u][0 .. f] of every user u < p.rows, row stride ldg; column f, the bias', is a zero.  Needs bpr_negatives
-void bpr_user_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, hipStream_t stream);
+void bpr_user_gradient(const DeviceCsr &train, const BprProblem &p, float *grad, int ldg, hipStream_t stream);
 // grad[i][0 .. f] of every item i < p.cols (column f: the bias'): regroups the negatives by item once per (seed, sweep), writes
-// c.coef at the current model, then sums.  Needs bpr_negatives
-void bpr_item_gradient(BprCache &c, const BprProblem &p, float *grad, int ldg, hipStream_t stream);
+// the coefficients at the current model, then sums.  Needs bpr_negatives
+void bpr_item_gradient(const DeviceCsr &train, const BprProblem &p, float *grad, int ldg, hipStream_t stream);
 // out[6] = {sum over triples of ln sigma(x_e), sum |p_u|^2, sum |q_i|^2, sum ib_i^2, triples, triples with x_e > 0}, in double
 // (synchronises).  Needs bpr_negatives
-void bpr_objective(BprCache &c, const BprProblem &p, double (&out)[6], hipStream_t stream);
+void bpr_objective(const DeviceCsr &train, const BprProblem &p, double (&out)[6], hipStream_t stream);
 
 }  // namespace cu2rec

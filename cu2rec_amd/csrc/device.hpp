@@ -11,6 +11,7 @@
 
 #include "als.hpp"
 #include "bpr.hpp"
+#include "csr_views.hpp"
 #include "hip_check.hpp"
 #include "knn.hpp"
 #include "lmf.hpp"
@@ -86,17 +87,14 @@ struct DeviceCsr {
     int users_with_ratings;
     mutable std::unique_ptr<OrderedSchedule> schedule;  // created on first CU2REC_SGD_ORDERED use
     mutable DeviceBuffer<uint2> pairs;                   // sample array, created on first Hogwild use (SgdArgs::pairs)
-    mutable std::unique_ptr<AlsCache> als;               // item-major view and row plans, created on first ALS use
-    mutable std::unique_ptr<BprCache> bpr;               // row-sorted items and the current sweep's negatives, created on first BPR use
-    mutable std::unique_ptr<KnnRows> knn_rows;           // row-sorted (column, value) pairs, created on first ItemKNN use
+    mutable CsrViews views;                              // item-major, row-sorted and row-of-entry views, each built on first request
+    mutable AlsCache als;                                // the ALS row plans and workspaces
+    mutable BprCache bpr;                                // the current sweep's negatives and their regrouping
 };
 
-// The rows one ALS half-step solves, as it reads them: the CSR itself for the users, its item-major view for the items -- built on
-// the device, and either side planned, the first time it is asked for (device_trainers.cpp).
+// The rows one ALS half-step solves, as it reads them: the CSR itself for the users, its item-major view for the items, planned the
+// first time the side is asked for (device_trainers.cpp).
 AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream);
-// The item-major view alone (c.items' indptr / indices / data and c.t_pos), built the first time it is asked for and shared with
-// als_side; the ALS row plan is left to the first ALS call.  What the ItemKNN build reads (knn.hip).
-AlsCache &item_major_view(const DeviceCsr &train, hipStream_t stream);
 
 // P, Q, biases on the device with padded rows (see include/cu2rec_amd.h "Device data layout").
 struct DeviceModel {

@@ -8,44 +8,27 @@
 
 namespace cu2rec {
 
-// device.hpp: the item-major view alone, built on the device once per rating matrix; nothing is planned
-AlsCache &item_major_view(const DeviceCsr &train, hipStream_t stream) {
-    if (!train.als) train.als.reset(new AlsCache);
-    AlsCache &c = *train.als;
-    if (!c.items_built) {
-        als_build_transpose(c, train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz, stream);
-        c.items.indptr = c.t_indptr.ptr;
-        c.items.indices = c.t_indices.ptr;
-        c.items.data = c.t_data.ptr;
-        c.items.rows = train.cols;
-        c.items.nnz = train.nnz;
-        c.items_built = true;
-    }
-    return c;
+namespace {
+// One side's rows as every full-batch trainer reads them: the CSR itself for the users, its item-major view for the items.
+RatingsRef side_rows(const DeviceCsr &train, bool users, hipStream_t stream) {
+    if (users) return train.ref();
+    const ItemMajorView &v = item_major_view(train, stream);
+    return {v.indptr.ptr, v.indices.ptr, v.data.ptr, train.cols};
 }
+}  // namespace
 
 // device.hpp: the rows one ALS half-step solves, as it reads them
 AlsSide &als_side(const DeviceCsr &train, bool users, hipStream_t stream) {
-    if (!train.als) train.als.reset(new AlsCache);
-    AlsCache &c = *train.als;
-    if (users) {
-        if (!c.users_ready) {
-            c.users.indptr = train.indptr.ptr;
-            c.users.indices = train.indices.ptr;
-            c.users.data = train.data.ptr;
-            c.users.rows = train.rows;
-            c.users.nnz = train.nnz;
-            als_plan_side(c.users, stream);
-            c.users_ready = true;
-        }
-        return c.users;
+    AlsSide &side = users ? train.als.users : train.als.items;
+    if (!side.planned) {
+        const RatingsRef r = side_rows(train, users, stream);
+        side.indptr = r.indptr;
+        side.indices = r.indices;
+        side.data = r.data;
+        side.rows = r.n_rows;
+        als_plan_side(side, stream);
     }
-    if (!c.items_ready) {
-        item_major_view(train, stream);
-        als_plan_side(c.items, stream);
-        c.items_ready = true;
-    }
-    return c.items;
+    return side;
 }
 
 namespace {
@@ -95,7 +78,7 @@ int als_half_step_of(DeviceModel &m, AlsKind kind, const DeviceCsr &train, const
         p.alpha = alpha;
         p.x_rows = users ? train.cols : train.rows;  // every partner row inside the CSR counts
     }
-    const int unsolved = (implicit ? ials_half_step : als_half_step)(*train.als, rows_of_side, p, users ? m.rows : m.cols, stream, cg_steps);
+    const int unsolved = (implicit ? ials_half_step : als_half_step)(train.als, rows_of_side, p, users ? m.rows : m.cols, stream, cg_steps);
     m.other_in_sync = false;  // Q moved on without the ping-pong pair
     return unsolved;
 }
@@ -116,10 +99,9 @@ double DeviceModel::implicit_objective(const DeviceCsr &train, const cu2rec_hype
     need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": ratings exceed the model's shape");
     need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
     enter(*this);
-    if (!train.als) train.als.reset(new AlsCache);
     const AlsObjectiveProblem o{train.indptr.ptr, train.indices.ptr, train.data.ptr, train.rows, train.cols, train.nnz,
                                 P.ptr, ld, Q.ptr, ldq, n_factors, alpha, h.P_reg, h.Q_reg};
-    return ials_objective(*train.als, o, stream);
+    return ials_objective(train.als, o, stream);
 }
 
 // Logistic matrix factorization and Bayesian Personalized Ranking (include/cu2rec_amd.h: cu2rec_model_lmf, cu2rec_model_bpr).  The
@@ -154,11 +136,11 @@ int DeviceModel::adagrad_half_step(const LmfProblem &p, bool users, hipStream_t 
 }
 
 namespace {
-// the half-step's view of one side; the item side reads the item-major view cached on the CSR by the ALS calls
+// the half-step's view of one side
 LmfProblem lmf_problem(DeviceModel &m, const DeviceCsr &train, const cu2rec_hyper &h, float alpha, bool users, hipStream_t stream) {
-    const AlsSide &s = als_side(train, users, stream);
+    const RatingsRef s = side_rows(train, users, stream);
     const SideView v = side_view(m, users);
-    return {s.indptr, s.indices, s.data, v.own, v.ld_own, v.own_bias, users ? train.rows : train.cols, v.partner, v.ld_partner,
+    return {s.indptr, s.indices, s.data, v.own, v.ld_own, v.own_bias, s.n_rows, v.partner, v.ld_partner,
             v.partner_bias, users ? train.cols : train.rows, m.n_factors, m.global_bias, alpha, users ? h.P_reg : h.Q_reg,
             users ? h.user_bias_reg : h.item_bias_reg, h.learning_rate};
 }
@@ -205,17 +187,16 @@ double DeviceModel::lmf_objective(const DeviceCsr &train, const cu2rec_hyper &h,
 }
 
 namespace {
-// the kernels' view; items: with the item-major view cached on the CSR by the ALS calls
+// the kernels' view; items: with the CSR's item-major view
 BprProblem bpr_problem(DeviceModel &m, const DeviceCsr &train, const cu2rec_hyper &h, bool items, hipStream_t stream) {
     BprProblem p{train.indptr.ptr, train.indices.ptr, train.rows, train.cols, train.nnz, nullptr, nullptr, nullptr, m.P.ptr, m.ld,
                  m.Q.ptr, m.ldq, m.item_bias.ptr, m.n_factors, h.P_reg, h.Q_reg, h.item_bias_reg};
     if (items) {
-        const AlsSide &s = als_side(train, false, stream);
-        p.t_indptr = s.indptr;
-        p.t_indices = s.indices;
-        p.t_pos = train.als->t_pos.ptr;
+        const ItemMajorView &v = item_major_view(train, stream);
+        p.t_indptr = v.indptr.ptr;
+        p.t_indices = v.indices.ptr;
+        p.t_pos = v.pos.ptr;
     }
-    if (!train.bpr) train.bpr.reset(new BprCache);
     return p;
 }
 
@@ -224,8 +205,8 @@ void bpr_gradient_into(LmfState &st, const DeviceCsr &train, const BprProblem &p
     const int ldg = 32 * lmf_tiles(p.n_factors);
     const size_t need = static_cast<size_t>(std::max(users ? p.rows : p.cols, 1)) * ldg;
     if (st.grad.count < need) st.grad.allocate(need);
-    bpr_negatives(*train.bpr, p, seed, sweep, stream);
-    (users ? bpr_user_gradient : bpr_item_gradient)(*train.bpr, p, st.grad.ptr, ldg, stream);
+    bpr_negatives(train, p, seed, sweep, stream);
+    (users ? bpr_user_gradient : bpr_item_gradient)(train, p, st.grad.ptr, ldg, stream);
 }
 }  // namespace
 
@@ -255,9 +236,9 @@ double DeviceModel::bpr_objective(const DeviceCsr &train, const cu2rec_hyper &h,
     logistic_check("cu2rec_model_bpr_objective", train, h, {}, {}, sweep);
     enter(*this);
     const BprProblem p = bpr_problem(*this, train, h, false, stream);
-    bpr_negatives(*train.bpr, p, seed, sweep, stream);
+    bpr_negatives(train, p, seed, sweep, stream);
     double s[6];
-    cu2rec::bpr_objective(*train.bpr, p, s, stream);
+    cu2rec::bpr_objective(train, p, s, stream);
     if (n_triples) *n_triples = static_cast<long long>(s[4]);
     if (n_ordered) *n_ordered = static_cast<long long>(s[5]);
     return s[0] - 0.5 * (static_cast<double>(h.P_reg) * s[1] + static_cast<double>(h.Q_reg) * s[2] + static_cast<double>(h.item_bias_reg) * s[3]);
@@ -384,12 +365,11 @@ int cu2rec_csr_bpr_negatives(const cu2rec_csr *train, uint64_t seed, int sweep, 
         Need{"cu2rec_csr_bpr_negatives"}(sweep >= 0 && sweep < kBprMaxSweep, CU2REC_EINVAL, ": sweep must be in [0, 2^29)");
         const DeviceCsr &t = train->impl;
         require_device();
-        if (!t.bpr) t.bpr.reset(new BprCache);
         const BprProblem p{t.indptr.ptr, t.indices.ptr, t.rows, t.cols, t.nnz, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr,
                            0, 0.f, 0.f, 0.f};
-        bpr_negatives(*t.bpr, p, seed, sweep, nullptr);
+        bpr_negatives(t, p, seed, sweep, nullptr);
         CU2REC_HIP(hipStreamSynchronize(nullptr));
-        if (t.nnz) t.bpr->neg.download(neg_out, t.nnz);
+        if (t.nnz) t.bpr.neg.download(neg_out, t.nnz);
     });
 }
 

@@ -18,9 +18,6 @@
 // in ascending item-major position and then down a fixed shuffle tree, bm25's mean over the columns in one workgroup.
 #include <hip/hip_runtime.h>
 
-#include <cstring>  // (rocPRIM's headers call memset without including it)
-#include <rocprim/rocprim.hpp>
-
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -40,70 +37,6 @@ constexpr int kSlice = kKnnSliceItems;
 constexpr int kSliceWords = kSlice / 32;
 constexpr int kChunk = 256;  // candidates that enter one sort beside the best 256 so far
 static_assert(kSliceWords == 64 && kSlice % kChunk == 0, "one bitmap word per lane; whole chunks");
-
-int grid_for(size_t n, int threads = 256, int cap = 8192) {
-    return static_cast<int>(std::max<size_t>(1, std::min<size_t>((n + threads - 1) / threads, cap)));
-}
-
-// ---- the row-sorted copy ---------------------------------------------------------------------------------------------------
-__global__ void knn_iota_kernel(int *__restrict__ x, int n) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) x[i] = i;
-}
-
-__global__ void knn_gather_kernel(const float *__restrict__ src, const int *__restrict__ pos, int n, float *__restrict__ out) {
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = src[pos[i]];
-}
-
-// one wavefront per row of the sorted copy: a column equal to the one before it is a repeated entry
-__global__ __launch_bounds__(256) void knn_duplicate_kernel(const int *__restrict__ indptr, const int *__restrict__ idx, int rows,
-                                                            int *__restrict__ flag) {
-    const int lane = threadIdx.x & 63;
-    for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += gridDim.x * 4) {
-        const int lo = indptr[row], hi = indptr[row + 1];
-        for (int e = lo + 1 + lane; e < hi; e += 64)
-            if (idx[e] == idx[e - 1]) atomicOr(flag, 1);
-    }
-}
-
-unsigned key_bits(int top) {  // bits that hold every key in [0, top]
-    unsigned bits = 1;
-    while (bits < 32 && (1ull << bits) <= static_cast<unsigned long long>(top)) ++bits;
-    return bits;
-}
-
-const KnnRows &knn_rows(const DeviceCsr &m, hipStream_t stream) {
-    if (m.knn_rows) return *m.knn_rows;
-    std::unique_ptr<KnnRows> r(new KnnRows);
-    const size_t n = static_cast<size_t>(std::max(m.nnz, 1));
-    r->idx.allocate(n);
-    r->pos.allocate(n);
-    r->val.allocate(n);
-    if (m.nnz > 0) {
-        DeviceBuffer<int> iota(n), flag(1);
-        DeviceBuffer<unsigned char> temp;
-        hipLaunchKernelGGL(knn_iota_kernel, dim3(grid_for(n)), dim3(256), 0, stream, iota.ptr, m.nnz);
-        CU2REC_HIP(hipGetLastError());
-        const unsigned bits = key_bits(std::max(m.cols - 1, 1));
-        const unsigned *keys = reinterpret_cast<const unsigned *>(m.indices.ptr);
-        unsigned *keys_out = reinterpret_cast<unsigned *>(r->idx.ptr);
-        with_rocprim_temp(temp, [&](void *t, size_t &bytes) {
-            return rocprim::segmented_radix_sort_pairs(t, bytes, keys, keys_out, iota.ptr, r->pos.ptr, static_cast<unsigned>(m.nnz),
-                                                       static_cast<unsigned>(m.rows), m.indptr.ptr, m.indptr.ptr + 1, 0u, bits, stream);
-        });
-        hipLaunchKernelGGL(knn_gather_kernel, dim3(grid_for(n)), dim3(256), 0, stream, m.data.ptr, r->pos.ptr, m.nnz, r->val.ptr);
-        CU2REC_HIP(hipGetLastError());
-        CU2REC_HIP(hipMemsetAsync(flag.ptr, 0, sizeof(int), stream));
-        hipLaunchKernelGGL(knn_duplicate_kernel, dim3(grid_for(static_cast<size_t>(m.rows), 4)), dim3(256), 0, stream, m.indptr.ptr,
-                           r->idx.ptr, m.rows, flag.ptr);
-        CU2REC_HIP(hipGetLastError());
-        int dup = 0;
-        CU2REC_HIP(hipMemcpyAsync(&dup, flag.ptr, sizeof(int), hipMemcpyDeviceToHost, stream));
-        CU2REC_HIP(hipStreamSynchronize(stream));  // before the temporaries are freed
-        r->has_duplicate = dup != 0;
-    }
-    m.knn_rows = std::move(r);
-    return *m.knn_rows;
-}
 
 // ---- the weights -----------------------------------------------------------------------------------------------------------
 __global__ void knn_idf_kernel(const int *__restrict__ indptr, int rows, int cols, double *__restrict__ idf) {
@@ -388,9 +321,9 @@ std::vector<int> query_ids(const int *ids, int n_ids, int rows, const char *who)
 
 void check_k(const char *what, int k, int top) { require(k >= 1 && k <= top, what); }
 
-// the recommend product over `history` (its row-sorted copy) and the model's id-sorted lists
+// the recommend product over `history` (its row-sorted view) and the model's id-sorted lists
 KnnProduct recommend_product(const DeviceKnn &m, const DeviceCsr &history, const DeviceCsr *exclude, int k, hipStream_t stream) {
-    const KnnRows &rows = knn_rows(history, stream);
+    const RowSortedView &rows = row_sorted_view(history, true, stream);
     if (rows.has_duplicate) fail(CU2REC_EINVAL, "cu2rec_knn: a history row stores the same column twice");
     const bool ex = exclude && exclude->nnz > 0;
     return KnnProduct{history.indptr.ptr, history.indptr.ptr + 1, rows.idx.ptr, rows.val.ptr, m.s_begin.ptr, m.s_end.ptr, m.s_idx.ptr,
@@ -411,19 +344,17 @@ void knn_check_weighting(const char *fn, int weighting, float k1, float b) {
 
 void knn_weights(const DeviceCsr &csr, int weighting, float k1, float b, float *w, float *t_w, hipStream_t stream) {
     if (csr.nnz == 0) return;
-    const AlsCache &view = item_major_view(csr, stream);
-    const AlsSide &side = view.items;
-    const int *t_pos = view.t_pos.ptr;
+    const ItemMajorView &view = item_major_view(csr, stream);
     DeviceBuffer<double> idf(std::max(csr.rows, 1)), sums(std::max(csr.cols, 1)), mean(1);
     if (weighting == CU2REC_KNN_TFIDF || weighting == CU2REC_KNN_BM25)  // the other two never read it
-        hipLaunchKernelGGL(knn_idf_kernel, dim3(grid_for(static_cast<size_t>(csr.rows))), dim3(256), 0, stream, csr.indptr.ptr, csr.rows,
+        hipLaunchKernelGGL(knn_idf_kernel, dim3(element_grid(static_cast<size_t>(csr.rows))), dim3(256), 0, stream, csr.indptr.ptr, csr.rows,
                            csr.cols, idf.ptr);
     if (weighting != CU2REC_KNN_COUNT)
-        hipLaunchKernelGGL(knn_column_sums_kernel, dim3(grid_for(static_cast<size_t>(csr.cols), 4)), dim3(256), 0, stream, side.indptr,
-                           side.indices, side.data, idf.ptr, csr.cols, weighting, sums.ptr);
+        hipLaunchKernelGGL(knn_column_sums_kernel, dim3(element_grid(static_cast<size_t>(csr.cols), 4)), dim3(256), 0, stream, view.indptr.ptr,
+                           view.indices.ptr, view.data.ptr, idf.ptr, csr.cols, weighting, sums.ptr);
     if (weighting == CU2REC_KNN_BM25) hipLaunchKernelGGL(knn_mean_kernel, dim3(1), dim3(256), 0, stream, sums.ptr, csr.cols, mean.ptr);
-    hipLaunchKernelGGL(knn_weights_kernel, dim3(grid_for(static_cast<size_t>(csr.nnz))), dim3(256), 0, stream, csr.indices.ptr,
-                       side.indices, side.data, t_pos, idf.ptr, sums.ptr, mean.ptr, csr.nnz, weighting, static_cast<double>(k1),
+    hipLaunchKernelGGL(knn_weights_kernel, dim3(element_grid(static_cast<size_t>(csr.nnz))), dim3(256), 0, stream, csr.indices.ptr,
+                       view.indices.ptr, view.data.ptr, view.pos.ptr, idf.ptr, sums.ptr, mean.ptr, csr.nnz, weighting, static_cast<double>(k1),
                        static_cast<double>(b), w, t_w);
     CU2REC_HIP(hipGetLastError());
     CU2REC_HIP(hipStreamSynchronize(stream));  // before the temporaries are freed
@@ -438,24 +369,23 @@ DeviceKnn::DeviceKnn(const DeviceCsr &train, int weighting_, float k1, float b, 
     require_device();
     check_faults();
     hipStream_t stream = nullptr;
-    const KnnRows &rows = knn_rows(train, stream);
+    const RowSortedView &rows = row_sorted_view(train, true, stream);
     if (rows.has_duplicate) fail(CU2REC_EINVAL, "cu2rec_knn_create: a row stores the same column twice");
     const size_t nnz = static_cast<size_t>(std::max(train.nnz, 1)), total = static_cast<size_t>(items) * neighbours;
     DeviceBuffer<float> w(nnz), t_w(nnz), sw(nnz);
     knn_weights(train, weighting, k1, b, w.ptr, t_w.ptr, stream);
-    const AlsSide &side = item_major_view(train, stream).items;
-    if (train.nnz > 0) hipLaunchKernelGGL(knn_gather_kernel, dim3(grid_for(nnz)), dim3(256), 0, stream, w.ptr, rows.pos.ptr, train.nnz, sw.ptr);
+    const ItemMajorView &view = item_major_view(train, stream);
+    gather(w.ptr, rows.pos.ptr, train.nnz, sw.ptr, stream);
     ids.allocate(total);
     sims.allocate(total);
     s_begin.allocate(items);
     s_end.allocate(items);
     s_idx.allocate(total);
     s_val.allocate(total);
-    const KnnProduct build{side.indptr, side.indptr + 1, side.indices, t_w.ptr, train.indptr.ptr, train.indptr.ptr + 1, rows.idx.ptr,
+    const KnnProduct build{view.indptr.ptr, view.indptr.ptr + 1, view.indices.ptr, t_w.ptr, train.indptr.ptr, train.indptr.ptr + 1, rows.idx.ptr,
                            sw.ptr, nullptr, nullptr, 0, items, slices_of(items), 1, neighbours};
     DeviceBuffer<int> d_all(items);
-    hipLaunchKernelGGL(knn_iota_kernel, dim3(grid_for(static_cast<size_t>(items))), dim3(256), 0, stream, d_all.ptr, items);
-    CU2REC_HIP(hipGetLastError());
+    fill_iota(d_all.ptr, items, stream);
     ProductRunner run(build, items);
     for (int p0 = 0; p0 < items; p0 += run.batch)  // stream order: a batch's merge is done before the next product overwrites the keys
         run.run(d_all.ptr + p0, std::min(run.batch, items - p0), neighbours, ids.ptr + static_cast<size_t>(p0) * neighbours,
@@ -477,7 +407,7 @@ void DeviceKnn::neighbors(const int *ids_in, int n_ids, int k, int *out_ids, flo
     DeviceBuffer<int> d_q(q.size()), d_ids(total);
     DeviceBuffer<float> d_sims(total);
     d_q.upload(q.data(), q.size());
-    hipLaunchKernelGGL(knn_take_kernel, dim3(grid_for(total)), dim3(256), 0, stream, ids.ptr, sims.ptr, neighbours, d_q.ptr,
+    hipLaunchKernelGGL(knn_take_kernel, dim3(element_grid(total)), dim3(256), 0, stream, ids.ptr, sims.ptr, neighbours, d_q.ptr,
                        static_cast<int>(q.size()), k, d_ids.ptr, d_sims.ptr);
     CU2REC_HIP(hipGetLastError());
     d_ids.download(out_ids, total);
@@ -526,8 +456,7 @@ void DeviceKnn::rank_metrics(const DeviceCsr &history, const DeviceCsr *exclude,
     hipStream_t stream = nullptr;
     const int n = test.rows;  // rows past the test set's last row have no relevant items
     DeviceBuffer<int> d_all(std::max(n, 1));
-    hipLaunchKernelGGL(knn_iota_kernel, dim3(grid_for(static_cast<size_t>(n))), dim3(256), 0, stream, d_all.ptr, n);
-    CU2REC_HIP(hipGetLastError());
+    fill_iota(d_all.ptr, n, stream);
     ProductRunner run(recommend_product(*this, history, exclude, k, stream), n);
     // the stage's own workspace per row counts against the same budget
     const size_t per_row = (static_cast<size_t>(run.a.n_slices) + 1) * k * 8 + RankStage::bytes_per_row(items);

@@ -14,14 +14,6 @@ constexpr int kKnnSliceItems = 2048;  // candidate ids one wavefront accumulates
 constexpr int kKnnMaxK = CU2REC_KNN_MAX_NEIGHBOURS;
 constexpr size_t kKnnWorkspaceBytes = CU2REC_KNN_WORKSPACE_BYTES;  // per batch of queries
 
-// Cached on a cu2rec_csr, made on first use: every row's (column, value) by ascending column -- a segmented radix sort of the
-// columns that carries the entry positions along -- and whether some row stores a column twice (seen on the sorted copy).
-struct KnnRows {
-    DeviceBuffer<int> idx, pos;  // sorted columns; the CSR position of each
-    DeviceBuffer<float> val;     // data[pos]
-    bool has_duplicate = false;
-};
-
 // The model behind a cu2rec_knn handle.
 struct DeviceKnn {
     DeviceKnn(const DeviceCsr &train, int weighting, float k1, float b, int neighbours);
@@ -39,7 +31,7 @@ struct DeviceKnn {
 };
 
 // the weights of every stored entry (include/cu2rec_amd.h) into w (device, CSR entry order) and, if not null, into t_w (device,
-// the item-major order of the CSR's AlsCache); the arguments are checked by the caller
+// the order of the CSR's item-major view, csr_views.hpp); the arguments are checked by the caller
 void knn_weights(const DeviceCsr &csr, int weighting, float k1, float b, float *w, float *t_w, hipStream_t stream);
 // the argument checks cu2rec_knn_create and cu2rec_csr_knn_weights share; fn names the caller
 void knn_check_weighting(const char *fn, int weighting, float k1, float b);

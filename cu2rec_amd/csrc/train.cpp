@@ -79,7 +79,7 @@ void train(const DeviceCsr &train_csr, const DeviceCsr &test_csr, cu2rec_config 
             [&](const cu2rec_hyper &h, uint64_t, int n, hipStream_t s) {
                 solved += sweeps(n, cfg.is_train, [&](int side, int) {
                     const int unsolved = model.als(train_csr, h, side, s, cg_steps);
-                    return (side == CU2REC_SIDE_USERS ? train_csr.als->users : train_csr.als->items).rows_with_ratings - unsolved;
+                    return als_side(train_csr, side == CU2REC_SIDE_USERS, s).rows_with_ratings - unsolved;
                 });
             },
             [&](bool on_train, float *mae, float *rmse) {
@@ -113,7 +113,7 @@ void train_implicit(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel 
         "implicit", cfg, verbose, objectives, stats,
         [&](const cu2rec_hyper &h, int side, hipStream_t s, uint64_t) {
             const int unsolved = model.ials(train_csr, h, alpha, side, s, cg_steps);
-            return (side == CU2REC_SIDE_USERS ? train_csr.als->users : train_csr.als->items).rows_with_ratings - unsolved;
+            return als_side(train_csr, side == CU2REC_SIDE_USERS, s).rows_with_ratings - unsolved;
         },
         [&](const cu2rec_hyper &h, uint64_t) { return model.implicit_objective(train_csr, h, alpha, nullptr); });
 }

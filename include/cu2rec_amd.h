@@ -602,7 +602,7 @@ int cu2rec_model_lmf_reset(cu2rec_model *m);
  * and the first j that row u does not store is the entry's negative j_e; if all eight are stored items the entry has no triple in
  * this sweep (j_e = -1) and contributes nothing anywhere.  The draw depends on seed, u, k, t, I and the row's own set of items only.
  * Rows may be unsorted and hold repeats: the membership test is exact (a binary search of a row-sorted copy of the indices, cached
- * on the cu2rec_csr by the first BPR call, as the ALS calls cache the item-major view).  Both half-steps of a sweep use the same
+ * on the cu2rec_csr by the first call that needs it, as the item-major view is).  Both half-steps of a sweep use the same
  * negatives.  With x_e = (item_bias[i] - item_bias[j_e]) + p_u . (q_i - q_j) -- the user bias and the global bias cancel -- the
  * quantity to be MAXIMISED is
  *   L = sum_triples ln sigma(x_e) - 1/2 P_reg sum_(u < U) |p_u|^2 - 1/2 Q_reg sum_(i < I) |q_i|^2 - 1/2 item_bias_reg sum_(i < I) ib_i^2

@@ -240,7 +240,7 @@ def test_problems_without_triples():
 
 
 def test_other_trainers_are_unchanged_by_the_cache_on_the_csr():
-    """sgd, als, ials and lmf give the same bits on a CSR that the BPR calls have used (row-sorted copy, negatives, regrouping, the
+    """sgd, als, ials and lmf give the same bits on a CSR that the BPR calls have used (row-sorted view, negatives, regrouping, the
     kept sort values of the item-major view) as on a fresh one, in either order of first use."""
     case = chk.cases()["f62-65x1000"]
     state = case.state()

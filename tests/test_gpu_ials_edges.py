@@ -224,7 +224,7 @@ def _then_objective(step):
 
 
 def test_explicit_implicit_and_objective_interleaved_on_one_csr():
-    """One AlsCache (workspace, transposition, g0, g0_other, the unsolved counter) serves all three: every step, and the
+    """One cu2rec_csr (ALS workspace, item-major view, g0, g0_other, the unsolved counter) serves all three: every step, and the
     objective after it (which overwrites g0 with P's Gram), equals the same on a re-created model and a fresh CSR."""
     tr, _ = synth.make_ratings(300, 80, 5000, min_degree=2, seed=84)
     start = random_state(tr.rows, tr.cols, 16, 85)

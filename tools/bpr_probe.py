@@ -2,7 +2,7 @@
 
     python tools/bpr_probe.py [--shapes ml-20m] [--factors 100] [--reps 3]
 
-For every shape, after one warm-up sweep (it builds the row-sorted copy, the item-major view and the accumulators): the gradient calls
+For every shape, after one warm-up sweep (it builds the CSR's row-sorted and item-major views and the accumulators): the gradient calls
 with the sweep's negatives and regrouping already cached on the CSR, the same calls on a fresh sweep -- the differences are the
 negatives pass and the regrouping sort -- then the two half-steps, a whole sweep and the objective.  Times are wall clock around the
 synchronous C call (the gradient calls with NULL outputs: nothing is copied to the host; a half-step returns after a device-to-host

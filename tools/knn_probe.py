@@ -2,7 +2,7 @@
 
     python tools/knn_probe.py [--shapes ml-20m] [--weighting cosine] [--neighbours 20] [--k 10] [--users 4096] [--reps 3] [--out FILE]
 
-Times are wall clock around the synchronous call, best of --reps after one warm-up call (the warm-up builds the row-sorted copy and
+Times are wall clock around the synchronous call, best of --reps after one warm-up call (the warm-up builds the row-sorted and
 the item-major view, which the CSR keeps; every timed create repeats the weights, the product and the id-sorted copy).  Beside the
 times, the work counts of the build: sum over users of n_u^2 accumulations (every stored pair of a row, both orders and the diagonal,
 across all slices) and the bytes its wavefronts gather (8 bytes per accumulation: the partner row's id and weight), and the same for
