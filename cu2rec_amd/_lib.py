@@ -179,6 +179,15 @@ SIGNATURES = {
     "cu2rec_knn_neighbors": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_knn_recommend": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_knn_rank_metrics": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.POINTER(RankMetrics), _P]),
+    "cu2rec_ease_create": (C.c_int, [_P, C.c_float, C.POINTER(_P)]),
+    "cu2rec_ease_destroy": (None, [_P]),
+    "cu2rec_ease_info": (C.c_int, [_P, _ip, _fp]),
+    "cu2rec_ease_block_items": (C.c_int, []),
+    "cu2rec_csr_ease_gram": (C.c_int, [_P, C.c_float, _P]),
+    "cu2rec_ease_weights": (C.c_int, [_P, _P, C.c_int, _P]),
+    "cu2rec_ease_neighbors": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "cu2rec_ease_recommend": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "cu2rec_ease_rank_metrics": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.POINTER(RankMetrics), _P]),
 }
 
 _lib = None

@@ -26,6 +26,8 @@ MODES = {"hogwild": SGD_HOGWILD, "serial": SGD_SERIAL, "ordered": SGD_ORDERED, "
 KNN_COUNT, KNN_COSINE, KNN_TFIDF, KNN_BM25 = 0, 1, 2, 3
 KNN_WEIGHTINGS = {"count": KNN_COUNT, "cosine": KNN_COSINE, "tfidf": KNN_TFIDF, "bm25": KNN_BM25}
 KNN_WORKSPACE_BYTES = 64 << 20  # CU2REC_KNN_WORKSPACE_BYTES: the bound of the product's workspace per batch of queries
+EASE_MAX_ITEMS, EASE_MAX_K = 65536, 256  # CU2REC_EASE_MAX_ITEMS, CU2REC_EASE_MAX_K
+EASE_WORKSPACE_BYTES = 64 << 20  # CU2REC_EASE_WORKSPACE_BYTES: the bound of the lists' workspace per batch of queries
 ALS_SIDES = {"users": (SIDE_USERS,), "items": (SIDE_ITEMS,), "both": (SIDE_USERS, SIDE_ITEMS)}
 IALS_SOLVERS = ("cholesky", "cg")  # Model.als / Model.ials / train(mode="als" | "ials"): the exact solver, or conjugate-gradient steps per row
 ALS_CG_MAX_STEPS = 256             # CU2REC_ALS_CG_MAX_STEPS
@@ -287,6 +289,13 @@ class DeviceCSR:
         w = np.empty(self.nnz, np.float32)
         check(lib().cu2rec_csr_knn_weights(self._h, weighting, float(k1), float(b), _ptr(w)))
         return w
+
+    def ease_gram(self, l2):
+        """EASE's regularised Gram matrix (cu2rec_csr_ease_gram) -> float32 (cols, cols): ItemKNN's "count" similarities off the
+        diagonal, the columns' sums of squares plus l2 on it."""
+        g = np.empty((self.cols, self.cols), np.float32)
+        check(lib().cu2rec_csr_ease_gram(self._h, float(l2), _ptr(g)))
+        return g
 
     def blocksolve_items(self):
         """cu2rec_csr_blocksolve_items: how many items the block-solve mode solves block-wise here (0: it is the ordered walk)."""
@@ -583,6 +592,75 @@ class ItemKNN:
     def close(self):
         if self._h:
             lib().cu2rec_knn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EASE:
+    """EASE (Steck 2019; cu2rec_ease_*; include/cu2rec_amd.h): the closed-form item x item weights B_ij = -P_ij / P_jj, B_ii = 0, from
+    P = (X^T X + l2 I)^-1 of the values `train` stores, inverted in float32 on the device.  One hyper-parameter, no factors, no seed, no
+    iterations; results are bit-identical run to run.  At most 65,536 items on one GPU; rows may be unsorted; a train row that stores
+    a column twice is refused, and so is an l2 too small for the matrix to be positive definite in float32."""
+
+    def __init__(self, train, l2=500.0):
+        self._h = None
+        self.items, self.l2 = train.cols, float(l2)
+        h = C.c_void_p()
+        check(lib().cu2rec_ease_create(train._h, float(l2), C.byref(h)))
+        self._h = h
+
+    @staticmethod
+    def _ids(ids):
+        return None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+
+    def weights(self, ids=None):
+        """Rows of B (cu2rec_ease_weights) -> float32 (n, items).  ids: item ids (duplicates allowed), or None for every item."""
+        q = self._ids(ids)
+        n = self.items if q is None else len(q)
+        out = np.empty((n, self.items), np.float32)
+        check(lib().cu2rec_ease_weights(self._h, _ptr(q), int(n), _ptr(out)))
+        return out
+
+    def neighbors(self, ids=None, k=10):
+        """The k largest B_ij, j != i, of each listed item i (cu2rec_ease_neighbors) -> (ids, vals), each (n, k); topk's order, ties
+        and -1 / NaN padding.  ids: item ids (duplicates allowed), or None for every item.  1 <= k <= 256."""
+        k = int(k)
+        q = self._ids(ids)
+        n = self.items if q is None else len(q)
+        out, vals = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_ease_neighbors(self._h, _ptr(q), int(n), k, _ptr(out), _ptr(vals)))
+        return out, vals
+
+    def recommend(self, history, exclude, k, users=None):
+        """The k best items for each listed row of `history` (cu2rec_ease_recommend) -> (items, scores), each (n, k): the row's raw
+        values pushed through B; EVERY item outside row u of `exclude` (DeviceCSR or None) is a candidate.  users: row ids of
+        history (duplicates allowed), or None for every row.  1 <= k <= 256."""
+        k = int(k)
+        q = self._ids(users)
+        n = history.rows if q is None else len(q)
+        items, scores = np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+        check(lib().cu2rec_ease_recommend(self._h, history._h, exclude._h if exclude is not None else None, _ptr(q), int(n), k,
+                                          _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def rank_metrics(self, history, test, k, exclude=None, threshold=None, per_user=False):
+        """Model.rank_metrics' figures over recommend()'s lists of every row of `history` (cu2rec_ease_rank_metrics)."""
+        out = RankMetrics()
+        per = np.empty((history.rows, 5), np.float64) if per_user else None
+        thr = -np.inf if threshold is None else float(threshold)
+        check(lib().cu2rec_ease_rank_metrics(self._h, history._h, exclude._h if exclude is not None else None, test._h, int(k), thr,
+                                             C.byref(out), _ptr(per)))
+        res = {name: getattr(out, name) for name, _ in RankMetrics._fields_}
+        return (res, per) if per_user else res
+
+    def close(self):
+        if self._h:
+            lib().cu2rec_ease_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -86,4 +86,12 @@ struct KnnHandle {
     ~KnnHandle() { cu2rec_knn_destroy(h); }
 };
 
+struct EaseHandle {
+    cu2rec_ease *h = nullptr;
+    EaseHandle(const CsrHandle &train, float l2) { check(cu2rec_ease_create(train.h, l2, &h)); }
+    EaseHandle(const EaseHandle &) = delete;
+    EaseHandle &operator=(const EaseHandle &) = delete;
+    ~EaseHandle() { cu2rec_ease_destroy(h); }
+};
+
 }  // namespace cu2rec

@@ -2,8 +2,8 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn] [-a alpha] [-C cg_steps] [-g gpus] [-s sync_every]
-//          [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-k K [-t T]] train.csv test.csv
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease] [-a alpha] [-C cg_steps] [-g gpus]
+//          [-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
 // for bit).  `-m hogwild` opts into sgd.cu's own racy semantics (fastest, 1e-3 away from the sequential result while
@@ -24,6 +24,10 @@
 // <base>_knn_ids.csv and <base>_knn_sims.csv (items x N, -1 / nan padding) where the five files would go, and prints -k's ranking line
 // with the training rows as history and exclusion (cu2rec_knn_rank_metrics).  -k is required; no config is read, so -c is refused, as
 // are -a, -C, -g, -s and -w.
+// `-m ease` trains nothing either: it builds the closed-form item x item weights B (cu2rec_ease_create) on the training file -- -L the
+// regulariser l2 (default 500) -- writes B to <base>_ease_b.csv (items x items) when there are at most 4,096 items (more: the file is
+// skipped, with a word on stderr), and prints -k's ranking line with the training rows as history and exclusion
+// (cu2rec_ease_rank_metrics).  -k is required; -c, -a, -C, -g, -s, -w, -W and -N are refused.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -54,7 +58,7 @@ namespace {
 bool g_mode_given = false;  // -m on the command line
 
 // what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
-enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn };
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn, Ease };
 
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
@@ -325,11 +329,34 @@ int run_knn(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::strin
     return 0;
 }
 
+// bin/mf -m ease: B of the training file to <base>_ease_b.csv (at most kEaseCsvItems items), then -k's ranking line
+constexpr int kEaseCsvItems = 4096;
+int run_ease(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::string &train_path, float l2, int rank_k, float rank_threshold) {
+    if (test.rows > train.rows || test.cols > train.cols)
+        throw std::runtime_error("the test file names users / items the training file does not have");
+    test.cols = train.cols;  // the recommender's lists and the test rows name one catalogue
+    cu2rec::CsrHandle d_train(train), d_test(test);
+    cu2rec::EaseHandle ease(d_train, l2);
+    std::string parent_dir, base;
+    output_place(train_path, parent_dir, base);
+    if (train.cols <= kEaseCsvItems) {
+        std::vector<float> b(static_cast<size_t>(train.cols) * train.cols);
+        cu2rec::check(cu2rec_ease_weights(ease.h, nullptr, train.cols, b.data()));
+        cu2rec::check(cu2rec_write_csv((parent_dir + "/" + base + "_ease_b.csv").c_str(), b.data(), train.cols, train.cols));
+    } else {
+        std::cerr << "mf: " << train.cols << " items: " << base << "_ease_b.csv is skipped (written for at most " << kEaseCsvItems << " items)\n";
+    }
+    cu2rec_rank_metrics rm;
+    cu2rec::check(cu2rec_ease_rank_metrics(ease.h, d_train.h, d_train.h, d_test.h, rank_k, rank_threshold, &rm, nullptr));
+    print_rank_line(rm, rank_k);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn] [-a alpha] [-C cg_steps] [-g gpus] "
-                        "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-k K [-t T]] train.csv test.csv\n";
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease] [-a alpha] [-C cg_steps] [-g gpus] "
+                        "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
         return -1;
@@ -350,8 +377,10 @@ int main(int argc, char **argv) {
     bool weighting_given = false, neighbours_given = false;  // -W / -N: -m knn's weighting (-1: not one of the four) and list length
     int weighting = CU2REC_KNN_COSINE;
     long neighbours = 20;
+    bool l2_given = false;  // -L: -m ease's regulariser
+    float l2 = 500.f;
     int opt;
-    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:W:N:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:W:N:L:")) != -1) {
         switch (opt) {
             case 'a': {
                 char *end = nullptr;
@@ -380,6 +409,13 @@ int main(int argc, char **argv) {
                 neighbours_given = true;
                 neighbours = std::strtol(optarg, &end, 10);
                 if (end == optarg || *end != '\0') neighbours = 0;  // not a number: refused below
+                break;
+            }
+            case 'L': {
+                char *end = nullptr;
+                l2_given = true;
+                l2 = std::strtof(optarg, &end);
+                if (end == optarg || *end != '\0') l2 = NAN;  // not a number: refused below
                 break;
             }
             case 'k':
@@ -418,6 +454,7 @@ int main(int argc, char **argv) {
                           : std::strcmp(optarg, "lmf") == 0   ? Trainer::Lmf
                           : std::strcmp(optarg, "bpr") == 0   ? Trainer::Bpr
                           : std::strcmp(optarg, "knn") == 0   ? Trainer::Knn
+                          : std::strcmp(optarg, "ease") == 0  ? Trainer::Ease
                                                               : Trainer::Sgd;
                 mode = trainer != Trainer::Sgd                  ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0     ? CU2REC_SGD_SERIAL
@@ -446,6 +483,16 @@ int main(int argc, char **argv) {
     if (trainer == Trainer::Knn &&
         (!rank_given || alpha_given || cg_given || gpus > 1 || !config_path.empty() || sync_given || merge_given)) {  // before the GPU is touched
         std::cerr << "mf: -m knn needs -k, reads no config (no -c), takes no -a and no -C, and is single-GPU only (no -g, -s, -w)\n" << usage;
+        return 1;
+    }
+    if (trainer == Trainer::Ease && (!rank_given || alpha_given || cg_given || gpus > 1 || !config_path.empty() || sync_given || merge_given ||
+                                     weighting_given || neighbours_given)) {  // before the GPU is touched
+        std::cerr << "mf: -m ease needs -k, reads no config (no -c), takes no -a, no -C, no -W and no -N, and is single-GPU only (no -g, -s, -w)\n"
+                  << usage;
+        return 1;
+    }
+    if (l2_given && (trainer != Trainer::Ease || !(std::isfinite(l2) && l2 > 0.f))) {
+        std::cerr << "mf: -L needs -m ease and a finite l2 > 0\n" << usage;
         return 1;
     }
     if (rank_given && gpus > 1) {
@@ -501,6 +548,7 @@ int main(int argc, char **argv) {
         const cu2rec::HostCsr test = cu2rec::load_ratings(test_path);    // mf.cu:47-51
         if (train.nnz == 0) throw std::runtime_error("no ratings read from " + train_path);
         if (trainer == Trainer::Knn) return run_knn(train, test, train_path, weighting, static_cast<int>(neighbours), rank_k, rank_threshold);
+        if (trainer == Trainer::Ease) return run_ease(train, test, train_path, l2, rank_k, rank_threshold);
 
         cu2rec_config cfg;  // mf.cu:54-57
         cu2rec::check(cu2rec_config_default(&cfg));

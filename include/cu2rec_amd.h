@@ -833,6 +833,63 @@ int cu2rec_knn_recommend(const cu2rec_knn *knn, const cu2rec_csr *history, const
 int cu2rec_knn_rank_metrics(const cu2rec_knn *knn, const cu2rec_csr *history, const cu2rec_csr *exclude, const cu2rec_csr *test,
                             int k, float threshold, cu2rec_rank_metrics *out, double *per_user);
 
+/* ------------------------------------------------------------------------------------------
+ * EASE (Steck, "Embarrassingly Shallow Autoencoders for Sparse Data", WWW 2019): a dense item x item weight matrix in closed form.
+ * One hyper-parameter (l2), no factors, no seed, no iterations.  `train` is the user x item CSR with I columns, values r as stored
+ * (the caller binarises if it wants to).
+ *   G    the Gram matrix: off the diagonal G_ij is ItemKNN's CU2REC_KNN_COUNT similarity S_ij, the fold acc = fmaf(r_ui, r_uj, acc)
+ *        from +0.0f over the users of column i in ascending order; on the diagonal G_ii = fl(sum_u r_ui^2 + l2), the sum in the same
+ *        order and l2 added once, as the float given, to the finished float sum
+ *   P    = G^-1 in float32 through the Cholesky factor G = L L^T: a blocked factorisation in place on the lower triangle (blocks of
+ *        cu2rec_ease_block_items() items), the blocked triangular inverse of L, then L^-T L^-1
+ *   B    B_ij = -P_ij / P_jj (an IEEE division) for i != j, B_ii = 0: the columns are scaled, B is not symmetric
+ * The score of history row u for item j is sum_i r_ui B_ij over the row's stored entries in ascending item id (an entry that repeats
+ * a column counts each time), the fold acc = fmaf(r, B_ij, acc) from +0.0f.  EVERY item that row u of `exclude` does not name is a
+ * candidate -- also one whose score is 0 and one nobody stores, unlike ItemKNN's touched candidates -- so a list has
+ * min(k, I - excluded) entries, best first, ties by ascending id, then cu2rec_model_topk's -1 / NaN padding.  The neighbours of item i
+ * are that list for the one-entry history {i: 1.0} with i excluded: the k largest B_ij of row i.  An item nobody stores has
+ * P_ii = 1 / l2 and a zero row and column of B.
+ *
+ * No float atomics; every sum is a fixed-order fmaf / matrix-core chain: a model built twice is bit-identical, results are
+ * bit-identical run to run, and a query alone gives what it gives among others.
+ *
+ * Limits: one GPU; I <= CU2REC_EASE_MAX_ITEMS (more: CU2REC_EUNSUPPORTED, before anything is allocated); k in [1, CU2REC_EASE_MAX_K];
+ * the inverse is float32.  The model holds one (I rounded up to whole blocks)^2 float matrix, in which every stage runs in place
+ * beside O(I x block) of workspace; a matrix that does not fit is CU2REC_ENOMEM.  A pivot of the factorisation that is not a finite
+ * number above the rounding noise of its own diagonal entry, 2^-22 G_jj (l2 too small for the data in float -- two identical columns
+ * with l2 below an ulp of their sum of squares --, a NaN value) fails the whole build with CU2REC_EUNSUPPORTED, cu2rec_last_error()
+ * naming the pivot's item, and *out stays NULL; nothing on the device traps.  cols == 0 or nnz == 0 is a valid model with nothing
+ * (or only zero scores) to list.
+ *
+ * A train row that stores the same column twice, an l2 that is not finite or <= 0, k outside its range, an id out of range, null
+ * arguments, a history, exclude or test CSR whose column count differs from the model's: CU2REC_EINVAL, checked before the device is
+ * touched where the arguments alone show it.  Rows of every CSR may be unsorted.
+ *
+ * Lists come from one wavefront per (query, slice of cu2rec_knn_slice_items() consecutive ids), in batches of queries whose workspace
+ * ((slices + 1) * k * 8 bytes per query) fits CU2REC_EASE_WORKSPACE_BYTES. */
+enum { CU2REC_EASE_MAX_ITEMS = 65536, CU2REC_EASE_MAX_K = 256, CU2REC_EASE_WORKSPACE_BYTES = 64 << 20 };
+typedef struct cu2rec_ease cu2rec_ease;
+/* builds the model: G, its inverse and B, all in one buffer */
+int cu2rec_ease_create(const cu2rec_csr *train, float l2, cu2rec_ease **out);
+void cu2rec_ease_destroy(cu2rec_ease *ease);
+int cu2rec_ease_info(const cu2rec_ease *ease, int *items, float *l2); /* pointers may be NULL */
+/* items per block of the factorisation and the inverse (a constant of the build; needs no device) */
+int cu2rec_ease_block_items(void);
+/* G alone, dense -> out (host, I x I floats) */
+int cu2rec_csr_ease_gram(const cu2rec_csr *csr, float l2, float *out);
+/* rows of B (ids: host, duplicates allowed; NULL: every item, n ignored) -> out (host, n x I floats) */
+int cu2rec_ease_weights(const cu2rec_ease *ease, const int *ids, int n, float *out);
+/* the k largest B_ij, j != i, of each listed item i (ids as above) -> host, n x k */
+int cu2rec_ease_neighbors(const cu2rec_ease *ease, const int *ids, int n, int k, int *out_ids, float *out_vals);
+/* the k best candidates of each listed history row (users: host row ids of `history`, duplicates allowed; NULL: every row; row u
+ * of `exclude` -- may be NULL, rows past its last exclude nothing -- is not listed for row u) -> host, n x k */
+int cu2rec_ease_recommend(const cu2rec_ease *ease, const cu2rec_csr *history, const cu2rec_csr *exclude, const int *users, int n,
+                          int k, int *out_items, float *out_scores);
+/* cu2rec_model_rank_metrics' definitions over cu2rec_ease_recommend's lists of every history row (the rows the means are taken
+ * over; test rows past them: CU2REC_EINVAL).  per_user: host, history rows x 5, may be NULL. */
+int cu2rec_ease_rank_metrics(const cu2rec_ease *ease, const cu2rec_csr *history, const cu2rec_csr *exclude, const cu2rec_csr *test,
+                             int k, float threshold, cu2rec_rank_metrics *out, double *per_user);
+
 #ifdef __cplusplus
 }
 #endif
