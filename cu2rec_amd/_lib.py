@@ -51,6 +51,11 @@ class RankMetrics(C.Structure):
                 ("recall", C.c_double), ("ndcg", C.c_double), ("map", C.c_double), ("hit_rate", C.c_double)]
 
 
+class SlimReport(C.Structure):
+    """cu2rec_slim_report: the sweeps run, the last sweep's largest |delta|, the nonzeros of W."""
+    _fields_ = [("sweeps", C.c_int), ("last_delta", C.c_float), ("nonzeros", C.c_longlong)]
+
+
 class CommInfo(C.Structure):
     """cu2rec_comm_info_t: what RCCL itself reports about the attached communicator."""
     _fields_ = [("rank", C.c_int), ("nranks", C.c_int), ("rccl_nranks", C.c_int), ("rccl_rank", C.c_int), ("rccl_device", C.c_int),
@@ -188,6 +193,7 @@ SIGNATURES = {
     "cu2rec_ease_neighbors": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_ease_recommend": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_ease_rank_metrics": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.POINTER(RankMetrics), _P]),
+    "cu2rec_slim_create": (C.c_int, [_P, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.POINTER(SlimReport), C.POINTER(_P)]),
 }
 
 _lib = None

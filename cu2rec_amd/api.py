@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from ._lib import Config, Cu2recError, Hyper, RankMetrics, TrainStats, check, lib
+from ._lib import Config, Cu2recError, Hyper, RankMetrics, SlimReport, TrainStats, check, lib
 
 SGD_HOGWILD, SGD_SERIAL, SGD_ORDERED, SGD_PINGPONG, SGD_BLOCKSOLVE = 0, 1, 2, 3, 4
 ALS = 5  # alternating least squares: a training method of train() / cu2rec_train only (Model.sgd refuses it)
@@ -668,6 +668,22 @@ class EASE:
             self.close()
         except Exception:
             pass
+
+
+class SLIM(EASE):
+    """SLIM (Ning & Karypis 2011; cu2rec_slim_create; include/cu2rec_amd.h): sparse item x item weights W -- EASE's least-squares
+    problem with an L1 penalty `l1` and, when `positive`, non-negative weights -- by at most `sweeps` sweeps of blocked cyclic
+    coordinate descent in float32 on the device, stopping after a sweep whose largest change is <= tol.  `.report` holds the sweeps
+    run, the last sweep's largest |delta| and the nonzeros of W.  The lists are EASE's, from W in B's place; results are bit-identical
+    run to run.  EASE's limits; while it is built the model holds three items x items matrices instead of one."""
+
+    def __init__(self, train, l1=5.0, l2=500.0, positive=True, sweeps=10, tol=1e-3):
+        self._h = None
+        self.items, self.l1, self.l2, self.positive = train.cols, float(l1), float(l2), bool(positive)
+        h, rep = C.c_void_p(), SlimReport()
+        check(lib().cu2rec_slim_create(train._h, float(l1), float(l2), int(bool(positive)), int(sweeps), float(tol), C.byref(rep), C.byref(h)))
+        self._h = h
+        self.report = {"sweeps": rep.sweeps, "last_delta": rep.last_delta, "nonzeros": rep.nonzeros}
 
 
 def default_mode(n_factors):

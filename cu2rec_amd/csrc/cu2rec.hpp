@@ -89,6 +89,9 @@ struct KnnHandle {
 struct EaseHandle {
     cu2rec_ease *h = nullptr;
     EaseHandle(const CsrHandle &train, float l2) { check(cu2rec_ease_create(train.h, l2, &h)); }
+    EaseHandle(const CsrHandle &train, float l1, float l2, bool positive, int max_sweeps, float tol, cu2rec_slim_report *report) {
+        check(cu2rec_slim_create(train.h, l1, l2, positive, max_sweeps, tol, report, &h));
+    }
     EaseHandle(const EaseHandle &) = delete;
     EaseHandle &operator=(const EaseHandle &) = delete;
     ~EaseHandle() { cu2rec_ease_destroy(h); }

@@ -31,6 +31,7 @@
 
 #include "device.hpp"
 #include "ease.hpp"
+#include "ease_tile.hpp"
 #include "hip_check.hpp"
 #include "mfma_f32.hpp"
 #include "rank_stage.hpp"
@@ -41,13 +42,10 @@ namespace cu2rec {
 
 namespace {
 
-constexpr int kNb = kEaseBlock;
-constexpr int kLs = kNb + 1;  // row stride of a tile in LDS: odd, so that a column read is conflict free
 constexpr int kSlice = kKnnSliceItems;
 constexpr int kSliceWords = kSlice / 32;
 constexpr int kChunk = 256;  // candidates that enter one sort beside the best 256 so far
 constexpr float kPivotNoise = 0x1p-22f;
-static_assert(kNb == 64, "a tile is 2 x 2 MFMA accumulators, one per wavefront of a 256-thread workgroup; a row or column per lane");
 static_assert(kSliceWords == 64 && kSlice % kChunk == 0 && kSlice % kNb == 0, "one bitmap word per lane; whole chunks; whole blocks");
 
 // the wavefront's LDS accesses before this point are done before those after it
@@ -118,46 +116,6 @@ __global__ __launch_bounds__(256) void ease_gram_kernel(EaseGram a, float *__res
         if (slice_lo + j == i) v = i < a.items ? v + a.l2 : 1.f;
         row[slice_lo + j] = v;
     }
-}
-
-// ---- tiles -------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float *tile_at(float *g, int ld, int bi, int bj) {
-    return g + static_cast<size_t>(bi) * kNb * ld + static_cast<size_t>(bj) * kNb;
-}
-
-// tile (row stride ld) -> t[kNb][kLs], by all `threads` threads of the workgroup; coalesced rows
-__device__ __forceinline__ void load_tile(float (*t)[kLs], const float *src, size_t ld, int threads) {
-    for (int x = threadIdx.x; x < kNb * kNb; x += threads) t[x >> 6][x & 63] = src[static_cast<size_t>(x >> 6) * ld + (x & 63)];
-}
-
-// this wavefront's 32 x 32 quarter (wi, wj) of a tile: acc += X Y, the operands in LDS.  Every caller starts a tile product from
-// zero_tile() and adds or subtracts the finished product with one rounding per element: a sum over many tiles is then a sum of
-// tile-sized parts, whose error grows with the number of tiles and not with the number of terms.  XT: X is read transposed
-// (X[i][k] = x[k][i]); NEG: -X.  Y[k][j] = y[k][j] (YT false) or y[j][k] (YT true).  The contraction runs k = 0 .. kNb - 1 in
-// ascending pairs.
-template <bool XT, bool YT, bool NEG>
-__device__ __forceinline__ void tile_mma(f32x16 &acc, const float (*x)[kLs], const float (*y)[kLs], int wi, int wj, int lane) {
-    const int r = lane & 31, h = lane >> 5;
-#pragma unroll 8
-    for (int k = 0; k < kNb; k += 2) {
-        float av = XT ? x[k + h][wi * 32 + r] : x[wi * 32 + r][k + h];
-        const float bv = YT ? y[wj * 32 + r][k + h] : y[k + h][wj * 32 + r];
-        if (NEG) av = -av;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ f32x16 zero_tile() {
-    f32x16 z;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) z[reg] = 0.f;
-    return z;
-}
-
-__device__ __forceinline__ void store_quarter(const f32x16 &acc, float *dst, size_t ld, int wi, int wj, int lane) {
-    const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-    for (int reg = 0; reg < 16; ++reg) dst[static_cast<size_t>(wi * 32 + acc_row(reg, h)) * ld + wj * 32 + c] = acc[reg];
 }
 
 // ---- 2: the Cholesky factor --------------------------------------------------------------------------------------------------
@@ -494,10 +452,11 @@ EaseQuery recommend_query(const DeviceEase &m, const DeviceCsr &history, const D
                      ex ? exclude->indices.ptr : nullptr, ex ? exclude->rows : 0, m.B.ptr, m.ld, m.items, slices_of(m.items), k};
 }
 
-int padded(int items) { return (items + kNb - 1) / kNb * kNb; }
+}  // namespace
 
-// hipMalloc of n floats into buf; memory that is not there is CU2REC_ENOMEM
-void allocate_matrix(DeviceBuffer<float> &buf, size_t n, const char *fn) {
+int ease_padded(int items) { return (items + kNb - 1) / kNb * kNb; }
+
+void ease_allocate_matrix(DeviceBuffer<float> &buf, size_t n, const char *fn) {
     if (n == 0) return;
     float *p = nullptr;
     const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p), n * sizeof(float));
@@ -509,8 +468,6 @@ void allocate_matrix(DeviceBuffer<float> &buf, size_t n, const char *fn) {
     buf.ptr = p;
     buf.count = n;
 }
-
-}  // namespace
 
 void ease_check_l2(const char *fn, float l2) { Need{fn}(std::isfinite(l2) && l2 > 0.f, CU2REC_EINVAL, ": l2 must be finite and > 0"); }
 
@@ -524,7 +481,7 @@ void ease_gram(const DeviceCsr &csr, float l2, int ld, float *g, hipStream_t str
     CU2REC_HIP(hipGetLastError());
 }
 
-DeviceEase::DeviceEase(const DeviceCsr &train, float l2_) : items(train.cols), ld(padded(train.cols)), l2(l2_) {
+DeviceEase::DeviceEase(const DeviceCsr &train, float l2_) : items(train.cols), ld(ease_padded(train.cols)), l2(l2_) {
     ease_check_l2("cu2rec_ease_create", l2);
     if (items > kEaseMaxItems) fail(CU2REC_EUNSUPPORTED, "cu2rec_ease_create: more than CU2REC_EASE_MAX_ITEMS columns");
     if (items == 0) return;
@@ -532,7 +489,7 @@ DeviceEase::DeviceEase(const DeviceCsr &train, float l2_) : items(train.cols), l
     check_faults();
     hipStream_t stream = nullptr;
     const int T = ld / kNb;
-    allocate_matrix(B, static_cast<size_t>(ld) * ld, "cu2rec_ease_create");
+    ease_allocate_matrix(B, static_cast<size_t>(ld) * ld, "cu2rec_ease_create");
     DeviceBuffer<float> panel(static_cast<size_t>(ld) * kNb), diag(ld);
     DeviceBuffer<int> flag(2);
     flag.zero();
@@ -682,9 +639,9 @@ int cu2rec_csr_ease_gram(const cu2rec_csr *csr, float l2, float *out) {
         if (m.cols == 0) return;
         require_device();
         check_faults();
-        const int ld = padded(m.cols);
+        const int ld = ease_padded(m.cols);
         DeviceBuffer<float> g;
-        allocate_matrix(g, static_cast<size_t>(ld) * ld, "cu2rec_csr_ease_gram");
+        ease_allocate_matrix(g, static_cast<size_t>(ld) * ld, "cu2rec_csr_ease_gram");
         ease_gram(m, l2, ld, g.ptr, nullptr);
         const size_t row = static_cast<size_t>(m.cols) * sizeof(float);
         CU2REC_HIP(hipMemcpy2D(out, row, g.ptr, static_cast<size_t>(ld) * sizeof(float), row, m.cols, hipMemcpyDeviceToHost));

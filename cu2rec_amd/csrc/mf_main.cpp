@@ -2,8 +2,8 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease] [-a alpha] [-C cg_steps] [-g gpus]
-//          [-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-k K [-t T]] train.csv test.csv
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus]
+//          [-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-l l1] [-n sweeps] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
 // for bit).  `-m hogwild` opts into sgd.cu's own racy semantics (fastest, 1e-3 away from the sequential result while
@@ -28,6 +28,10 @@
 // regulariser l2 (default 500) -- writes B to <base>_ease_b.csv (items x items) when there are at most 4,096 items (more: the file is
 // skipped, with a word on stderr), and prints -k's ranking line with the training rows as history and exclusion
 // (cu2rec_ease_rank_metrics).  -k is required; -c, -a, -C, -g, -s, -w, -W and -N are refused.
+// `-m slim` is `-m ease` with SLIM's sparse weights W in B's place (cu2rec_slim_create: non-negative weights, tol 1e-3): -l the L1
+// penalty l1 (default 5), -L l2 (default 500), -n the most sweeps of coordinate descent (default 10).  It writes W to <base>_slim_w.csv
+// under the same 4,096-item rule, prints one line with the sweeps run, the last sweep's largest change and the nonzeros of W, then
+// -k's ranking line.  It refuses what -m ease refuses; -l and -n are refused without it.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -58,7 +62,7 @@ namespace {
 bool g_mode_given = false;  // -m on the command line
 
 // what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
-enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn, Ease };
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn, Ease, Slim };
 
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
@@ -329,22 +333,19 @@ int run_knn(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::strin
     return 0;
 }
 
-// bin/mf -m ease: B of the training file to <base>_ease_b.csv (at most kEaseCsvItems items), then -k's ranking line
+// bin/mf -m ease and -m slim: the model's weights of the training file to <base><suffix> (at most kEaseCsvItems items), then -k's
+// ranking line
 constexpr int kEaseCsvItems = 4096;
-int run_ease(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::string &train_path, float l2, int rank_k, float rank_threshold) {
-    if (test.rows > train.rows || test.cols > train.cols)
-        throw std::runtime_error("the test file names users / items the training file does not have");
-    test.cols = train.cols;  // the recommender's lists and the test rows name one catalogue
-    cu2rec::CsrHandle d_train(train), d_test(test);
-    cu2rec::EaseHandle ease(d_train, l2);
+int serve_ease(const cu2rec::EaseHandle &ease, const cu2rec::HostCsr &train, const cu2rec::CsrHandle &d_train, const cu2rec::CsrHandle &d_test,
+               const std::string &train_path, const char *suffix, int rank_k, float rank_threshold) {
     std::string parent_dir, base;
     output_place(train_path, parent_dir, base);
     if (train.cols <= kEaseCsvItems) {
         std::vector<float> b(static_cast<size_t>(train.cols) * train.cols);
         cu2rec::check(cu2rec_ease_weights(ease.h, nullptr, train.cols, b.data()));
-        cu2rec::check(cu2rec_write_csv((parent_dir + "/" + base + "_ease_b.csv").c_str(), b.data(), train.cols, train.cols));
+        cu2rec::check(cu2rec_write_csv((parent_dir + "/" + base + suffix).c_str(), b.data(), train.cols, train.cols));
     } else {
-        std::cerr << "mf: " << train.cols << " items: " << base << "_ease_b.csv is skipped (written for at most " << kEaseCsvItems << " items)\n";
+        std::cerr << "mf: " << train.cols << " items: " << base << suffix << " is skipped (written for at most " << kEaseCsvItems << " items)\n";
     }
     cu2rec_rank_metrics rm;
     cu2rec::check(cu2rec_ease_rank_metrics(ease.h, d_train.h, d_train.h, d_test.h, rank_k, rank_threshold, &rm, nullptr));
@@ -352,11 +353,30 @@ int run_ease(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::stri
     return 0;
 }
 
+// slim: null for -m ease; else -m slim's l1 and most sweeps
+struct SlimOptions {
+    float l1;
+    int sweeps;
+};
+int run_ease(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::string &train_path, float l2, const SlimOptions *slim, int rank_k,
+             float rank_threshold) {
+    if (test.rows > train.rows || test.cols > train.cols)
+        throw std::runtime_error("the test file names users / items the training file does not have");
+    test.cols = train.cols;  // the recommender's lists and the test rows name one catalogue
+    cu2rec::CsrHandle d_train(train), d_test(test);
+    if (!slim) return serve_ease(cu2rec::EaseHandle(d_train, l2), train, d_train, d_test, train_path, "_ease_b.csv", rank_k, rank_threshold);
+    cu2rec_slim_report report;
+    cu2rec::EaseHandle model(d_train, slim->l1, l2, true, slim->sweeps, 1e-3f, &report);
+    std::printf("SLIM: l1: %g l2: %g Sweeps: %d LastDelta: %g Nonzeros: %lld of %lld\n", slim->l1, l2, report.sweeps, report.last_delta,
+                report.nonzeros, static_cast<long long>(train.cols) * train.cols);
+    return serve_ease(model, train, d_train, d_test, train_path, "_slim_w.csv", rank_k, rank_threshold);
+}
+
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease] [-a alpha] [-C cg_steps] [-g gpus] "
-                        "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-k K [-t T]] train.csv test.csv\n";
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus] "
+                        "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-l l1] [-n sweeps] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
         return -1;
@@ -377,10 +397,13 @@ int main(int argc, char **argv) {
     bool weighting_given = false, neighbours_given = false;  // -W / -N: -m knn's weighting (-1: not one of the four) and list length
     int weighting = CU2REC_KNN_COSINE;
     long neighbours = 20;
-    bool l2_given = false;  // -L: -m ease's regulariser
+    bool l2_given = false;  // -L: the regulariser of -m ease and -m slim
     float l2 = 500.f;
+    bool l1_given = false, sweeps_given = false;  // -l / -n: -m slim's L1 penalty and most sweeps
+    float l1 = 5.f;
+    long sweeps = 10;
     int opt;
-    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:W:N:L:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:m:g:s:w:k:t:a:C:W:N:L:l:n:")) != -1) {
         switch (opt) {
             case 'a': {
                 char *end = nullptr;
@@ -416,6 +439,20 @@ int main(int argc, char **argv) {
                 l2_given = true;
                 l2 = std::strtof(optarg, &end);
                 if (end == optarg || *end != '\0') l2 = NAN;  // not a number: refused below
+                break;
+            }
+            case 'l': {
+                char *end = nullptr;
+                l1_given = true;
+                l1 = std::strtof(optarg, &end);
+                if (end == optarg || *end != '\0') l1 = NAN;  // not a number: refused below
+                break;
+            }
+            case 'n': {
+                char *end = nullptr;
+                sweeps_given = true;
+                sweeps = std::strtol(optarg, &end, 10);
+                if (end == optarg || *end != '\0') sweeps = 0;  // not a number: refused below
                 break;
             }
             case 'k':
@@ -455,6 +492,7 @@ int main(int argc, char **argv) {
                           : std::strcmp(optarg, "bpr") == 0   ? Trainer::Bpr
                           : std::strcmp(optarg, "knn") == 0   ? Trainer::Knn
                           : std::strcmp(optarg, "ease") == 0  ? Trainer::Ease
+                          : std::strcmp(optarg, "slim") == 0  ? Trainer::Slim
                                                               : Trainer::Sgd;
                 mode = trainer != Trainer::Sgd                  ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0     ? CU2REC_SGD_SERIAL
@@ -485,14 +523,19 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -m knn needs -k, reads no config (no -c), takes no -a and no -C, and is single-GPU only (no -g, -s, -w)\n" << usage;
         return 1;
     }
-    if (trainer == Trainer::Ease && (!rank_given || alpha_given || cg_given || gpus > 1 || !config_path.empty() || sync_given || merge_given ||
+    const bool is_slim = trainer == Trainer::Slim;
+    if ((trainer == Trainer::Ease || is_slim) && (!rank_given || alpha_given || cg_given || gpus > 1 || !config_path.empty() || sync_given || merge_given ||
                                      weighting_given || neighbours_given)) {  // before the GPU is touched
-        std::cerr << "mf: -m ease needs -k, reads no config (no -c), takes no -a, no -C, no -W and no -N, and is single-GPU only (no -g, -s, -w)\n"
+        std::cerr << "mf: -m " << trainer_name << " needs -k, reads no config (no -c), takes no -a, no -C, no -W and no -N, and is single-GPU only (no -g, -s, -w)\n"
                   << usage;
         return 1;
     }
-    if (l2_given && (trainer != Trainer::Ease || !(std::isfinite(l2) && l2 > 0.f))) {
-        std::cerr << "mf: -L needs -m ease and a finite l2 > 0\n" << usage;
+    if (l2_given && ((trainer != Trainer::Ease && !is_slim) || !(std::isfinite(l2) && l2 > 0.f))) {
+        std::cerr << "mf: -L needs -m ease or -m slim and a finite l2 > 0\n" << usage;
+        return 1;
+    }
+    if ((l1_given || sweeps_given) && (!is_slim || !(std::isfinite(l1) && l1 >= 0.f) || sweeps < 1 || sweeps > 1000000)) {
+        std::cerr << "mf: -l and -n need -m slim, a finite l1 >= 0 and between 1 and 1000000 sweeps\n" << usage;
         return 1;
     }
     if (rank_given && gpus > 1) {
@@ -548,7 +591,11 @@ int main(int argc, char **argv) {
         const cu2rec::HostCsr test = cu2rec::load_ratings(test_path);    // mf.cu:47-51
         if (train.nnz == 0) throw std::runtime_error("no ratings read from " + train_path);
         if (trainer == Trainer::Knn) return run_knn(train, test, train_path, weighting, static_cast<int>(neighbours), rank_k, rank_threshold);
-        if (trainer == Trainer::Ease) return run_ease(train, test, train_path, l2, rank_k, rank_threshold);
+        if (trainer == Trainer::Ease) return run_ease(train, test, train_path, l2, nullptr, rank_k, rank_threshold);
+        if (is_slim) {
+            const SlimOptions slim{l1, static_cast<int>(sweeps)};
+            return run_ease(train, test, train_path, l2, &slim, rank_k, rank_threshold);
+        }
 
         cu2rec_config cfg;  // mf.cu:54-57
         cu2rec::check(cu2rec_config_default(&cfg));

@@ -890,6 +890,37 @@ int cu2rec_ease_recommend(const cu2rec_ease *ease, const cu2rec_csr *history, co
 int cu2rec_ease_rank_metrics(const cu2rec_ease *ease, const cu2rec_csr *history, const cu2rec_csr *exclude, const cu2rec_csr *test,
                              int k, float threshold, cu2rec_rank_metrics *out, double *per_user);
 
+/* ------------------------------------------------------------------------------------------
+ * SLIM (Ning & Karypis, "SLIM: Sparse Linear Methods for Top-N Recommender Systems", ICDM 2011): EASE's least-squares problem with an
+ * L1 penalty and, optionally, non-negative weights; a weight matrix of a few per cent nonzeros.  With A = G of EASE above (X^T X with
+ * l2 on the diagonal), column j of W minimises over w, with w_j = 0 and, when `positive`, w >= 0,
+ *     1/2 w^T A w - sum_{k != j} A_kj w_k + l1 |w|_1.
+ * EASE is l1 = 0 with free signs, at convergence.  The solver is cyclic coordinate descent from W = 0, in float32.  One sweep visits
+ * the coordinates k = 0 .. I - 1 in ascending order, each for all columns j at once; with C = A - A W,
+ *     rho = fmaf(A_kk, W_kj, C_kj);  new = max(rho - l1, 0) / A_kk when positive, else sign(rho) max(|rho| - l1, 0) / A_kk;
+ *     new = 0 for k = j;  delta = new - W_kj;  W_kj = new;  C[:, j] -= delta A[:, k].
+ * The device takes the coordinates in blocks of cu2rec_ease_block_items(): inside a block each delta reaches the block's later
+ * coordinates as c = fmaf(-delta, A_sk, c) on a copy of C's rows, and after the block C -= A[:, block] Delta as one matrix-core tile
+ * product per tile, from zero, subtracted with one rounding per element -- the same sequence of values as coordinate by coordinate,
+ * up to float rounding.  A tile of Delta that is all zeros is skipped: the update it would make is an exact zero.
+ *
+ * At most max_sweeps sweeps are run; with tol > 0 a sweep whose largest |delta| is <= tol is the last (tol = 0: every sweep
+ * is run).  report (may be NULL): the sweeps run, the last sweep's largest |delta|, the nonzeros of W.  No float atomics and a
+ * fixed order of every sum: a model built twice is bit-identical.
+ *
+ * The handle is a cu2rec_ease: cu2rec_ease_weights (rows of W), cu2rec_ease_neighbors, cu2rec_ease_recommend (the score of a history
+ * row for item j is sum_i r_ui W_ij, EASE's fold), cu2rec_ease_rank_metrics, cu2rec_ease_info (items and SLIM's l2) and
+ * cu2rec_ease_destroy serve it as they serve EASE's B.
+ *
+ * Limits are EASE's: one GPU, I <= CU2REC_EASE_MAX_ITEMS (more: CU2REC_EUNSUPPORTED before anything is allocated).  While it is built
+ * the model holds THREE (I rounded up to whole blocks)^2 float matrices (A, C and W) and afterwards one; memory that is not there is
+ * CU2REC_ENOMEM.  l1 not finite or < 0, l2 not finite or <= 0, max_sweeps < 1, tol NaN or < 0, null arguments and a train row that
+ * stores a column twice are CU2REC_EINVAL before anything is allocated.  A weight that is not a finite number (a NaN or an infinite
+ * value in the data) fails the build with CU2REC_EUNSUPPORTED.  cols == 0 or nnz == 0 is a valid model of zeros. */
+typedef struct { int sweeps; float last_delta; long long nonzeros; } cu2rec_slim_report;
+int cu2rec_slim_create(const cu2rec_csr *train, float l1, float l2, int positive, int max_sweeps, float tol,
+                       cu2rec_slim_report *report /* may be NULL */, cu2rec_ease **out);
+
 #ifdef __cplusplus
 }
 #endif
