@@ -56,6 +56,11 @@ class SlimReport(C.Structure):
     _fields_ = [("sweeps", C.c_int), ("last_delta", C.c_float), ("nonzeros", C.c_longlong)]
 
 
+class SvdReport(C.Structure):
+    """cu2rec_svd_report: the sweeps run, captured = |X Q|_F^2 and total = |X|_F^2."""
+    _fields_ = [("sweeps", C.c_int), ("captured", C.c_double), ("total", C.c_double)]
+
+
 class CommInfo(C.Structure):
     """cu2rec_comm_info_t: what RCCL itself reports about the attached communicator."""
     _fields_ = [("rank", C.c_int), ("nranks", C.c_int), ("rccl_nranks", C.c_int), ("rccl_rank", C.c_int), ("rccl_device", C.c_int),
@@ -194,6 +199,12 @@ SIGNATURES = {
     "cu2rec_ease_recommend": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "cu2rec_ease_rank_metrics": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.POINTER(RankMetrics), _P]),
     "cu2rec_slim_create": (C.c_int, [_P, C.c_float, C.c_float, C.c_int, C.c_int, C.c_float, C.POINTER(SlimReport), C.POINTER(_P)]),
+    "cu2rec_model_svd": (C.c_int, [_P, _P, C.c_int, C.POINTER(SvdReport)]),
+    "cu2rec_model_project": (C.c_int, [_P, _P, _P]),
+    "cu2rec_train_svd": (C.c_int, [_P, C.POINTER(Config), _P, C.c_int, C.POINTER(SvdReport)]),
+    "cu2rec_csr_multiply": (C.c_int, [_P, C.c_int, _P, C.c_int, _P]),
+    "cu2rec_csr_multiply_stride": (C.c_int, [C.c_int, C.c_int]),
+    "cu2rec_orthonormalize": (C.c_int, [_P, C.c_int, C.c_int, _ip]),
 }
 
 _lib = None

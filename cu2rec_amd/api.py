@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from ._lib import Config, Cu2recError, Hyper, RankMetrics, SlimReport, TrainStats, check, lib
+from ._lib import Config, Cu2recError, Hyper, RankMetrics, SlimReport, SvdReport, TrainStats, check, lib
 
 SGD_HOGWILD, SGD_SERIAL, SGD_ORDERED, SGD_PINGPONG, SGD_BLOCKSOLVE = 0, 1, 2, 3, 4
 ALS = 5  # alternating least squares: a training method of train() / cu2rec_train only (Model.sgd refuses it)
@@ -297,6 +297,20 @@ class DeviceCSR:
         check(lib().cu2rec_csr_ease_gram(self._h, float(l2), _ptr(g)))
         return g
 
+    def multiply(self, D, transpose=False, padded=False):
+        """X D, or X^T D with transpose (cu2rec_csr_multiply): PureSVD's sparse x dense-skinny product -> float32 (rows, f), or
+        (cols, f) with transpose.  D: (cols, f), or (rows, f) with transpose; 1 <= f <= ALS_MAX_FACTORS.  padded: the rows as the
+        device wrote them at the model's stride (f rounded up to 4 for user rows, to 32 for item rows), the padding columns zero."""
+        D = np.ascontiguousarray(D, dtype=np.float32)
+        n_in, n_out = (self.rows, self.cols) if transpose else (self.cols, self.rows)
+        if D.ndim != 2 or D.shape[0] != n_in:
+            raise ValueError("D must have shape (%d, f), not %s" % (n_in, D.shape))
+        f = D.shape[1]
+        ld = max(lib().cu2rec_csr_multiply_stride(1 if transpose else 0, f), f)
+        out = np.empty((n_out, ld), np.float32)
+        check(lib().cu2rec_csr_multiply(self._h, 1 if transpose else 0, _ptr(D), f, _ptr(out)))
+        return out if padded else np.ascontiguousarray(out[:, :f])
+
     def blocksolve_items(self):
         """cu2rec_csr_blocksolve_items: how many items the block-solve mode solves block-wise here (0: it is the ordered walk)."""
         n = lib().cu2rec_csr_blocksolve_items(self._h)
@@ -439,6 +453,24 @@ class Model:
         L, n, m = C.c_double(), C.c_longlong(), C.c_longlong()
         check(lib().cu2rec_model_bpr_objective(self._h, train._h, C.byref(h), int(seed), int(sweep), C.byref(L), C.byref(n), C.byref(m)))
         return L.value, n.value, m.value
+
+    def svd(self, train, sweeps=4):
+        """PureSVD (cu2rec_model_svd; Cremonesi, Koren, Turrin 2010): `sweeps` sweeps of block subspace iteration on the matrix
+        `train` stores, from the model's current item factors -- Y = orth(X Q), Q = orth(X^T Y), orth being Cholesky-QR twice --
+        then P = X Q and both biases 0, so that P Q^T = X Q Q^T.  No learning rate, no regulariser; create the model with
+        global_bias 0 for the scores to be p . q.  Q is the only carried state: svd(sweeps=2) twice is svd(sweeps=4) once, bit
+        for bit.  n_factors above the matrix's numerical rank is refused (Cu2recError, CU2REC_EUNSUPPORTED) and leaves the model
+        as it was.  Returns dict(sweeps, captured = |X Q|_F^2, total = |X|_F^2)."""
+        rep = SvdReport()
+        check(lib().cu2rec_model_svd(self._h, train._h, int(sweeps), C.byref(rep)))
+        return {"sweeps": rep.sweeps, "captured": rep.captured, "total": rep.total}
+
+    def project(self, history):
+        """H Q for the rows of `history` (cu2rec_model_project) -> float32 (history.rows, n_factors): the fold-in of new users by
+        projection, p = r Q.  history: DeviceCSR with the model's column count.  project(train) is svd(train)'s P bit for bit."""
+        out = np.empty((history.rows, self.n_factors), np.float32)
+        check(lib().cu2rec_model_project(self._h, history._h, _ptr(out)))
+        return out
 
     def loss(self, ratings):
         """calculate_loss_gpu + get_error_metrics_gpu (loss.cu:40-49,195-200) -> dict(mae, rmse, sum_abs, sum_sq)."""
@@ -686,6 +718,20 @@ class SLIM(EASE):
         self.report = {"sweeps": rep.sweeps, "last_delta": rep.last_delta, "nonzeros": rep.nonzeros}
 
 
+def orthonormalize(Y):
+    """orth(Y) of PureSVD alone (cu2rec_orthonormalize): Cholesky-QR twice on the device -> float32 (n, f) with orthonormal columns
+    that span Y's.  A pivot that is not a finite number above 2^-22 of its diagonal entry (dependent columns, n < f, a NaN) raises
+    Cu2recError (CU2REC_EUNSUPPORTED) with .bad_column set."""
+    Y = np.array(Y, dtype=np.float32, order="C", ndmin=2)
+    bad = C.c_int(-1)
+    try:
+        check(lib().cu2rec_orthonormalize(_ptr(Y), Y.shape[0], Y.shape[1], C.byref(bad)))
+    except Cu2recError as e:
+        e.bad_column = bad.value
+        raise
+    return Y
+
+
 def default_mode(n_factors):
     """The default SGD mode of train(), bin/mf and bench.py: block-solve (mf_sequential.cu's result within float rounding, the mode
     certified against the 1e-4 RMSE bar); above 252 factors, where it is not compiled, `ordered` (the same result bit for bit)."""
@@ -701,7 +747,9 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     steps per row, cu2rec_train_implicit_cg; with mode "als" it is cu2rec_train_als_cg -- solver and cg_steps are read in these two modes
     only); "lmf" by logistic matrix factorization (cu2rec_train_lmf: like "ials", test_matrix may be None and the third element is the
     log-posterior at the checked sweeps; cfg.learning_rate is AdaGrad's and does not decay); "bpr" by Bayesian Personalized Ranking
-    (cu2rec_train_bpr: like "lmf", with cfg.seed drawing the negatives and no alpha).  alpha None is 40.0 for "ials" and 1.0 for
+    (cu2rec_train_bpr: like "lmf", with cfg.seed drawing the negatives and no alpha); "svd" builds PureSVD (cu2rec_train_svd:
+    cfg.total_iterations sweeps from the item factors, which a cfg.seed other than 42 draws again; test_matrix may be None, the model
+    is created with global_bias 0 unless one is given, and the third element is [captured, total] of Model.svd's report).  alpha None is 40.0 for "ials" and 1.0 for
     "lmf", where the weight multiplies a log-odds gradient and 40 x a 5-star rating saturates it.
     train_matrix / test_matrix: DeviceCSR (or HostCSR, uploaded here).
     Q / item_bias given = the 11-argument overload (caller-initialised item side, predict.cu:126);
@@ -713,11 +761,18 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     if alpha is None:
         alpha = 1.0 if mode == "lmf" else 40.0
     tr = train_matrix if isinstance(train_matrix, DeviceCSR) else DeviceCSR(train_matrix)
-    gb = tr.host.global_bias if global_bias is None else global_bias
+    gb = (0.0 if mode == "svd" else tr.host.global_bias) if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
     stats = TrainStats()
     if mode in ("bpr", "lmf", "ials"):  # the objective-driven modes
         losses = np.empty(max(cfg.total_iterations, 1), np.float64)
+    if mode == "svd":
+        rep = SvdReport()
+        check(lib().cu2rec_train_svd(tr._h, C.byref(cfg), model._h, 1 if verbose else 0, C.byref(rep)))
+        Pn, Qn, ub, ib = model.download()
+        model.close()
+        out = (Pn, Qn, np.array([rep.captured, rep.total], np.float64), ub, ib)
+        return out + (stats,) if return_stats else out
     if mode == "bpr":
         check(lib().cu2rec_train_bpr(tr._h, C.byref(cfg), model._h, 1 if verbose else 0, _ptr(losses), C.byref(stats)))
     elif mode == "lmf":

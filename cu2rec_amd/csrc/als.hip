@@ -522,6 +522,11 @@ int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows
                            [&](auto tiles) { return run_half_step<tiles(), AlsKind::Implicit>(c, side, p, max_rows, stream, cg_steps); });
 }
 
+void als_global_gram(AlsCache &c, const float *X, int ldx, int n, int f, DeviceBuffer<float> &out, hipStream_t stream) {
+    dispatch_1_to_8((f + 31) / 32, "n_factors above 252 is not supported",
+                    [&](auto tiles) { run_global_gram<tiles()>(c, X, ldx, n, f, out, stream); });
+}
+
 double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t stream) {
     const int nt = ials_tiles(o.n_factors);
     dispatch_1_to_8(nt, "cu2rec_model_implicit_objective: n_factors above 252 is not supported", [&](auto tiles) {

@@ -117,6 +117,12 @@ int ials_half_step(AlsCache &c, AlsSide &side, const AlsProblem &p, int max_rows
 // rows, longer rows are not touched.  A row whose iteration meets a non-finite or negative curvature, or ends non-finite, keeps
 // its bits and is counted in c.unsolved (allocated and zeroed by the caller)
 void ials_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, int max_rows, int cg_steps, hipStream_t stream);
+// out = X^T X over rows [0, n) of X (row stride ldx, a multiple of 4 and >= f rounded up to 4; the columns past f are never read as data)
+// in the accumulator layout [tile pair][16][64] of ceil(f / 32) tiles: the implicit half-step's G0 kernels, for a caller that wants the
+// Gram alone (svd.hip).  The rows go in tiles of kAlsChunk through c.workspace, the tiles' partial Grams are added in tile order
+void als_global_gram(AlsCache &c, const float *X, int ldx, int n, int f, DeviceBuffer<float> &out, hipStream_t stream);
+// als_cg.hip: a Gram in that layout -> dense [f][S], symmetric, the columns f .. S - 1 zero
+void als_unpack_gram(const float *acc, float *dense, int f, int S, hipStream_t stream);
 // the implicit objective L (two global Grams, one pass over the entries and both sides' rows in double); synchronises the stream
 double ials_objective(AlsCache &c, const AlsObjectiveProblem &o, hipStream_t stream);
 

@@ -305,15 +305,19 @@ void launch_cg_rows(const CgArgs &a, int order, hipStream_t stream) {
 
 }  // namespace
 
+void als_unpack_gram(const float *acc, float *dense, int f, int S, hipStream_t stream) {
+    const int threads = 256;
+    hipLaunchKernelGGL(cg_unpack_g0_kernel, dim3(static_cast<unsigned>((static_cast<size_t>(f) * S + threads - 1) / threads)), dim3(threads), 0,
+                       stream, acc, dense, f, S);
+    CU2REC_HIP(hipGetLastError());
+}
+
 void ials_cg_short_rows(AlsCache &c, const AlsSide &side, const AlsProblem &p, int max_rows, int cg_steps, hipStream_t stream) {
     const int F = p.n_factors, S = (F + 3) & ~3;
     if (F < 1 || F > kAlsMaxFactors) fail(CU2REC_EUNSUPPORTED, "cu2rec_model_als_implicit_cg: n_factors above 252 is not supported");
     const size_t dense = static_cast<size_t>(F) * S;
     if (c.g0_dense.count < dense) c.g0_dense.allocate(dense);
-    const int threads = 256;
-    hipLaunchKernelGGL(cg_unpack_g0_kernel, dim3(static_cast<unsigned>((dense + threads - 1) / threads)), dim3(threads), 0, stream,
-                       c.g0.ptr, c.g0_dense.ptr, F, S);
-    CU2REC_HIP(hipGetLastError());
+    als_unpack_gram(c.g0.ptr, c.g0_dense.ptr, F, S, stream);
     CgArgs a{side.indptr, side.indices, side.data, p, c.g0_dense.ptr, S, std::min(side.rows, max_rows), cg_steps, c.unsolved.ptr};
     launch_cg_rows<AlsKind::Implicit>(a, F, stream);
 }

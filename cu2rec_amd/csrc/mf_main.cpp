@@ -2,7 +2,7 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|svd|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus]
 //          [-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-l l1] [-n sweeps] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
@@ -32,6 +32,10 @@
 // penalty l1 (default 5), -L l2 (default 500), -n the most sweeps of coordinate descent (default 10).  It writes W to <base>_slim_w.csv
 // under the same 4,096-item rule, prints one line with the sweeps run, the last sweep's largest change and the nonzeros of W, then
 // -k's ranking line.  It refuses what -m ease refuses; -l and -n are refused without it.
+// `-m svd` builds PureSVD (cu2rec_train_svd): the config's total_iterations sweeps of block subspace iteration at its n_factors, from the
+// seed-42 item factors (another seed in the config draws them again) -- no learning rate, no regulariser.  It writes the five files, both
+// bias files zero and the global bias 0 (the scores are p . q), prints one line with the sweeps and the captured and total squared
+// norms, and with -k the ranking line.  Single GPU; it refuses -a, -C, -g, -s, -w, -W, -N, -L, -l and -n.
 // -g N (N > 1): one process per GPU -- the program forks N - 1 more ranks before anything touches a GPU, rank r takes
 // device r and a contiguous range of users, the ranks train through cu2rec_train_sharded (RCCL all-reduce of the item
 // deltas every -s iterations, default one epoch), rank 0 prints the lines and writes the five files.
@@ -62,7 +66,7 @@ namespace {
 bool g_mode_given = false;  // -m on the command line
 
 // what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
-enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn, Ease, Slim };
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn, Ease, Slim, Svd };
 
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
@@ -375,7 +379,7 @@ int run_ease(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::stri
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus] "
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|svd|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus] "
                         "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-l l1] [-n sweeps] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
@@ -493,6 +497,7 @@ int main(int argc, char **argv) {
                           : std::strcmp(optarg, "knn") == 0   ? Trainer::Knn
                           : std::strcmp(optarg, "ease") == 0  ? Trainer::Ease
                           : std::strcmp(optarg, "slim") == 0  ? Trainer::Slim
+                          : std::strcmp(optarg, "svd") == 0   ? Trainer::Svd
                                                               : Trainer::Sgd;
                 mode = trainer != Trainer::Sgd                  ? CU2REC_ALS
                        : std::strcmp(optarg, "serial") == 0     ? CU2REC_SGD_SERIAL
@@ -521,6 +526,12 @@ int main(int argc, char **argv) {
     if (trainer == Trainer::Knn &&
         (!rank_given || alpha_given || cg_given || gpus > 1 || !config_path.empty() || sync_given || merge_given)) {  // before the GPU is touched
         std::cerr << "mf: -m knn needs -k, reads no config (no -c), takes no -a and no -C, and is single-GPU only (no -g, -s, -w)\n" << usage;
+        return 1;
+    }
+    if (trainer == Trainer::Svd && (alpha_given || cg_given || gpus > 1 || sync_given || merge_given || weighting_given || neighbours_given ||
+                                    l2_given || l1_given || sweeps_given)) {  // before the GPU is touched
+        std::cerr << "mf: -m svd takes no -a, -C, -W, -N, -L, -l or -n (its sweeps are the config's total_iterations), and is single-GPU only (no -g, -s, -w)\n"
+                  << usage;
         return 1;
     }
     const bool is_slim = trainer == Trainer::Slim;
@@ -604,9 +615,12 @@ int main(int argc, char **argv) {
         mode = effective_mode(mode, cfg.n_factors);
 
         cu2rec::CsrHandle d_train(train), d_test(test);
-        cu2rec::ModelHandle model(train.rows, train.cols, cfg.n_factors, train.global_bias);
+        const float global_bias = trainer == Trainer::Svd ? 0.f : train.global_bias;  // PureSVD's scores are p . q
+        cu2rec::ModelHandle model(train.rows, train.cols, cfg.n_factors, global_bias);
         std::vector<float> losses(static_cast<size_t>(cfg.total_iterations > 0 ? cfg.total_iterations : 1));
-        if (trainer == Trainer::Bpr)  // like -m ials: the test file is read, but only -k looks at it
+        if (trainer == Trainer::Svd)  // like -m ials: the test file is read, but only -k looks at it
+            cu2rec::check(cu2rec_train_svd(d_train.h, &cfg, model.h, 1, nullptr));
+        else if (trainer == Trainer::Bpr)  // like -m ials: the test file is read, but only -k looks at it
             cu2rec::check(cu2rec_train_bpr(d_train.h, &cfg, model.h, 1, nullptr, nullptr));
         else if (trainer == Trainer::Lmf)
             cu2rec::check(cu2rec_train_lmf(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
@@ -626,7 +640,7 @@ int main(int argc, char **argv) {
         // mf.cu:65-87: outputs go next to the training file, named <base>_f<F>_<component>.csv
         std::string parent_dir, base;
         output_place(train_path, parent_dir, base);
-        const float gb = train.global_bias;
+        const float gb = global_bias;
         const int f = cfg.n_factors;
         cu2rec::check(cu2rec_write_component(parent_dir.c_str(), base.c_str(), "p", P.data(), train.rows, f, f));
         cu2rec::check(cu2rec_write_component(parent_dir.c_str(), base.c_str(), "q", Q.data(), train.cols, f, f));

@@ -1,7 +1,7 @@
 // bin/predict -- partial fit for new users against a trained model, then recommendations.
 // Drop-in for the reference CLI (predict.cu:72-146):
 //
-//   bin/predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-I alpha] [-k K] user_ratings.csv
+//   bin/predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-I alpha] [-P] [-k K] user_ratings.csv
 //
 // Q, item_bias and global_bias come from the files bin/mf wrote; only the users' factor rows and biases are
 // trained (is_train = false).  Unlike the reference, the frozen-item flag really reaches the device (there
@@ -21,6 +21,9 @@
 // -I alpha: the implicit-feedback fold-in for a model trained by bin/mf -m ials -- ONE implicit user half-step against the frozen
 // q.csv (cu2rec_model_als_implicit with confidence weight alpha * r and the config's P_reg; every item of q.csv counts, the
 // file's items as positives).  Not together with -A.
+//
+// -P: the fold-in for a model built by bin/mf -m svd -- no fit at all, the new users' rows are the projection p = r Q of their
+// ratings on the frozen q.csv (cu2rec_model_project), their biases 0.  Not together with -A or -I.
 //
 //   bin/predict -c config -q q.csv -S [-k K] item_ids.txt
 //
@@ -106,16 +109,17 @@ int similar_items(const cu2rec_config &cfg, const std::string &q_path, const std
 int main(int argc, char **argv) {
     if (argc < 2) return 2;  // predict.cu:73-75
     std::string config_path, item_bias_path, global_bias_path, q_path;
-    bool many_users = false, similar = false, als = false, implicit = false;
+    bool many_users = false, similar = false, als = false, implicit = false, projection = false;
     float alpha = 0.f;  // -I
     int top_k = 0;  // 0: every unrated item, as the reference prints
     const char *k_arg = nullptr;
     int opt;
-    while ((opt = getopt(argc, argv, "c:i:g:q:uk:SAI:")) != -1) {
+    while ((opt = getopt(argc, argv, "c:i:g:q:uk:SAI:P")) != -1) {
         switch (opt) {
             case 'u': many_users = true; break;
             case 'S': similar = true; break;
             case 'A': als = true; break;
+            case 'P': projection = true; break;
             case 'I': {
                 char *end = nullptr;
                 implicit = true;
@@ -155,8 +159,12 @@ int main(int argc, char **argv) {
             return 3;
         }
     }
+    if (projection && (als || implicit)) {
+        std::cerr << "predict: -P excludes -A and -I\n";
+        return 2;
+    }
     if (optind >= argc || config_path.empty() || item_bias_path.empty() || global_bias_path.empty() || q_path.empty()) {
-        std::cerr << "usage: predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-I alpha] [-k K] user_ratings.csv\n";
+        std::cerr << "usage: predict -c config -i item_bias.csv -g global_bias.csv -q q.csv [-u] [-A] [-I alpha] [-P] [-k K] user_ratings.csv\n";
         return 2;
     }
     if (als && implicit) {
@@ -225,8 +233,15 @@ int main(int argc, char **argv) {
             std::copy(one_p.begin(), one_p.end(), P0.begin() + static_cast<size_t>(u) * f);
             ub0[u] = one_ub[0];
         }
+        if (projection) {  // p = r Q through a first model, of which only Q is read; the users' biases are 0
+            cu2rec::ModelHandle items_only(B, n_items, f, global_bias, P0.data(), Q.data, ub0.data(), item_bias.data);
+            cu2rec::check(cu2rec_model_project(items_only.h, d_users.h, P0.data()));
+            std::fill(ub0.begin(), ub0.end(), 0.f);
+        }
         cu2rec::ModelHandle model(B, n_items, f, global_bias, P0.data(), Q.data, ub0.data(), item_bias.data);
-        if (als || implicit) {  // one exact user half-step: every user's optimum against the frozen items
+        if (projection) {
+            // nothing is fitted
+        } else if (als || implicit) {  // one exact user half-step: every user's optimum against the frozen items
             const cu2rec_hyper h{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
             int unsolved = 0;
             cu2rec::check(implicit ? cu2rec_model_als_implicit(model.h, d_users.h, &h, alpha, CU2REC_SIDE_USERS, &unsolved)

@@ -921,6 +921,59 @@ typedef struct { int sweeps; float last_delta; long long nonzeros; } cu2rec_slim
 int cu2rec_slim_create(const cu2rec_csr *train, float l1, float l2, int positive, int max_sweeps, float tol,
                        cu2rec_slim_report *report /* may be NULL */, cu2rec_ease **out);
 
+/* ------------------------------------------------------------------------------------------
+ * PureSVD (Cremonesi, Koren, Turrin, "Performance of Recommender Algorithms on Top-N Recommendation Tasks", RecSys 2010): the rank-f
+ * truncated SVD of the rating matrix, scored as X Q Q^T.  The only training-free baseline that is a FACTOR model: its result is a
+ * (P, Q) pair that cu2rec_model_topk, cu2rec_model_rank_metrics, cu2rec_model_similar, cu2rec_model_top_users, the five files and
+ * bin/predict serve unchanged.  No learning rate, no regulariser, no seed beyond the start.
+ *
+ * X is the users x items matrix of the values `train` stores, entries that repeat a column within a row summed; f = n_factors.  Block
+ * subspace (orthogonal) iteration from Q = the model's current item factors (a fresh model: initialize_normal_array, seed 42):
+ *     each sweep:  Y = orth(X Q)   Q = orth(X^T Y)        at the end:  P = X Q,  user_bias = item_bias = 0
+ * orth is Cholesky-QR applied twice; one pass forms G = Y^T Y, factors G = L L^T and sets Y <- Y L^-T, all in float32.  The scores
+ * P Q^T depend only on the subspace Q spans, so there are no singular values, no ordering of the factors and no Rayleigh-Ritz step;
+ * orthonormalising after every single multiply keeps cond(G) at (sigma_1 / sigma_f)^2.  Scores are p . q exactly only with a model
+ * whose global_bias is 0 (cu2rec_train_svd insists on it; cu2rec_model_svd does not touch the model's).
+ *
+ * A pivot of a factorisation that is not a finite number above 2^-22 of its own diagonal entry (EASE's rule: f above the numerical
+ * rank, a zero matrix, a NaN value) fails the call with CU2REC_EUNSUPPORTED, cu2rec_last_error() naming the sweep, the product and the
+ * column.  The sweeps run in scratch buffers and the model is written at the end: a call that fails leaves P, Q and both biases bit
+ * for bit as they were.  The host reads one status word per pass of orth: four stream synchronisations per sweep.
+ *
+ * Limits: one GPU; f <= CU2REC_ALS_MAX_FACTORS, train's rows >= f and cols >= f (else CU2REC_EUNSUPPORTED); sweeps >= 1, train within
+ * the model's shape, non-null m / train (else CU2REC_EINVAL); all checked before the device or the model is touched.  Rows of the
+ * model outside train's shape become zero rows.
+ *
+ * No float atomics; the order of every sum is a function of the row's length and f alone (rows longer than CU2REC_ALS_CHUNK are cut
+ * by the ALS row plan, the chunks added in chunk order): a model built twice is bit-identical, and since Q is the only state that is
+ * carried, sweeps = 2 twice is sweeps = 4 once, bit for bit.
+ *
+ * report (may be NULL): the sweeps run, captured = |X Q|_F^2 = |P|_F^2 and total = |X|_F^2, both summed in double in a fixed order;
+ * captured / total is the share of the matrix's energy the subspace holds (at most 1 up to float rounding). */
+typedef struct { int sweeps; double captured; double total; } cu2rec_svd_report;
+int cu2rec_model_svd(cu2rec_model *m, const cu2rec_csr *train, int sweeps, cu2rec_svd_report *report /* may be NULL */);
+/* out = H Q (host, history rows x n_factors, dense): the fold-in of new users by projection, p = r Q, for any CSR with the model's
+ * column count (another: CU2REC_EINVAL).  The kernel and the row strides are cu2rec_model_svd's last product: projecting the training
+ * matrix gives the model's P bit for bit.  The model is only read. */
+int cu2rec_model_project(cu2rec_model *m, const cu2rec_csr *history, float *out);
+/* PureSVD as a trainer, beside cu2rec_train_implicit: cfg->total_iterations sweeps of cu2rec_model_svd on `model`, whose n_factors must
+ * be cfg->n_factors and whose global_bias must be 0 (else CU2REC_EINVAL).  The start is the model's item factors -- a fresh model's are
+ * the seed-42 draw; a cfg->seed other than 42 first draws them again, initialize_normal_array(cols x f, f, seed).  Everything else in
+ * cfg is ignored; cfg->cur_iterations advances by the sweeps.  verbose: one line,
+ * "SVD: Factors: %d Sweeps: %d Captured: %f Total: %f Share: %f". */
+int cu2rec_train_svd(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, int verbose, cu2rec_svd_report *report);
+/* The two stages alone, for tests and tools.
+ * cu2rec_csr_multiply: out[row, 0 : f] = sum over the row's entries of r * D[column, 0 : f] for every row of csr (transpose != 0: of
+ * its item-major view, out = X^T D).  D: host, dense, (transpose ? rows : cols) x f.  It is staged at the model's row strides -- the
+ * user side's rows at f rounded up to 4 floats, the item side's at f rounded up to 32, the padding filled with NaNs -- and out
+ * (host) receives the PADDED rows as the device wrote them: (transpose ? cols : rows) x cu2rec_csr_multiply_stride(transpose, f)
+ * floats, the padding columns zero.  f outside [1, CU2REC_ALS_MAX_FACTORS]: CU2REC_EUNSUPPORTED. */
+int cu2rec_csr_multiply(const cu2rec_csr *csr, int transpose, const float *D, int f, float *out);
+int cu2rec_csr_multiply_stride(int transpose, int f);
+/* cu2rec_orthonormalize: Y (host, n x f, dense) <- orth(Y) in place.  A refused pivot is CU2REC_EUNSUPPORTED with *bad_column (may be
+ * NULL; -1 otherwise) its column and Y untouched; n < f is refused before the device with column n. */
+int cu2rec_orthonormalize(float *Y, int n, int f, int *bad_column);
+
 #ifdef __cplusplus
 }
 #endif
