@@ -163,6 +163,12 @@ SIGNATURES = {
     "cu2rec_csr_bpr_negatives": (C.c_int, [_P, C.c_uint64, C.c_int, _P]),
     "cu2rec_train_bpr": (C.c_int, [_P, C.POINTER(Config), _P, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_train_lmf": (C.c_int, [_P, C.POINTER(Config), _P, C.c_float, C.c_int, _P, C.POINTER(TrainStats)]),
+    "cu2rec_model_softmax": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_int, _ip]),
+    "cu2rec_model_softmax_gradient": (C.c_int, [_P, _P, C.POINTER(Hyper), C.c_int, _P, _P]),
+    "cu2rec_model_softmax_objective": (C.c_int, [_P, _P, C.POINTER(Hyper), _dp]),
+    "cu2rec_model_softmax_lse": (C.c_int, [_P, _P, _P]),
+    "cu2rec_model_softmax_mass": (C.c_int, [_P, _P, _P]),
+    "cu2rec_train_softmax": (C.c_int, [_P, C.POINTER(Config), _P, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_train": (C.c_int, [_P, _P, C.POINTER(Config), _P, C.c_int, C.c_int, _P, C.POINTER(TrainStats)]),
     "cu2rec_shard_plan": (C.c_int, [C.c_int, C.c_int, _P]),
     "cu2rec_comm_unique_id": (C.c_int, [_P]),

@@ -454,6 +454,46 @@ class Model:
         check(lib().cu2rec_model_bpr_objective(self._h, train._h, C.byref(h), int(seed), int(sweep), C.byref(L), C.byref(n), C.byref(m)))
         return L.value, n.value, m.value
 
+    def softmax(self, train, hyper, side="both", sweeps=1):
+        """Softmax matrix factorization half-steps (cu2rec_model_softmax; the multinomial likelihood of Liang et al. 2018, full
+        batch): a user's items form one distribution pi_ui = softmax_i(s_ui) over every item of train's shape, a stored entry
+        (u, i, r) is r draws from it, and a half-step is the gradient of sum w log pi_ui minus the regularisers, then lmf()'s AdaGrad
+        step at hyper's learning rate.  There is no alpha; user biases and the global bias cancel and never move; of hyper's
+        regularisers P_reg, Q_reg and item_bias_reg are read.  side and sweeps as in als().  The AdaGrad accumulators are lmf()'s
+        (lmf_state, lmf_reset): the model has one set, reset it between trainers.  New users are fitted with side="users" on a model
+        that shares Q.  Returns the number of rows left unchanged (a non-finite gradient or step), summed over the half-steps."""
+        h = _hyper(hyper)
+        return _half_steps(side, sweeps, lambda s, n: lib().cu2rec_model_softmax(self._h, train._h, C.byref(h), s, n))
+
+    def softmax_gradient(self, train, hyper, side):
+        """The gradient softmax() would step along for side "users" or "items" (cu2rec_model_softmax_gradient) -> (grad, bias_grad)
+        shaped as lmf_gradient()'s; the users' bias_grad is all zeros.  The model and the accumulators are untouched."""
+        h = _hyper(hyper)
+        s, grad, bias = self._gradient_out(train, side)
+        check(lib().cu2rec_model_softmax_gradient(self._h, train._h, C.byref(h), s, _ptr(grad), _ptr(bias)))
+        return grad, bias
+
+    def softmax_objective(self, train, hyper):
+        """The objective softmax() climbs, at the model's current values (cu2rec_model_softmax_objective) -> float."""
+        h = _hyper(hyper)
+        L = C.c_double()
+        check(lib().cu2rec_model_softmax_objective(self._h, train._h, C.byref(h), C.byref(L)))
+        return L.value
+
+    def softmax_lse(self, train):
+        """log sum_i exp(s_ui) over every item of train's shape, for every user of train (cu2rec_model_softmax_lse) -> float32
+        (train.rows,), as the half-steps form it."""
+        lse = np.empty(train.rows, np.float32)
+        check(lib().cu2rec_model_softmax_lse(self._h, train._h, _ptr(lse)))
+        return lse
+
+    def softmax_mass(self, train):
+        """sum_i pi_ui of every user of train as the user half-step's matrix-core product forms it (cu2rec_model_softmax_mass) ->
+        float32 (train.rows,): 1 within rounding."""
+        mass = np.empty(train.rows, np.float32)
+        check(lib().cu2rec_model_softmax_mass(self._h, train._h, _ptr(mass)))
+        return mass
+
     def svd(self, train, sweeps=4):
         """PureSVD (cu2rec_model_svd; Cremonesi, Koren, Turrin 2010): `sweeps` sweeps of block subspace iteration on the matrix
         `train` stores, from the model's current item factors -- Y = orth(X Q), Q = orth(X^T Y), orth being Cholesky-QR twice --
@@ -747,7 +787,8 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     steps per row, cu2rec_train_implicit_cg; with mode "als" it is cu2rec_train_als_cg -- solver and cg_steps are read in these two modes
     only); "lmf" by logistic matrix factorization (cu2rec_train_lmf: like "ials", test_matrix may be None and the third element is the
     log-posterior at the checked sweeps; cfg.learning_rate is AdaGrad's and does not decay); "bpr" by Bayesian Personalized Ranking
-    (cu2rec_train_bpr: like "lmf", with cfg.seed drawing the negatives and no alpha); "svd" builds PureSVD (cu2rec_train_svd:
+    (cu2rec_train_bpr: like "lmf", with cfg.seed drawing the negatives and no alpha); "softmax" by softmax matrix factorization
+    (cu2rec_train_softmax: like "lmf" without an alpha, the third element its objective); "svd" builds PureSVD (cu2rec_train_svd:
     cfg.total_iterations sweeps from the item factors, which a cfg.seed other than 42 draws again; test_matrix may be None, the model
     is created with global_bias 0 unless one is given, and the third element is [captured, total] of Model.svd's report).  alpha None is 40.0 for "ials" and 1.0 for
     "lmf", where the weight multiplies a log-odds gradient and 40 x a 5-star rating saturates it.
@@ -764,7 +805,7 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
     gb = (0.0 if mode == "svd" else tr.host.global_bias) if global_bias is None else global_bias
     model = Model(tr.rows, tr.cols, cfg.n_factors, gb, P=P, Q=Q, user_bias=user_bias, item_bias=item_bias)
     stats = TrainStats()
-    if mode in ("bpr", "lmf", "ials"):  # the objective-driven modes
+    if mode in ("bpr", "lmf", "softmax", "ials"):  # the objective-driven modes
         losses = np.empty(max(cfg.total_iterations, 1), np.float64)
     if mode == "svd":
         rep = SvdReport()
@@ -777,6 +818,8 @@ def train(train_matrix, test_matrix, cfg, Q=None, item_bias=None, global_bias=No
         check(lib().cu2rec_train_bpr(tr._h, C.byref(cfg), model._h, 1 if verbose else 0, _ptr(losses), C.byref(stats)))
     elif mode == "lmf":
         check(lib().cu2rec_train_lmf(tr._h, C.byref(cfg), model._h, float(alpha), 1 if verbose else 0, _ptr(losses), C.byref(stats)))
+    elif mode == "softmax":
+        check(lib().cu2rec_train_softmax(tr._h, C.byref(cfg), model._h, 1 if verbose else 0, _ptr(losses), C.byref(stats)))
     elif mode == "ials":
         if solver == "cg":
             check(lib().cu2rec_train_implicit_cg(tr._h, C.byref(cfg), model._h, float(alpha), int(cg_steps), 1 if verbose else 0,

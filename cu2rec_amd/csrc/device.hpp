@@ -16,6 +16,7 @@
 #include "knn.hpp"
 #include "lmf.hpp"
 #include "ordered.hpp"
+#include "softmax.hpp"
 
 struct cu2rec_csr;
 struct cu2rec_model;
@@ -138,6 +139,17 @@ struct DeviceModel {
     // the BPR objective at the current model over sweep `sweep`'s triples, their number and the number with x_e > 0 (synchronises)
     double bpr_objective(const DeviceCsr &train, const cu2rec_hyper &h, uint64_t seed, int sweep, long long *n_triples,
                          long long *n_ordered, hipStream_t stream);
+    // one softmax-MF half-step (softmax.hpp: the users' log-sum-exp, the gradient over every pair, then the logistic trainer's AdaGrad
+    // step on ITS accumulators); returns the rows left unchanged
+    int softmax(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream);
+    // the same gradient to the host, as lmf_gradient; the model and the accumulators untouched
+    void softmax_gradient(const DeviceCsr &train, const cu2rec_hyper &h, int side, float *grad_out, float *bias_grad_out, hipStream_t stream);
+    // the softmax objective at the current model (synchronises)
+    double softmax_objective(const DeviceCsr &train, const cu2rec_hyper &h, hipStream_t stream);
+    // every user's log-sum-exp and sum_i pi_ui (the dense pass's column f) to the host, U floats each; either may be null
+    void softmax_lse(const DeviceCsr &train, float *lse_out, float *mass_out, hipStream_t stream);
+    // the argument checks of the softmax calls, before the device or the model is touched; fn names the caller
+    void softmax_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, std::optional<int> side) const;
     // what the logistic and the BPR calls end in: lmf_st.grad's first n_own rows to the host (synchronises); the AdaGrad step from
     // lmf_st.grad on the accumulators of p's side, which returns the rows left unchanged
     void download_gradient(int n_own, float *grad_out, float *bias_grad_out, hipStream_t stream);
@@ -152,6 +164,7 @@ struct DeviceModel {
     bool swap_pending = false;
     mutable DeviceBuffer<double> workspace;
     LmfState lmf_st;  // AdaGrad accumulators and workspace of the logistic trainer, created by its first call
+    SoftmaxState softmax_st;  // the users' log-sum-exp and row weights of the last softmax call
     int rows, cols, n_factors;
     int ld;   // row stride of P in floats: n_factors rounded up to 4 (16-byte aligned rows)
     int ldq;  // row stride of Q: rounded up to 32 floats, so that every item row is a whole number of 128-byte lines --

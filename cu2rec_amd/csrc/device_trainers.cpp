@@ -244,6 +244,71 @@ double DeviceModel::bpr_objective(const DeviceCsr &train, const cu2rec_hyper &h,
     return s[0] - 0.5 * (static_cast<double>(h.P_reg) * s[1] + static_cast<double>(h.Q_reg) * s[2] + static_cast<double>(h.item_bias_reg) * s[3]);
 }
 
+// Softmax matrix factorization (include/cu2rec_amd.h: cu2rec_model_softmax).  The logistic calls' checks in their order, without an
+// alpha and without the user bias' regulariser: the user biases cancel in the softmax and are never trained.
+void DeviceModel::softmax_check(const char *fn, const DeviceCsr &train, const cu2rec_hyper &h, std::optional<int> side) const {
+    const Need need{fn};
+    need(!side || is_side(*side), CU2REC_EINVAL, ": side must be CU2REC_SIDE_USERS or CU2REC_SIDE_ITEMS");
+    for (float reg : {h.P_reg, h.Q_reg, h.item_bias_reg})
+        need(finite_at_least(reg, 0.f), CU2REC_EINVAL, ": P_reg, Q_reg and item_bias_reg must be finite and >= 0");
+    need(std::isfinite(h.learning_rate) && h.learning_rate > 0.f, CU2REC_EINVAL, ": learning_rate must be finite and > 0");
+    need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": entries exceed the model's shape");
+    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
+}
+
+namespace {
+// softmax_st of the users inside `train` at the model's current values -> the user side's view
+LmfProblem softmax_enter(DeviceModel &m, const DeviceCsr &train, const cu2rec_hyper &h, hipStream_t stream) {
+    enter(m);
+    const LmfProblem users = lmf_problem(m, train, h, 1.f, true, stream);
+    cu2rec::softmax_lse(m.softmax_st, users, stream);
+    return users;
+}
+}  // namespace
+
+int DeviceModel::softmax(const DeviceCsr &train, const cu2rec_hyper &h, int side, hipStream_t stream) {
+    softmax_check("cu2rec_model_softmax", train, h, side);
+    const LmfProblem user_side = softmax_enter(*this, train, h, stream);
+    lmf_ensure_state(*this);
+    const bool users = side == CU2REC_SIDE_USERS;
+    const LmfProblem p = users ? user_side : lmf_problem(*this, train, h, 1.f, false, stream);
+    cu2rec::softmax_gradient(lmf_st, softmax_st, p, users, stream);
+    return adagrad_half_step(p, users, stream);
+}
+
+void DeviceModel::softmax_gradient(const DeviceCsr &train, const cu2rec_hyper &h, int side, float *grad_out, float *bias_grad_out,
+                                   hipStream_t stream) {
+    softmax_check("cu2rec_model_softmax_gradient", train, h, side);
+    const LmfProblem user_side = softmax_enter(*this, train, h, stream);
+    const bool users = side == CU2REC_SIDE_USERS;
+    const LmfProblem p = users ? user_side : lmf_problem(*this, train, h, 1.f, false, stream);
+    if (p.n_own == 0) return;
+    cu2rec::softmax_gradient(lmf_st, softmax_st, p, users, stream);
+    download_gradient(p.n_own, grad_out, bias_grad_out, stream);
+}
+
+double DeviceModel::softmax_objective(const DeviceCsr &train, const cu2rec_hyper &h, hipStream_t stream) {
+    softmax_check("cu2rec_model_softmax_objective", train, h, {});
+    const LmfProblem users = softmax_enter(*this, train, h, stream);
+    double s[4];
+    softmax_objective_sums(lmf_st, softmax_st, users, train.nnz, s, stream);
+    return s[0] - 0.5 * (static_cast<double>(h.P_reg) * s[1] + static_cast<double>(h.Q_reg) * s[2] + static_cast<double>(h.item_bias_reg) * s[3]);
+}
+
+void DeviceModel::softmax_lse(const DeviceCsr &train, float *lse_out, float *mass_out, hipStream_t stream) {
+    const Need need{"cu2rec_model_softmax_lse"};
+    need(train.rows <= rows && train.max_item < cols && train.cols <= cols, CU2REC_EINVAL, ": entries exceed the model's shape");
+    need(n_factors <= kAlsMaxFactors, CU2REC_EUNSUPPORTED, ": n_factors above 252 is not supported");
+    const LmfProblem users = softmax_enter(*this, train, cu2rec_hyper{}, stream);
+    if (train.rows == 0) return;
+    if (mass_out) {
+        cu2rec::softmax_gradient(lmf_st, softmax_st, users, true, stream, /*mass=*/true);
+        download_gradient(train.rows, nullptr, mass_out, stream);
+    }
+    CU2REC_HIP(hipStreamSynchronize(stream));
+    if (lse_out) softmax_st.lse.download(lse_out, train.rows);
+}
+
 void DeviceModel::lmf_download_state(float *aP, float *aQ, float *a_ub, float *a_ib) {
     if (!lmf_st.aP.ptr) {
         if (aP) std::fill(aP, aP + static_cast<size_t>(rows) * n_factors, 0.f);
@@ -370,6 +435,43 @@ int cu2rec_csr_bpr_negatives(const cu2rec_csr *train, uint64_t seed, int sweep, 
         bpr_negatives(t, p, seed, sweep, nullptr);
         CU2REC_HIP(hipStreamSynchronize(nullptr));
         if (t.nnz) t.bpr.neg.download(neg_out, t.nnz);
+    });
+}
+
+int cu2rec_model_softmax(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *n_unchanged) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_softmax: null argument");
+        const int n = m->impl.softmax(train->impl, *hyper, side, nullptr);
+        if (n_unchanged) *n_unchanged = n;
+    });
+}
+
+int cu2rec_model_softmax_gradient(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, float *grad_out,
+                                  float *bias_grad_out) {
+    return guarded([&] {
+        require(m && train && hyper, "cu2rec_model_softmax_gradient: null argument");
+        m->impl.softmax_gradient(train->impl, *hyper, side, grad_out, bias_grad_out, nullptr);
+    });
+}
+
+int cu2rec_model_softmax_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, double *L) {
+    return guarded([&] {
+        require(m && train && hyper && L, "cu2rec_model_softmax_objective: null argument");
+        *L = m->impl.softmax_objective(train->impl, *hyper, nullptr);
+    });
+}
+
+int cu2rec_model_softmax_lse(cu2rec_model *m, const cu2rec_csr *train, float *lse_out) {
+    return guarded([&] {
+        require(m && train && lse_out, "cu2rec_model_softmax_lse: null argument");
+        m->impl.softmax_lse(train->impl, lse_out, nullptr, nullptr);
+    });
+}
+
+int cu2rec_model_softmax_mass(cu2rec_model *m, const cu2rec_csr *train, float *mass_out) {
+    return guarded([&] {
+        require(m && train && mass_out, "cu2rec_model_softmax_mass: null argument");
+        m->impl.softmax_lse(train->impl, nullptr, mass_out, nullptr);
     });
 }
 

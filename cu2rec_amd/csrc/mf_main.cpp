@@ -2,7 +2,7 @@
 // Drop-in for the reference CLI (mf.cu:16-99): same arguments, same stdout lines, same output
 // files; built on the C ABI of libcu2rec_amd.
 //
-//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|svd|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus]
+//   bin/mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|svd|softmax|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus]
 //          [-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-l l1] [-n sweeps] [-k K [-t T]] train.csv test.csv
 // Default mode: blocksolve -- mf_sequential.cu's result within float rounding (the mode bench.py certifies against the
 // 1e-4 RMSE bar); n_factors above 252, where block-solve is not compiled, falls back to `ordered` (the same result bit
@@ -19,6 +19,9 @@
 // `-m bpr` trains by Bayesian Personalized Ranking (cu2rec_train_bpr): total_iterations deterministic full-batch sweeps over one
 // sampled negative per stored entry (the config's seed), AdaGrad at the config's learning rate; single GPU, no -a, no -C.  Like
 // `-m ials` and `-m lmf` it reads the test file only for -k.
+// `-m softmax` trains by softmax matrix factorization (cu2rec_train_softmax): total_iterations full-batch sweeps under the multinomial
+// likelihood, AdaGrad at the config's learning rate, the stored values as weights; user biases stay as they start.  It reads the test
+// file only for -k, writes the five files, and refuses -a, -C, -g, -s, -w, -W, -N, -L, -l and -n.
 // `-m knn` trains nothing: it builds the item-neighbourhood recommender (cu2rec_knn_create) on the training file -- -W the weighting
 // (default cosine; bm25 with k1 = 100, b = 0.8), -N the neighbours kept per item (default 20, at most 256) -- writes every item's list to
 // <base>_knn_ids.csv and <base>_knn_sims.csv (items x N, -1 / nan padding) where the five files would go, and prints -k's ranking line
@@ -66,7 +69,7 @@ namespace {
 bool g_mode_given = false;  // -m on the command line
 
 // what -m names: one of the SGD modes (a cu2rec_sgd_mode, through cu2rec_train), or a full-batch trainer with an entry point of its own
-enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Knn, Ease, Slim, Svd };
+enum class Trainer { Sgd, Als, AlsCg, Ials, Lmf, Bpr, Softmax, Knn, Ease, Slim, Svd };
 
 // the default mode is block-solve; where it is not compiled (n_factors > 252) the default becomes `ordered`: the same
 // sequential result, bit for bit instead of within float rounding
@@ -379,7 +382,7 @@ int run_ease(const cu2rec::HostCsr &train, cu2rec::HostCsr test, const std::stri
 }  // namespace
 
 int main(int argc, char **argv) {
-    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|svd|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus] "
+    const char *usage = "usage: mf [-c config] [-m blocksolve|ordered|hogwild|serial|pingpong|als|alscg|svd|softmax|ials|lmf|bpr|knn|ease|slim] [-a alpha] [-C cg_steps] [-g gpus] "
                         "[-s sync_every] [-w adaptive|mean|weighted|sum] [-W count|cosine|tfidf|bm25] [-N neighbours] [-L l2] [-l l1] [-n sweeps] [-k K [-t T]] train.csv test.csv\n";
     if (argc < 2) {  // mf.cu:17-19 (the reference says nothing; the usage line goes to stderr)
         std::cerr << usage;
@@ -494,6 +497,7 @@ int main(int argc, char **argv) {
                           : std::strcmp(optarg, "ials") == 0  ? Trainer::Ials
                           : std::strcmp(optarg, "lmf") == 0   ? Trainer::Lmf
                           : std::strcmp(optarg, "bpr") == 0   ? Trainer::Bpr
+                          : std::strcmp(optarg, "softmax") == 0 ? Trainer::Softmax
                           : std::strcmp(optarg, "knn") == 0   ? Trainer::Knn
                           : std::strcmp(optarg, "ease") == 0  ? Trainer::Ease
                           : std::strcmp(optarg, "slim") == 0  ? Trainer::Slim
@@ -568,6 +572,12 @@ int main(int argc, char **argv) {
         std::cerr << "mf: -m bpr takes no -a and no -C, and is single-GPU only (not with -g)\n" << usage;
         return 1;
     }
+    if (trainer == Trainer::Softmax && (alpha_given || cg_given || gpus > 1 || sync_given || merge_given || weighting_given ||
+                                        neighbours_given || l2_given || l1_given || sweeps_given)) {  // before the GPU is touched
+        std::cerr << "mf: -m softmax takes no -a, -C, -W, -N, -L, -l or -n (its sweeps are the config's total_iterations), and is single-GPU only (no -g, -s, -w)\n"
+                  << usage;
+        return 1;
+    }
     if ((weighting_given || neighbours_given) &&
         (trainer != Trainer::Knn || weighting < 0 || neighbours < 1 || neighbours > CU2REC_KNN_MAX_NEIGHBOURS)) {
         std::cerr << "mf: -W and -N need -m knn, a weighting of count, cosine, tfidf or bm25, and between 1 and " << CU2REC_KNN_MAX_NEIGHBOURS
@@ -622,6 +632,8 @@ int main(int argc, char **argv) {
             cu2rec::check(cu2rec_train_svd(d_train.h, &cfg, model.h, 1, nullptr));
         else if (trainer == Trainer::Bpr)  // like -m ials: the test file is read, but only -k looks at it
             cu2rec::check(cu2rec_train_bpr(d_train.h, &cfg, model.h, 1, nullptr, nullptr));
+        else if (trainer == Trainer::Softmax)  // like -m ials: the test file is read, but only -k looks at it
+            cu2rec::check(cu2rec_train_softmax(d_train.h, &cfg, model.h, 1, nullptr, nullptr));
         else if (trainer == Trainer::Lmf)
             cu2rec::check(cu2rec_train_lmf(d_train.h, &cfg, model.h, alpha, 1, nullptr, nullptr));
         else if (trainer == Trainer::Ials && cg_given)

@@ -155,7 +155,33 @@ void train_bpr(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &mode
         [&](const cu2rec_hyper &h, uint64_t t) { return model.bpr_objective(train_csr, h, seed, static_cast<int>(t), nullptr, nullptr, nullptr); });
 }
 
+// Softmax matrix factorization (include/cu2rec_amd.h: cu2rec_train_softmax): full-batch softmax sweeps and their objective.  The
+// accumulators are the logistic trainer's; the learning rate is AdaGrad's and does not decay.
+void train_softmax(const DeviceCsr &train_csr, cu2rec_config &cfg, DeviceModel &model, bool verbose, double *objectives,
+                   cu2rec_train_stats *stats) {
+    require(cfg.n_factors == model.n_factors, "cu2rec_train_softmax: cfg.n_factors differs from the model's");
+    require(cfg.total_iterations >= 0 && cfg.check_error > 0, "cu2rec_train_softmax: bad iteration counts");
+    const cu2rec_hyper hyper{cfg.learning_rate, cfg.P_reg, cfg.Q_reg, cfg.user_bias_reg, cfg.item_bias_reg};
+    model.softmax_check("cu2rec_train_softmax", train_csr, hyper, {});
+    model.lmf_reset();
+    train_by_objective(
+        "softmax", cfg, verbose, objectives, stats,
+        [&](const cu2rec_hyper &h, int side, hipStream_t s, uint64_t) {
+            return (side == CU2REC_SIDE_USERS ? train_csr.rows : train_csr.cols) - model.softmax(train_csr, h, side, s);
+        },
+        [&](const cu2rec_hyper &h, uint64_t) { return model.softmax_objective(train_csr, h, nullptr); });
+}
+
 }  // namespace cu2rec
+
+extern "C" int cu2rec_train_softmax(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, int verbose, double *objectives,
+                                    cu2rec_train_stats *stats) {
+    using namespace cu2rec;
+    return guarded([&] {
+        require(train && cfg && model, "cu2rec_train_softmax: null argument");
+        cu2rec::train_softmax(unwrap(train), *cfg, unwrap(model), verbose != 0, objectives, stats);
+    });
+}
 
 extern "C" int cu2rec_train_lmf(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, float alpha, int verbose,
                                 double *objectives, cu2rec_train_stats *stats) {

@@ -641,6 +641,59 @@ int cu2rec_model_bpr_objective(cu2rec_model *m, const cu2rec_csr *train, const c
 int cu2rec_csr_bpr_negatives(const cu2rec_csr *train, uint64_t seed, int sweep, int *neg_out);
 
 /* ------------------------------------------------------------------------------------------
+ * Implicit feedback: softmax matrix factorization -- matrix factorization under the multinomial likelihood of Mult-DAE / Mult-VAE
+ * (Liang, Krishnan, Hoffman, Jebara: Variational Autoencoders for Collaborative Filtering, WWW 2018, sections 2-3), full batch.
+ * U = train rows, I = train cols; a stored entry (u, i, r) has weight w = r (repeated pairs count separately; there is no alpha:
+ * scaling w only rescales the likelihood against the regularisers); W_u = the sum of w over the entries of u.  The score is the
+ * one the ranking calls and cu2rec_model_lmf use, s_ui = ((global_bias + user_bias[u]) + item_bias[i]) + p_u . q_i.  For user u
+ * the items form ONE distribution and the user's interactions are draws from it:
+ *   lse_u = log sum_(i < I) exp(s_ui)       (every item of train's shape, stored or not)
+ *   pi_ui = exp(s_ui - lse_u)
+ * global_bias and user_bias[u] cancel in pi, so neither is ever trained: user biases keep their bits.  To be MAXIMISED:
+ *   L = sum_entries w (s_ui - lse_u) - 1/2 P_reg sum_(u < U) |p_u|^2 - 1/2 Q_reg sum_(i < I) |q_i|^2 - 1/2 item_bias_reg sum_(i < I) ib_i^2
+ * (plain regularisers, as in cu2rec_model_lmf, not n * reg; user_bias_reg is not read).
+ * CU2REC_SIDE_USERS, for every u < U:  g_u = sum_(entries of u) w q_i - W_u sum_(i < I) pi_ui q_i - P_reg p_u;  the user bias'
+ * gradient is a zero; a user without entries only shrinks.
+ * CU2REC_SIDE_ITEMS, for every i < I (on the item-major view the ALS calls cache on the cu2rec_csr):
+ *   g_i  = sum_(u has i) w p_u - sum_(u < U) W_u pi_ui p_u - Q_reg q_i
+ *   gb_i = sum_(u has i) w     - sum_(u < U) W_u pi_ui     - item_bias_reg ib_i
+ * Either side then takes cu2rec_model_lmf's AdaGrad step at hyper->learning_rate, with its unchanged-row rule and its count
+ * (*n_unchanged, may be NULL), ON THE SAME ACCUMULATORS: the model has one set, which cu2rec_model_lmf_state /
+ * cu2rec_model_lmf_reset expose and the logistic, the BPR and the softmax calls all move; reset them between trainers.  The user
+ * side adds a zero to the user bias and its accumulator.  Model rows past the CSR and the frozen side keep their bits.
+ * Nothing of size U x I is formed.  Every call first takes W_u (the row's values added in entry order) and lse_u: 32 users per
+ * workgroup against the items 128 at a time, scored in float32 on the matrix cores as cu2rec_model_lmf scores, with an online
+ * max and sum per user (per lane over its 16 scores, the two halves of the wavefront, the wavefront's steps, the four wavefronts
+ * in order; expf and logf, not the fast intrinsics).  The half-step then scores the pairs again -- the same bits, so
+ * exp(s_ui - lse_u) cannot overflow -- and pushes the coefficient (pi_ui, or W_u pi_ui on the item side) through a second
+ * matrix-core product against [partner rows | 1], as cu2rec_model_lmf pushes sigma.  Every sum's order is a function of the partner
+ * index or the entry's position alone, there are no float atomics: results are bit-identical run to run, and a user's lse and
+ * gradient from a one-row CSR of the same cols equal what it gets among all the others.
+ * Non-finite values behave as they fall out of the arithmetic.  A user whose lse_u is not finite (a NaN or an infinity among its
+ * factors, its bias or the item side) has a non-finite gradient: it is left unchanged and counted.  In an item half-step that
+ * user's coefficients W_u pi_ui are NaN for every item -- also where W_u = 0, since 0 x NaN is NaN -- so every item is left
+ * unchanged and counted.
+ * CU2REC_EINVAL, all checked before the device or the model is touched: a null m / train / hyper, a bad side, P_reg, Q_reg or
+ * item_bias_reg not finite or < 0, learning_rate not finite or <= 0, a CSR whose rows or cols exceed the model's.
+ * n_factors > CU2REC_ALS_MAX_FACTORS: CU2REC_EUNSUPPORTED.  A CSR with cols == 0 or nnz == 0 is a valid problem.  Single GPU.
+ * ---------------------------------------------------------------------------------------- */
+int cu2rec_model_softmax(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, int *n_unchanged);
+/* The gradient cu2rec_model_softmax would step along, to the host, shaped as cu2rec_model_lmf_gradient's (either may be NULL); the
+ * users' bias_grad_out is all zeros.  The model and the accumulators are untouched. */
+int cu2rec_model_softmax_gradient(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, int side, float *grad_out,
+                                  float *bias_grad_out);
+/* *L = the objective above at the model's current values: lse_u in float32 as the half-steps form it, the entries' scores, the
+ * term w (s_ui - lse_u) and every sum in double, the workgroups' partial sums added in order.  The same checks (no side), and L
+ * not NULL.  Reads the model only. */
+int cu2rec_model_softmax_objective(cu2rec_model *m, const cu2rec_csr *train, const cu2rec_hyper *hyper, double *L);
+/* lse_out (host, U floats) = lse_u of every user inside the CSR, as the half-steps form it; -inf where cols == 0.
+ * cu2rec_model_softmax_mass: mass_out (host, U floats) = sum_(i < I) pi_ui as the user half-step's matrix-core product forms it
+ * (its column of ones), 1 within rounding: a check of the two passes against each other.  CU2REC_EINVAL: a null argument, a CSR
+ * past the model's shape; CU2REC_EUNSUPPORTED as above.  Read the model only. */
+int cu2rec_model_softmax_lse(cu2rec_model *m, const cu2rec_csr *train, float *lse_out);
+int cu2rec_model_softmax_mass(cu2rec_model *m, const cu2rec_csr *train, float *mass_out);
+
+/* ------------------------------------------------------------------------------------------
  * train() -- replaces both overloads of train (training.h:12-15, training.cu:21-217):
  * total_iterations iterations; loss on train and test when i == 0, (i+1) % check_error == 0
  * or last (training.cu:118) printed as "TRAIN: Iteration %d GPU MAE: %f RMSE: %f" / "TEST: ..."
@@ -695,6 +748,13 @@ int cu2rec_train_lmf(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *
  * before the device or the model is touched. */
 int cu2rec_train_bpr(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, int verbose, double *objectives,
                      cu2rec_train_stats *stats);
+/* Softmax matrix factorization training: the accumulators (the logistic trainer's) are reset, then total_iterations sweeps of
+ * cu2rec_model_softmax -- the users, then the items when cfg->is_train -- at learning rate cfg->learning_rate (no decay), with the
+ * objective L evaluated at cu2rec_train_implicit's cadence, printed as "TRAIN: Iteration %d GPU softmax objective: %f" when
+ * `verbose`, and stored in objectives[i] (may be NULL; NaN elsewhere).  stats->updates = rows stepped.  cu2rec_model_softmax's
+ * checks with its codes, before the device or the model is touched. */
+int cu2rec_train_softmax(const cu2rec_csr *train, cu2rec_config *cfg, cu2rec_model *model, int verbose, double *objectives,
+                         cu2rec_train_stats *stats);
 
 /* ------------------------------------------------------------------------------------------
  * Sharding by user (multi-GPU; the reference is single device).  Host-side planner:
